@@ -1,8 +1,15 @@
 """Headline benchmark: rays/sec through the CR-NeRF rendering hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the outputs (--dump-outputs) and prints the line: headline rate,
+ms_per_step, the roofline of the render kernel and the per-step timing of the timed steps.  --full adds everything else below
+(direct_c_abi, cpu_baseline, parity, extra), measured after the timed steps in the same process.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32, float64 where
+the step computed float64; at most 64 MB in all, a fixed seeded sample of each array's elements beyond that).  The inputs are seeded,
+so two builds can be compared output for output.
 
 One step = one pass of the hot path over one batch of synthetic rays already resident in HBM:
 render_rays_cross_ray (coarse 64 + fine 64+128 samples, two 8x256 NeRF_sigma MLPs, compositing,
@@ -14,6 +21,7 @@ only collectives).  Rank 0 prints ONE JSON line.
 roofline: the dominant kernel is render_rays16_kernel (fp32 MFMA bound).  achieved = algorithmic MLP
 FLOPs per launch (1,233,152 FLOP/point x 256 points/ray x rays) / its average duration,
 measured live with HIP events on the launch stream.  peak = 157.3 TFLOP/s (fp32 MFMA, MI355X guide).
+--full only:
 cpu_baseline: the CPU oracle (plain-PyTorch restatement of the reference, oracle/cpu_ref.py) timed on
 this box's host cores on a bounded sample of the same workload; rank 0, N == 1 only.
 parity (with cpu_baseline, untimed): BASELINE's "PSNR vs ref" on the timed batch and on well-conditioned nets -- max-abs / rel-L2 of
@@ -47,7 +55,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=1024, help="rays per GPU per step (configs[1]: 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the direct C-ABI leg, the CPU baseline, parity, the other precisions / configs and the "
+                         "training steps (N == 1; off by default: a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline, parity and extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 or float64, <= 64 MB in all)")
     ap.add_argument("--precision", choices=["f32", "bf16", "f32x3", "f32h2"], default="f32",
                     help="f32 = BASELINE configs[1] on the fp32 MFMA (the headline, default); bf16 = the bf16 matrix-core kernel of configs[2]; "
                          "f32x3 = configs[1] in fp32 on the bf16 matrix cores (three-piece splits, six MFMAs per product; DESIGN 3.4b); "
@@ -468,6 +481,27 @@ def timed_steps(a, step, use_dist, dist, dev):
     return dt, last
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (float64 stays float64).  Past DUMP_LIMIT_BYTES in all, each
+    array keeps the same share of its elements, picked by a fixed seed from its flattened form (same shapes -> same elements)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        v = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        host[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(v.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def strong_configs2(a, dev, world, rank, use_dist, dist, exchange):
     """ONE configs[2] frame (default 800x800 = 640,000 rays, 64+128, cross-ray decoder on) split over the ranks: contiguous ray blocks,
     32,768-ray render chunks per rank, the decoder's two all-reduces + the RGB all-gather (parallel.decode_sharded)."""
@@ -508,6 +542,8 @@ def strong_configs2(a, dev, world, rank, use_dist, dist, exchange):
 
         dt, last = timed_steps(a, step, use_dist, dist, dev)
         torch.cuda.synchronize()
+        if a.dump_outputs and rank == 0:
+            write_outputs(a.dump_outputs, {"rgb": last})
         render_ms = sum(s.elapsed_time(e) for s, e in ev[-a.steps:]) / a.steps
     flops_local = FLOP_PER_POINT * (NC + NC + NI) * (hi - lo)
     peak = PEAK_BF16_MFMA_TFLOPS if prec in ("bf16", "f32x3", "f32h2") else PEAK_F32_MFMA_TFLOPS
@@ -558,6 +594,7 @@ def strong_configs4(a, dev, world, rank, use_dist, dist, exchange):
         lo, hi = parallel.shard_bounds(H * W, world, rank) if by_rays else (0, H * W)
         mine = range(a.frames) if by_rays else range(rank, a.frames, world)
         ev = []
+        kept = {}
 
         def step():
             a_emb = enc(style)                                   # once per style image (appearance_modification_video.py:239)
@@ -575,9 +612,12 @@ def strong_configs4(a, dev, world, rank, use_dist, dist, exchange):
                     img = pipeline.decode_image(m, res, H, W, a_emb).reshape(H, W, 3)
                 frame = (img.clamp(0, 1) * 255).to(torch.uint8)  # what the script writes out (:255-262); stays on the device here
                 checksum += frame.double().sum()
+                kept["last_frame"] = frame
             return checksum
 
         dt, last = timed_steps(a, step, use_dist, dist, dev)
+        if a.dump_outputs and rank == 0:
+            write_outputs(a.dump_outputs, {"last_frame": kept["last_frame"], "frames_checksum": last})
         total = last.clone()
         if use_dist and not by_rays:
             dist.all_reduce(total)                               # (untimed) the whole fly-through's checksum: every rank holds only its frames
@@ -653,6 +693,8 @@ def strong_configs3(a, dev, world, rank, use_dist, dist):
         return loss.detach()
 
     dt, last = timed_steps(a, step, use_dist, dist, dev)
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, {"loss": last})
     # One more step, instrumented: where the ray-SHARDED part (the two MLPs' render, forward and backward: 1 / N of it per rank) ends and the rest
     # begins.  Events: step start | features ready (render + all-gather done) | forward done | gradient arrives back at the features (everything
     # downstream of the render has been differentiated) | backward done | gradients synchronised + Adam done.
@@ -853,7 +895,7 @@ def main():
                 ev[i][2].record()
             if not direct:
                 host_stamp[i] = time.perf_counter()
-            return rgb
+            return rgb, out
 
         def fence():
             if use_dist:
@@ -862,31 +904,38 @@ def main():
 
         import gc
         for i in range(a.warmup):
-            last_rgb = step(i)
+            last_rgb, last_out = step(i)
         gc.collect()
         gc.disable()        # a generation-2 collection of torch's heap is a ~10 ms host pause: exposed if it lands on the first steps, before work is queued
+        direct_c_abi = None
         try:
             fence()
             t0 = time.perf_counter()
             for i in range(a.warmup, n_ev):
-                last_rgb = step(i)
+                last_rgb, last_out = step(i)
             t_enq = time.perf_counter()
             fence()
             dt = time.perf_counter() - t0
-            # the same steps through the C-ABI wrapper alone (ops.render_rays: what rounds 1-5 timed), outside the contract's timed region
-            td0 = time.perf_counter()
-            if not use_dist:                       # (N = 1 only: under torch.distributed these steps would add collectives to the record)
+            # --full: the same steps through the C-ABI wrapper alone (ops.render_rays: what rounds 1-5 timed), outside the contract's timed region
+            if a.full and not use_dist:            # (N = 1 only: under torch.distributed these steps would add collectives to the record)
+                td0 = time.perf_counter()
                 for i in range(a.warmup, n_ev):
                     step(i, direct=True)
-            td_enq = time.perf_counter()
-            fence()
-            dt_direct = time.perf_counter() - td0
+                td_enq = time.perf_counter()
+                fence()
+                dt_direct = time.perf_counter() - td0
+                direct_c_abi = {"ms_per_step": dt_direct / a.steps * 1e3, "host_enqueue_ms_per_step": (td_enq - td0) / a.steps * 1e3,
+                                "note": "the same steps through ops.render_rays (the ctypes wrapper of crnerf_render_rays_*: what rounds 1-5 timed), "
+                                        "run after the timed region"}
         finally:
             gc.enable()
         if use_dist:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if a.dump_outputs and rank == 0:
+            outs = {k: v for k, v in last_out.items() if k != "feature_fine_random"}   # (the same tensor as feature_fine)
+            write_outputs(a.dump_outputs, dict(outs, rgb=last_rgb))
         tev = ev[a.warmup:]
         kern_each = [s.elapsed_time(e) for s, e, _ in tev]
         step_each = [s.elapsed_time(d) for s, _, d in tev]                      # render launch .. end of the decode, on the device
@@ -902,9 +951,7 @@ def main():
                   "step_ms": _stats(step_each), "kernel_ms": _stats(kern_each), "device_gap_ms": _stats(gap_each), "host_enqueue_ms": _stats(host_each),
                   "host_enqueue_total_ms": (t_enq - t0) * 1e3, "wall_ms": dt * 1e3, "device_span_ms": tev[0][0].elapsed_time(tev[-1][2]),
                   "timed_through": "crnerf_amd.models.rendering.render_rays_cross_ray (the reference's signature, eval.py:39-52) + style_net.forward",
-                  "direct_c_abi": None if use_dist else {"ms_per_step": dt_direct / a.steps * 1e3, "host_enqueue_ms_per_step": (td_enq - td0) / a.steps * 1e3,
-                                   "note": "the same steps through ops.render_rays (the ctypes wrapper of crnerf_render_rays_*: what rounds 1-5 timed), "
-                                           "run after the timed region"},
+                  "direct_c_abi": direct_c_abi,
                   "gc": "gc.collect() + gc.disable() around the timed region (a generation-2 collection is a ~10 ms host pause; a training loop that "
                         "does not do the same pays it now and then -- the device queue hides it once a few steps are in flight)",
                   "note": "HIP events on the launch stream (render start / render end / decode end of every timed step) and perf_counter stamps after "
@@ -957,7 +1004,7 @@ def main():
                          "kernel_ms": kern_ms, "flops_per_launch": flops},
             "timing": timing,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # untimed legs; the headline line above must be printed whatever happens in them
             try:
                 line["cpu_baseline"] = cpu_baseline(rays_np, st_c, st_f, dst, grid_hw, style.cpu().contiguous())
@@ -981,7 +1028,7 @@ def main():
                 gc.freeze()     # what the legs above left on the heap (oracle tensors, fixtures) is not this step's garbage: without this every
                                 # generation-2 collection during the host-bound 1,024-ray steps walks it (6.3-7.0 ms per step against 5.3-5.8 in a process that only trains)
                 for tr, st in ((1024, 30), (16384, 6)):
-                    ta = argparse.Namespace(**dict(vars(a), train_rays=tr, steps=st, warmup=5, train_precision="auto"))
+                    ta = argparse.Namespace(**dict(vars(a), train_rays=tr, steps=st, warmup=5, train_precision="auto", dump_outputs=None))
                     tl = strong_configs3(ta, dev, 1, 0, False, None)
                     line.setdefault("extra", {})["train_step_%d" % tr] = {"ms_per_step": tl["ms_per_step"], "rays_per_s": tl["value"], "dtype": tl["dtype"], "steps": st,
                                                            "fp32_work_tflops": tl["roofline"]["fp32_work_tflops"], "workload": tl["config"]["workload"]}

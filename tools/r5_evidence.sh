@@ -5,11 +5,11 @@ set -u
 O=$GRAFT_REPO_ROOT/gpurun_out/r5e
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-python bench.py > $O/bench_f32.json 2> $O/bench_f32.err
+python bench.py --full > $O/bench_f32.json 2> $O/bench_f32.err
 (python -m pytest tests -m gpu -q 2>&1 | grep -E "^FAILED|passed|failed") > $O/gpu_suite.txt
 (CRNERF_TEST_COLD_L2=1 python -m pytest tests -m gpu -q -k "not multiproc and not fullsize and not converges" 2>&1 | grep -E "^FAILED|passed|failed") > $O/gpu_suite_cold_l2.txt
-python bench.py --precision f32h2 --no-cpu-baseline > $O/bench_f32h2.json 2> /dev/null
-python bench.py --precision bf16 --no-cpu-baseline > $O/bench_bf16.json 2> /dev/null
+python bench.py --precision f32h2 --full --no-cpu-baseline > $O/bench_f32h2.json 2> /dev/null
+python bench.py --precision bf16 --full --no-cpu-baseline > $O/bench_bf16.json 2> /dev/null
 python bench.py --scaling strong --workload configs2 --steps 3 --warmup 1 > $O/strong_configs2_n1.json 2> /dev/null
 python bench.py --scaling strong --workload configs3 --steps 4 --warmup 2 > $O/strong_configs3_n1.json 2> /dev/null
 python bench.py --scaling strong --workload configs3 --train-precision f32 --steps 3 --warmup 1 > $O/strong_configs3_f32_n1.json 2> /dev/null
