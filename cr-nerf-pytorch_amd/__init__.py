@@ -27,7 +27,11 @@ def set_precision(precision):
     core refuses runs on f32x3, a ray (a 128-point group) the h2 core poisoned is re-rendered on f32x3 inside the same call, so that no NaN of
     the h2 core's making reaches the caller (include/crnerf.h "auto"), or "bf16_hc": bf16 with an fp32-accurate COARSE pass ("auto" arithmetic on the
     coarse network's 25 % of the points, the fine network on the bf16 matrix cores: the fine depths then follow the fp32 reference;
-    models/rendering.py::_render_bf16_accurate_coarse).  A `precision=` keyword to render_rays_cross_ray / batched_inference /
+    models/rendering.py::_render_bf16_accurate_coarse), or "bf16_fc": bf16 with an FP16 coarse pass -- the coarse network with one-piece fp16
+    operands (11 significand bits instead of bf16's 8 at bf16's cost; include/crnerf.h "f16"), rays whose activations leave fp16's range re-rendered on
+    f32x3 inside the call, the fine network on the bf16 matrix cores (models/rendering.py::_render_bf16_f16_coarse): between "bf16" and "bf16_hc" in
+    accuracy, at about "bf16"'s frame time; "f16": both networks with fp16 operands (NaN rows where a point leaves fp16's range -- no repair).
+    A `precision=` keyword to render_rays_cross_ray / batched_inference /
     NeRF_sigma.forward overrides it per call.
     Training (grad mode) does not read this setting: its default is "auto" for the forward and the data gradient (fp32-accurate two-piece fp16
     splits on the fp16 matrix cores, f32x3 where the h2 core refuses) and f16x2 for the weight gradients (the same two-piece form, ranged per
@@ -36,8 +40,8 @@ def set_precision(precision):
     autograd.set_training_forward_precision("f32") / CRNERF_TRAIN_FWD=f32 and autograd.set_wgrad_precision("f32") / CRNERF_WGRAD_F32=1
     (every product on the fp32 matrix cores); autograd.set_training_precision("bf16") is the opt-in mixed-precision mode."""
     global _precision
-    from .ops import _is_auto, _is_bf16, _is_h2, _is_x3
-    _precision = "bf16_hc" if precision in ("bf16_hc", "bf16+h2c") else "auto" if _is_auto(precision) else "f32h2" if _is_h2(precision) else ("f32x3" if _is_x3(precision) else ("bf16" if _is_bf16(precision) else "f32"))
+    from .ops import _is_auto, _is_bf16, _is_f16, _is_h2, _is_x3
+    _precision = "bf16_fc" if precision in ("bf16_fc", "bf16+f16c") else "f16" if _is_f16(precision) else "bf16_hc" if precision in ("bf16_hc", "bf16+h2c") else "auto" if _is_auto(precision) else "f32h2" if _is_h2(precision) else ("f32x3" if _is_x3(precision) else ("bf16" if _is_bf16(precision) else "f32"))
 
 
 def get_precision():

@@ -30,6 +30,7 @@ EXPORTS = [
     "crnerf_render_rays_f32x3_repair", "crnerf_mlp_forward_f32x3_repair",
     "crnerf_render_rays_train_f32h2", "crnerf_render_rays_train_f32x3_repair", "crnerf_packed_mlp_t_h2_bytes", "crnerf_pack_mlp_weights_t_h2", "crnerf_mlp_backward_h2_f32", "crnerf_pack_mlp_weights_h2_async", "crnerf_pack_h2_status",
     "crnerf_packed_mlp_x3_bytes", "crnerf_pack_mlp_weights_x3", "crnerf_mlp_forward_f32x3", "crnerf_render_rays_f32x3", "crnerf_render_rays_train_f32x3", "crnerf_packed_mlp_t_x3_bytes", "crnerf_pack_mlp_weights_t_x3", "crnerf_mlp_backward_x3_f32", "crnerf_packed_mlp_bf16_bytes", "crnerf_pack_mlp_weights_bf16", "crnerf_mlp_forward_bf16", "crnerf_render_rays_bf16", "crnerf_render_rays_bf16_fine",
+    "crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16",
     "crnerf_decoder_content_backward_workspace_bytes", "crnerf_decoder_content_backward_f32",
     "crnerf_encoder_train_saved_bytes", "crnerf_encoder_train_scratch_bytes", "crnerf_encoder_forward_train_f32", "crnerf_encoder_backward_f32",
     "crnerf_encoder_train_band_saved_bytes", "crnerf_encoder_train_band_scratch_bytes", "crnerf_encoder_forward_train_band_f32", "crnerf_encoder_backward_band_f32",
@@ -183,6 +184,10 @@ def load():
             "crnerf_packed_mlp_bf16_bytes": (ctypes.c_size_t, []),
             "crnerf_pack_mlp_weights_bf16": (ctypes.c_int, [pp, vp, vp]),
             "crnerf_mlp_forward_bf16": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
+            "crnerf_packed_mlp_f16_bytes": (ctypes.c_size_t, []),
+            "crnerf_pack_mlp_weights_f16": (ctypes.c_int, [pp, vp, vp]),
+            "crnerf_mlp_forward_f16": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
+            "crnerf_render_rays_f16": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
             "crnerf_crossray_chansum_f32": (ctypes.c_int, [vp, i64, vp, vp, vp]),
             "crnerf_crossray_gram_f32": (ctypes.c_int, [vp, i64, vp, pp, vp, vp, vp]),
             "crnerf_crossray_matrix_f32": (ctypes.c_int, [vp, f64, vp, vp, vp, vp]),

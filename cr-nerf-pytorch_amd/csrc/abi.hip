@@ -230,8 +230,9 @@ int crnerf_sample_pdf_merge_f32(const float* z_coarse, const float* weights_coar
 }
 
 // x3: 0 = no, 1 = the x3 core (three bf16 pieces), 2 = the h2 core (two fp16 pieces), 3 = the x3 core repairing NaN ray quads
+// bf16: the pair core (no in-kernel draws); f16: its fp16-operand build
 static int render_rays_common(const crnerf_render_args* a, void* stream, bool bf16, void* acts_c = nullptr, void* acts_f = nullptr,
-                              float* raw_c = nullptr, float* raw_f = nullptr, int x3 = 0) {
+                              float* raw_c = nullptr, float* raw_f = nullptr, int x3 = 0, bool f16 = false) {
   REQUIRE(a, "args");
   if (a->n_rays == 0) return 0;
   if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays: negative n_rays");
@@ -262,6 +263,7 @@ static int render_rays_common(const crnerf_render_args* a, void* stream, bool bf
   if (x3 == 2) return launch_render_rays_h2(r, (hipStream_t)stream);
   if (x3 == 3) r.repair = 1;
   if (x3) return launch_render_rays_x3(r, (hipStream_t)stream);
+  if (f16) return launch_render_rays_f16p(r, (hipStream_t)stream);     // inference only
   if (bf16) return launch_render_rays_bf16p(r, (hipStream_t)stream);   // inference and (acts_c) the mixed-precision training twin
   return launch_render_rays16(r, (hipStream_t)stream);                 // inference and (acts_c) the fp32 training twin
 }
@@ -485,6 +487,24 @@ int crnerf_mlp_forward_bf16(const void* packed, const float* x, float* out, int6
   if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_bf16: negative n");
   return launch_mlp_forward_bf16p(packed, x, out, (long)n, sigma_only, (hipStream_t)stream);
 }
+
+size_t crnerf_packed_mlp_f16_bytes(void) { return PACKEDB_BYTES; }
+
+int crnerf_pack_mlp_weights_f16(const float* const* tensors, void* packed, void* stream) {
+  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
+  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
+    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_f16: a tensor pointer is NULL");
+  return launch_pack_mlp_f16(to_tensors(tensors), packed, (hipStream_t)stream);
+}
+
+int crnerf_mlp_forward_f16(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
+  if (n == 0) return 0;
+  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
+  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_f16: negative n");
+  return launch_mlp_forward_f16p(packed, x, out, (long)n, sigma_only, (hipStream_t)stream);
+}
+
+int crnerf_render_rays_f16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, true, nullptr, nullptr, nullptr, nullptr, 0, true); }
 
 size_t crnerf_encoder_workspace_bytes(int H, int W) { return encoder_workspace_bytes(H, W); }
 

@@ -130,6 +130,7 @@ struct RenderArgs {
 int launch_render_rays16(const RenderArgs& a, hipStream_t stream);
 int launch_mlp_forward16(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);
 int launch_pack_mlp_bf16(const MlpTensors& t, void* packed, hipStream_t stream);
+int launch_pack_mlp_f16(const MlpTensors& t, void* packed, hipStream_t stream);   // the bf16 layout with fp16 elements; -4 when a weight does not fit fp16
 int launch_pack_mlp_x3(const MlpTensors& t, void* packed, hipStream_t stream);
 int launch_mlp_forward_x3(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream, int repair);
 int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream);
@@ -149,6 +150,9 @@ int launch_mlp_dgrad_x3(const void* packedT_x3, const float* out, const float* d
                         hipStream_t stream, const int* only_if = nullptr);
 int launch_mlp_forward_bf16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);   // pair core: the module entry
 int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream);
+// the pair core with one-piece fp16 operands and a range guard (mlp_forward_bf16p_f16.hip, render_fused_bf16p_f16.hip; inference only)
+int launch_mlp_forward_f16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);
+int launch_render_rays_f16p(const RenderArgs& a, hipStream_t stream);
 int launch_rng_fill(float* out, long R, int n, unsigned long long seed, int stream_id, long ray_offset, hipStream_t stream);   // one ray per wave PAIR, 32-point tiles, two waves per SIMD (render_fused_bf16p.hip)
 
 

@@ -12,12 +12,29 @@
 #include <hip/hip_runtime.h>
 #include "layout.h"
 #include "mlp_core.h"
+#include "sincos_pow2.h"
 
 namespace crnerf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// CRNERF_P_F16 = 1 (mlp_forward_bf16p_f16.hip, render_fused_bf16p_f16.hip): the same core with ONE-PIECE FP16 operands -- 11 significand bits instead of 8, one
+// v_mfma_f32_32x32x16_f16 per product (same shape and fragment layout as the _bf16 instruction), v_cvt_pk_f16_f32 where the bf16 build has
+// v_cvt_pk_bf16_f32 -- and the range guard fp16's 65,504 needs (mlp_core_bf16p.h "Range guard").  Everything whose code depends on the operand
+// type lives in the inline namespace pcore_f16 there, so the two builds of this header never share a symbol.  0: the bf16 core, untouched.
+#ifndef CRNERF_P_F16
+#define CRNERF_P_F16 0
+#endif
+#if CRNERF_P_F16
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+#define CRNERF_MFMA_P(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)
+#else
+#define CRNERF_MFMA_P(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
+#endif
 
 #ifndef CRNERF_B_AHEAD
 #define CRNERF_B_AHEAD 4
@@ -91,10 +108,30 @@ constexpr int B_RING = 4;
 static_assert(STAGESB_PER_PASS % B_RING == 0, "the static ring needs a whole number of ring turns per pass");
 static_assert(B_RING * STAGE_BYTES <= 65536 && B_RING <= RING_SLOTS, "ds_read offsets are 16 bits; the LDS ring area is shared with the fp32 core");
 
+#if CRNERF_P_F16
+inline namespace pcore_f16 {
+// the operand pair of the fp16 build (the name is kept: every caller packs "the core's operand type").  Inline asm: from {(_Float16)a, (_Float16)b}
+// hipcc emits two v_cvt_f16_f32 and a v_pack_b32_f16.  RNE (the kernel's default rounding mode); beyond 65,504 the result is inf, which the
+// range guard looks for; fp16 subnormals are kept (include/crnerf.h "f16").  No MFMA reads the result within two wait states: every caller
+// packs whole k-steps ahead of the tile's first MFMA.
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
+  uint32_t v;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(v) : "v"(a), "v"(b));   // element 0 = low half
+  return v;
+}
+// running range guard: g = max over both 16-bit halves of |operand| as an integer (fp16 magnitudes order like unsigned integers); inf / NaN <=> >= 0x7C00
+constexpr uint32_t F16_INF_BITS = 0x7C00u;
+__device__ __forceinline__ uint32_t guard_max(uint32_t g, uint32_t nonneg_pair) {   // v_pk_max_u16; the halves must have their sign bits clear
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, g), __builtin_bit_cast(u16x2, nonneg_pair)));
+}
+__device__ __forceinline__ uint32_t guard_max_signed(uint32_t g, uint32_t pair) { return guard_max(g, pair & 0x7fff7fffu); }
+__device__ __forceinline__ bool guard_tripped(uint32_t g) { return (g & 0xffffu) >= F16_INF_BITS || (g >> 16) >= F16_INF_BITS; }
+#else
 __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
   const bf16x2 v = {(__bf16)a, (__bf16)b};   // v_cvt_pk_bf16_f32 (RNE); element 0 = low half
   return __builtin_bit_cast(uint32_t, v);
 }
+#endif
 // ---- epilogues -------------------------------------------------------------------------------------------
 // Issue budget (tools/ubench/gen_mfma_stream.py, one wave per SIMD): beside a v_mfma_f32_32x32x16_bf16 up to FOUR
 // other instructions per MFMA gap are free (32.7 cycles/MFMA with 8 fillers per k-step split 4 + 4); 10 per k-step cost
@@ -171,9 +208,15 @@ __device__ __forceinline__ void posenc_b(float x, float y, float z, int h, u32x4
         const Revolutions r1 = d1 == 0 ? rx : (d1 == 1 ? ry : rz);
         const float P = h ? r1.p : r0.p, E = h ? r1.e : r0.e;
         const int fe = h ? f1 : f0;
+#if CRNERF_P_F16
+        // fp16 keeps 11 significand bits of the embedding: the hardware v_sin_f32 / v_cos_f32 (good for bf16's 8, see above) are not accurate enough
+        // for it, so the fp16 build takes the fp32 renderers' routine (sincos_pow2.h: ~1.3 ulp, 26 VALU per pair) on the same two-float revolutions
+        sincos_rev2pi(Rev2Pi{P, E}, fe, sn, cs);
+#else
         const float t = __builtin_amdgcn_fractf(ldexpf(P, fe)) + ldexpf(E, fe);
         sn = __builtin_amdgcn_sinf(t);
         cs = __builtin_amdgcn_cosf(t);
+#endif
       }
       const float e0_0 = trig0 ? sn : (a0 == 3 * F ? x : (a0 == 3 * F + 1 ? z : 0.0f));
       const float e0_1 = trig0 ? cs : (a0 == 3 * F ? y : 0.0f);
@@ -183,4 +226,7 @@ __device__ __forceinline__ void posenc_b(float x, float y, float z, int h, u32x4
     }
 }
 
+#if CRNERF_P_F16
+}  // inline namespace pcore_f16
+#endif
 }  // namespace crnerf

@@ -172,10 +172,28 @@ constexpr int SAVE_LDS_ROW = 128 + 16;         // one point's bytes of a tile pa
 constexpr int SAVE_LDS_WAVE = 32 * SAVE_LDS_ROW;
 struct NoSaveP {
   static constexpr bool on = false;
+  static constexpr bool guard = false;
   __device__ __forceinline__ void drain() {}
 };
+#if CRNERF_P_F16
+// Range guard (fp16 build; inference only).  fp16 ends at 65,504: an operand beyond it converts to inf, and inf through the softplus is alpha = 1 --
+// a finite, wrong pixel.  So a tile carries ONE register `g` through its layers, the running maximum of |operand| over everything it converts
+// (both embeddings, every layer's output), kept as the packed fp16 bit patterns: after the relu both halves are non-negative and order like
+// unsigned integers, so the update is one v_pk_max_u16 per epilogue quarter (three VALU instead of two; xyz_encoding_final's un-relu'd output takes a
+// v_and_b32 for the sign bits first: four), and the test is two integer compares per tile: a half >= 0x7C00 is inf or NaN.  A point that trips
+// it gets its 65 outputs replaced by NaN (mlp_tile_p), as in the h2 core (mlp_core_h2.h); the fused renderer then writes a NaN feature row for the
+// ray, which is what crnerf_render_rays_f32x3_repair looks for.  A negative overflow in front of a relu is not an error (relu(-inf) = 0 is the
+// fp32 result too) and does not trip it.  The object rides where the training twin's saver does: one per tile, handed to every epilogue.
+struct GuardSaveP {
+  static constexpr bool on = false;
+  static constexpr bool guard = true;
+  uint32_t g = 0;
+  __device__ __forceinline__ void drain() {}
+};
+#endif
 struct ActSaveP {
   static constexpr bool on = true;
+  static constexpr bool guard = false;
   const char* acts;      // scalar: this pass' buffer
   long slot_bytes;       // scalar: P * 512
   long P;                // scalar
@@ -262,6 +280,15 @@ struct SaveSlot<NoSaveP> {
   template <bool BITS>
   __device__ __forceinline__ void step(NoSaveP&, const u32x4 (&)[KS_HID], int, int) {}
 };
+#if CRNERF_P_F16
+template <>
+struct SaveSlot<GuardSaveP> {
+  template <bool BITS>
+  __device__ __forceinline__ void set(const GuardSaveP&, int) {}
+  template <bool BITS>
+  __device__ __forceinline__ void step(GuardSaveP&, const u32x4 (&)[KS_HID], int, int) {}
+};
+#endif
 
 // ---- the static store schedule of one tile (what ActSaveP::drain / SaveSlot::step issue where mma_layer_p calls them), for the ring's vmcnt
 struct PLayerSched { int fbase, nt, ns, prev_kind, epi_kind, pt; };   // kind 0: stores nothing, 1: rows, 2: rows + activity bits
@@ -314,6 +341,9 @@ static_assert(P_STORES.ok && p_store_total() == 9 * 16 + 8 + 8 * 4 + 2, "store s
 // kernel 128 VGPR + 128 AGPR (SIRegisterInfo: usesAGPRs => MaxNumVGPRs /= 2), which does not hold the two 64-register
 // activation buffers -- and a VGPR accumulator needs no v_accvgpr_read: a quarter is TWO VALU instructions.  The asm
 // statements pin each quarter to the k-step it was written in (see PackEpi in mlp_core_bf16.h).
+#if CRNERF_P_F16
+inline namespace pcore_f16 {
+#endif
 struct NoEpiP {
   static constexpr bool saving = false;
   __device__ __forceinline__ void prefetch(int) {}
@@ -333,10 +363,30 @@ struct PackEpiP {
   __device__ __forceinline__ void prefetch(int) {}
   __device__ __forceinline__ void finish(int T, int qc, const f32x16& acc) {
     uint32_t pk;
+#if CRNERF_P_F16
+    // v_pk_max_i16 x, 0 is a relu for packed fp16 as it is for bf16 (a negative value, -0 and -inf included, is a negative int16).  The guard's
+    // instructions sit in the same statement: pinned to this k-step like the conversion.  (pk is read by an MFMA no earlier than the next tile's
+    // k-step 14 / the next layer: far beyond the two wait states a VALU write needs; tools/isa_audit.py checks every build.)
+    if constexpr (SV::guard) {
+      if (RELU) {
+        asm volatile("v_cvt_pk_f16_f32 %0, %2, %3\n\tv_pk_max_i16 %0, %0, 0\n\tv_pk_max_u16 %1, %1, %0" : "=v"(pk), "+v"(sv.g) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
+      } else {
+        uint32_t mag;
+        asm volatile("v_cvt_pk_f16_f32 %0, %3, %4\n\tv_and_b32 %2, 0x7fff7fff, %0\n\tv_pk_max_u16 %1, %1, %2"
+                     : "=v"(pk), "+v"(sv.g), "=v"(mag) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
+      }
+    } else {
+      if (RELU)
+        asm volatile("v_cvt_pk_f16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0" : "=v"(pk) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
+      else
+        asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(pk) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
+    }
+#else
     if (RELU)
       asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\tv_pk_max_i16 %0, %0, 0" : "=v"(pk) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
     else
       asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(acc[2 * qc]), "v"(acc[2 * qc + 1]));
+#endif
     dst[2 * T + (qc >> 2)][qc & 3] = pk;
   }
 };
@@ -364,6 +414,12 @@ struct SigmaEpiP {
     float x0 = acc[2 * qc], x1 = acc[2 * qc + 1];
     asm volatile("" : "+v"(x0), "+v"(x1));
     dst[2 * T + (qc >> 2)][qc & 3] = pack_pair<true>(x0, x1);
+#if CRNERF_P_F16
+    if constexpr (SV::guard) {
+      sv.g = guard_max(sv.g, dst[2 * T + (qc >> 2)][qc & 3]);
+      asm volatile("" : "+v"(sv.g));
+    }
+#endif
     sg = fmaf(wv[qc >> 1][e], fmaxf(x0, 0.0f), sg);
     sg = fmaf(wv[qc >> 1][e + 1], fmaxf(x1, 0.0f), sg);
     asm volatile("" : "+v"(sg));
@@ -422,7 +478,7 @@ __device__ __forceinline__ void mma_layer_p(WeightPipeP& p, const u32x4 (&srcA)[
       u32x4 af = q[i % B_AHEAD];
       asm volatile("" : "+v"(af));   // ties this k-step's MFMA into the side-effect chain (see the epilogue notes in mlp_core_bf16.h)
       const u32x4 b = s < NSA ? srcA[s < NSA ? s : 0] : srcB[s < NSA ? 0 : s - NSA];
-      accs[cur] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, b), accs[cur], 0, 0, 0);
+      accs[cur] = CRNERF_MFMA_P(af, b, accs[cur]);
       __builtin_amdgcn_sched_barrier(0);   // MFMA first, its fillers behind it
       if (p_piece_at(i, P_STAGGER) >= 0) p.issue_piece(p_piece_at(i, P_STAGGER), i / STAGE_FRAGS + B_RING - 1);
       q[i % B_AHEAD] = p.read(b_pos(i + B_AHEAD));
@@ -511,6 +567,18 @@ __device__ __forceinline__ void mlp_tile_p(WeightPipeP& p, int model, int next_m
   u32x4 dv[KS_DIR];
 #pragma unroll
   for (int s = 0; s < KS_DIR; ++s) dv[s] = *(const __attribute__((address_space(3))) u32x4*)(dirsrc + 32 * s);
+#if CRNERF_P_F16
+  if constexpr (SV::guard) {   // the two embeddings (un-relu'd: sign bits masked); 32 dwords per tile
+#pragma unroll
+    for (int s = 0; s < KS_XYZ; ++s)
+#pragma unroll
+      for (int d = 0; d < 4; ++d) sv.g = guard_max_signed(sv.g, pe[s][d]);
+#pragma unroll
+    for (int s = 0; s < KS_DIR; ++s)
+#pragma unroll
+      for (int d = 0; d < 4; ++d) sv.g = guard_max_signed(sv.g, dv[s][d]);
+  }
+#endif
   tm.tick(T_SIGMA);
   eB.slot(9);
   mma_layer_p<4, KS_HID, KS_DIR, OFFB_DIR, 72, 7>(p, actA, dv, q, accs, C + C_BDIR, C + C_BRGB, h, efin, eB, sv);                      // dir_encoding
@@ -520,7 +588,24 @@ __device__ __forceinline__ void mlp_tile_p(WeightPipeP& p, int model, int next_m
   for (int qc = 0; qc < 8; ++qc) {   // rgb's last tile: nothing left to hide it behind
     ergb.finish(1, qc, accs[(76 + 1) & 1]);
   }
+#if CRNERF_P_F16
+  if constexpr (SV::guard) {   // an operand of this point left fp16's range (either lane half holds half of its operands): NaN out, not a finite wrong answer
+    uint32_t g = sv.g;
+    g = guard_max(g, (uint32_t)__shfl_xor((int)g, 32));
+    if (guard_tripped(g)) {
+      const float poison = __uint_as_float(0x7fc00000u);   // (by bit pattern: the build has -fno-honor-nans)
+      sigma = poison;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) feat[t][r] = poison;
+    }
+  }
+#endif
   tm.tick(T_EPILOGUE);
 }
 
+#if CRNERF_P_F16
+}  // inline namespace pcore_f16
+#endif
 }  // namespace crnerf

@@ -6,7 +6,17 @@
 #include "kernels.h"
 #include "mlp_core_bf16p.h"
 
+// mlp_forward_bf16p_f16.hip builds this unit a second time with CRNERF_P_F16 = 1 (fp16 operands + range guard, see mlp_core_bf16.h) under its own names
+#ifndef CRNERF_P_MLP_KERNEL
+#define CRNERF_P_MLP_KERNEL mlp_forward_bf16p_kernel
+#define CRNERF_P_MLP_LAUNCH launch_mlp_forward_bf16p
+#define CRNERF_P_MLP_NAME "mlp_forward_bf16p_kernel"
+#endif
+
 namespace crnerf {
+#if CRNERF_P_F16
+inline namespace pcore_f16 {
+#endif
 
 constexpr int LDS_DIR_M = LDS_SCRATCH_P;                    // 8 waves x 64 lanes x 64 B: every POINT's direction embedding as B operands (dword 32 s)
 constexpr int LDS_TOTAL_M = LDS_DIR_M + P_WAVES * 64 * 64;
@@ -31,7 +41,7 @@ __device__ __forceinline__ void gather_embedded_p(const float* __restrict__ row,
     }
 }
 
-__global__ __launch_bounds__(512, 2) void mlp_forward_bf16p_kernel(const char* __restrict__ packed, const float* __restrict__ x, float* __restrict__ out,
+__global__ __launch_bounds__(512, 2) void CRNERF_P_MLP_KERNEL(const char* __restrict__ packed, const float* __restrict__ x, float* __restrict__ out,
                                                                    int sigma_only, long P, int iters) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* lds = (lds_char*)smem;
@@ -40,6 +50,10 @@ __global__ __launch_bounds__(512, 2) void mlp_forward_bf16p_kernel(const char* _
   const int p = lane & 31, h = lane >> 5;
 
   load_consts(lds, packed, packed);
+#if CRNERF_P_F16
+  // a pack that carries the range flag (a weight beyond fp16; crnerf_pack_mlp_weights_f16 has already refused it): NaN out, as the h2 kernels do
+  const bool refused = __float_as_uint(((const lds_float*)(lds + LDS_CONST0))[H2_FLAG_WORD]) != 0u;
+#endif
   lds_char* dirbuf = lds + LDS_DIR_M + wave * (64 * 64) + lane * 64;   // this lane's own 2 x 16 bytes (the fused renderer parks ONE embedding per ray)
   WeightPipeP pipe;
   pipe.start(lds, packed + CONST_BYTES, packed + CONST_BYTES, 0, lane, wave);
@@ -47,7 +61,9 @@ __global__ __launch_bounds__(512, 2) void mlp_forward_bf16p_kernel(const char* _
   pipe.prime(q);
   PhaseTimer tm;
   tm.start(false);
+#if !CRNERF_P_F16
   NoSaveP sv;
+#endif
 
 #pragma unroll 1
   for (int it = 0; it < iters; ++it) {
@@ -65,7 +81,19 @@ __global__ __launch_bounds__(512, 2) void mlp_forward_bf16p_kernel(const char* _
     for (int s = 0; s < KS_DIR; ++s) *(__attribute__((address_space(3))) u32x4*)(dirbuf + 32 * s) = dv[s];
     f32x16 feat[2];
     float sigma;
+#if CRNERF_P_F16
+    GuardSaveP sv;   // one range guard per tile
+#endif
     mlp_tile_p(pipe, 0, 0, pe, dirbuf, feat, sigma, h, q, tm, sv);   // (reads its lane's dirbuf after its own writes: same wave, in order)
+#if CRNERF_P_F16
+    if (refused) {
+      sigma = __uint_as_float(0x7fc00000u);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) feat[t][r] = sigma;
+    }
+#endif
     if (valid) {
       if (sigma_only) {
         if (h == 0) out[n] = sigma;
@@ -82,15 +110,19 @@ __global__ __launch_bounds__(512, 2) void mlp_forward_bf16p_kernel(const char* _
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int launch_mlp_forward_bf16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream) {
+#if CRNERF_P_F16
+}  // inline namespace pcore_f16
+#endif
+
+int CRNERF_P_MLP_LAUNCH(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream) {
   if (P <= 0) return 0;
   const long groups = (P + 255) / 256;  // 256 points per workgroup-iteration (eight 32-point tiles)
   const int cus = num_cus();
   const int grid = (int)(groups < cus ? groups : cus);
   const int iters = (int)((groups + grid - 1) / grid);
-  if (int rc = ensure_dynamic_lds((const void*)mlp_forward_bf16p_kernel, LDS_TOTAL_M, "mlp_forward_bf16p_kernel")) return rc;
-  hipLaunchKernelGGL(mlp_forward_bf16p_kernel, dim3(grid), dim3(512), LDS_TOTAL_M, stream, (const char*)packed, x, out, sigma_only, P, iters);
-  return check_launch("mlp_forward_bf16p_kernel");
+  if (int rc = ensure_dynamic_lds((const void*)CRNERF_P_MLP_KERNEL, LDS_TOTAL_M, CRNERF_P_MLP_NAME)) return rc;
+  hipLaunchKernelGGL(CRNERF_P_MLP_KERNEL, dim3(grid), dim3(512), LDS_TOTAL_M, stream, (const char*)packed, x, out, sigma_only, P, iters);
+  return check_launch(CRNERF_P_MLP_NAME);
 }
 
 }  // namespace crnerf

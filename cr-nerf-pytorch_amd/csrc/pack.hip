@@ -99,7 +99,10 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
   return (unsigned short)(u >> 16);
 }
 
-__global__ void pack_stream_bf16_kernel(MlpTensors t, unsigned short* __restrict__ stream) {
+// F16: the same fragment order with fp16 elements (crnerf_pack_mlp_weights_f16), round-to-nearest-even, subnormals kept; a weight fp16 cannot hold --
+// not finite, or beyond 65,504 -- raises the pack's range flag (the h2 packs' word and convention, layout.h H2_FLAG_WORD)
+template <bool F16>
+__global__ void pack_stream_bf16_kernel(MlpTensors t, unsigned short* __restrict__ stream, int* __restrict__ range_flag) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)STREAMB_FRAGS * 512) return;
   const int frag = (int)(idx / 512);
@@ -137,7 +140,14 @@ __global__ void pack_stream_bf16_kernel(MlpTensors t, unsigned short* __restrict
     default: col = CRNERF_HID_FEATURE(s); break;
   }
   #undef CRNERF_HID_FEATURE
-  stream[idx] = col >= 0 ? f32_to_bf16_rne(W[(long)row * in_dim + col]) : (unsigned short)0;
+  if (!F16) {
+    stream[idx] = col >= 0 ? f32_to_bf16_rne(W[(long)row * in_dim + col]) : (unsigned short)0;
+    return;
+  }
+  if (col < 0) { stream[idx] = 0; return; }
+  const float w = W[(long)row * in_dim + col];
+  if ((__float_as_uint(w) & 0x7fffffffu) > 0x477fe000u) atomicOr(range_flag, 1);   // |w| > 65,504, inf or NaN (bit test: this unit is built with -fno-honor-nans)
+  stream[idx] = __builtin_bit_cast(unsigned short, (_Float16)w);
 }
 
 int launch_pack_mlp_bf16(const MlpTensors& t, void* packed, hipStream_t stream) {
@@ -145,8 +155,25 @@ int launch_pack_mlp_bf16(const MlpTensors& t, void* packed, hipStream_t stream) 
   unsigned short* wstream = (unsigned short*)((char*)packed + CONST_BYTES);
   hipLaunchKernelGGL(pack_consts_kernel, dim3((CONST_BYTES / 4 + 255) / 256), dim3(256), 0, stream, t, consts, 1.0f);
   const long n = (long)STREAMB_FRAGS * 512;
-  hipLaunchKernelGGL(pack_stream_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t, wstream);
+  hipLaunchKernelGGL(pack_stream_bf16_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t, wstream, (int*)nullptr);
   return check_launch("pack_mlp_bf16");
+}
+
+// fp16 pack: the bf16 pack's layout with fp16 elements.  Waits for the stream to read the range flag, like launch_pack_mlp_h2: packing happens once
+// per set of weights, and a weight beyond fp16 would otherwise render as inf.
+int launch_pack_mlp_f16(const MlpTensors& t, void* packed, hipStream_t stream) {
+  float* consts = (float*)packed;
+  unsigned short* wstream = (unsigned short*)((char*)packed + CONST_BYTES);
+  hipLaunchKernelGGL(pack_consts_kernel, dim3((CONST_BYTES / 4 + 255) / 256), dim3(256), 0, stream, t, consts, 1.0f);
+  const long n = (long)STREAMB_FRAGS * 512;
+  int flag = 0;
+  int* dflag = (int*)consts + H2_FLAG_WORD;
+  hipLaunchKernelGGL(pack_stream_bf16_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t, wstream, dflag);
+  if (int rc = check_launch("pack_mlp_f16")) return rc;
+  if (hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+    return set_error(-10, "pack_mlp_f16: reading the range flag failed");
+  if (flag) return set_error(-4, "pack_mlp_weights_f16: a weight is outside fp16's range (|w| <= 65,504, finite); use the bf16, f32h2 / f32x3 or fp32 entry points");
+  return 0;
 }
 
 // x3 stream (layout.h "fragX"): one thread per bf16 element; the three pieces of a weight by repeated round-to-nearest-even

@@ -16,7 +16,20 @@
 #include "pair_ops.h"
 #include "ray_ops.h"
 
+// render_fused_bf16p_f16.hip builds this unit a second time with CRNERF_P_F16 = 1 (fp16 operands + range guard, see mlp_core_bf16.h) under its own names:
+// the inference kernel only -- the training twin and the fine-only kernel stay bf16
+#ifndef CRNERF_P_RENDER_KERNEL
+#define CRNERF_P_RENDER_KERNEL render_rays_bf16p_kernel
+#define CRNERF_P_RENDER_LAUNCH launch_render_rays_bf16p
+#define CRNERF_P_RENDER_SCHED crnerf_sched_bf16p
+#define CRNERF_P_RENDER_NAME "render_rays_bf16p_kernel"
+#define CRNERF_P_RENDER_WHAT "render_rays_bf16"
+#endif
+
 namespace crnerf {
+#if CRNERF_P_F16
+inline namespace pcore_f16 {
+#endif
 
 struct RenderParamsP {
   const char* packed0; const char* packed1;
@@ -40,7 +53,11 @@ static_assert(LDS_TOTAL_TRAIN_P <= 160 * 1024 && LDS_STAGE_P % 16 == 0, "LDS bud
 // kernel instantiates the no-op hook.
 struct NoHookP {
   static constexpr bool on = false;
+#if CRNERF_P_F16
+  __device__ __forceinline__ GuardSaveP saver(int, long, int, int, int, bool, int, int, lds_char*) const { return GuardSaveP(); }   // one range guard per tile
+#else
   __device__ __forceinline__ NoSaveP saver(int, long, int, int, int, bool, int, int, lds_char*) const { return NoSaveP(); }
+#endif
 };
 struct TrainHookP {
   static constexpr bool on = true;
@@ -69,7 +86,7 @@ struct TrainHookP {
   }
 };
 
-static __device__ unsigned int crnerf_sched_bf16p[SCHED_SLOTS][2];   // kernels.h "Dynamic work distribution"
+static __device__ unsigned int CRNERF_P_RENDER_SCHED[SCHED_SLOTS][2];   // kernels.h "Dynamic work distribution"
 #ifdef CRNERF_TIMING
 static __device__ unsigned long long crnerf_wg_times_p[2 * 1024];
 #endif
@@ -110,6 +127,17 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
   PhaseTimer tm;
   tm.start(blockIdx.x == 0 && threadIdx.x == 0);
   load_consts(lds, a.packed0, a.packed1);
+#if CRNERF_P_F16
+  // a pack that carries the range flag (a weight beyond fp16; crnerf_pack_mlp_weights_f16 has already refused it): nothing is rendered, every ray
+  // is marked NaN where crnerf_render_rays_f32x3_repair looks for it -- the h2 kernels' convention (render_fused_x3.hip)
+  if ((__float_as_uint(((const lds_float*)(lds + LDS_CONST0))[H2_FLAG_WORD]) | __float_as_uint(((const lds_float*)(lds + LDS_CONST1))[H2_FLAG_WORD])) != 0u) {
+    for (long rr = (long)blockIdx.x * 512 + threadIdx.x; rr < a.R; rr += (long)gridDim.x * 512) {
+      a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+      if (a.Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+    }
+    return;
+  }
+#endif
   PairScratch scr;
   scr.bind(lds + LDS_SCRATCH_P + pair * PAIR_BYTES);
   lds_char* dirbuf = lds + LDS_DIR_P + wave * 64;
@@ -283,16 +311,22 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
 #endif
 }
 
-__global__ __launch_bounds__(512, 2) void render_rays_bf16p_kernel(RenderParamsP a) { render_rays_bf16p_body(a, NoHookP()); }
+__global__ __launch_bounds__(512, 2) void CRNERF_P_RENDER_KERNEL(RenderParamsP a) { render_rays_bf16p_body(a, NoHookP()); }
+#if !CRNERF_P_F16
 __global__ __launch_bounds__(512, 2) void render_rays_train_bf16p_kernel(RenderParamsP a, TrainHookP hook) { render_rays_bf16p_body(a, hook); }
 __global__ __launch_bounds__(512, 2) void render_rays_bf16p_fine_kernel(RenderParamsP a) { render_rays_bf16p_body<NoHookP, true>(a, NoHookP()); }
+#endif
 
-int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream) {
+#if CRNERF_P_F16
+}  // inline namespace pcore_f16
+#endif
+
+int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   if (a.R <= 0) return 0;
-  if (a.Nc < 2 || a.Nc > MAX_NC) return set_error(-2, "render_rays_bf16: N_samples must be in [2, 256] for the fused kernel");
-  if (a.Ni < 0 || a.Ni > MAX_NI) return set_error(-2, "render_rays_bf16: N_importance must be in [0, 256] for the fused kernel");
-  if (a.Ni > 0 && a.Nc < 3) return set_error(-2, "render_rays_bf16: hierarchical sampling needs N_samples >= 3");
-  if (a.Ni > 0 && !a.packed_fine) return set_error(-3, "render_rays_bf16: N_importance > 0 but no fine model");
+  if (a.Nc < 2 || a.Nc > MAX_NC) return set_error(-2, CRNERF_P_RENDER_WHAT ": N_samples must be in [2, 256] for the fused kernel");
+  if (a.Ni < 0 || a.Ni > MAX_NI) return set_error(-2, CRNERF_P_RENDER_WHAT ": N_importance must be in [0, 256] for the fused kernel");
+  if (a.Ni > 0 && a.Nc < 3) return set_error(-2, CRNERF_P_RENDER_WHAT ": hierarchical sampling needs N_samples >= 3");
+  if (a.Ni > 0 && !a.packed_fine) return set_error(-3, CRNERF_P_RENDER_WHAT ": N_importance > 0 but no fine model");
   RenderParamsP k;
   k.packed0 = (const char*)a.packed_coarse;
   k.packed1 = (const char*)(a.packed_fine ? a.packed_fine : a.packed_coarse);
@@ -302,6 +336,9 @@ int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream) {
   k.weights_c = a.weights_coarse; k.feature_c = a.feature_coarse; k.depth_c = a.depth_coarse;
   k.weights_f = a.weights_fine; k.feature_f = a.feature_fine; k.depth_f = a.depth_fine; k.z_fine = a.z_fine;
   k.wc_in = nullptr;
+#if CRNERF_P_F16
+  if (a.fine_only || a.train_acts_coarse) return set_error(-3, CRNERF_P_RENDER_WHAT ": the fp16 build has the inference kernel only");
+#else
   if (a.fine_only) {   // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT, the fine model runs alone
     if (a.Ni <= 0 || !a.packed_fine || !a.weights_coarse) return set_error(-3, "render_rays_bf16_fine: needs N_importance > 0, the fine model and weights_coarse");
     if (a.train_acts_coarse) return set_error(-3, "render_rays_bf16_fine: no training twin");
@@ -309,11 +346,13 @@ int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream) {
     k.wc_in = a.weights_coarse;
     k.weights_c = k.feature_c = k.depth_c = nullptr;
   }
+#endif
   const long quads = (a.R + 3) / 4;
   const int cus = num_cus();
   const int grid = (int)(quads < cus ? quads : cus);   // one workgroup per CU, persistent over ray quads
   k.iters = (int)((quads + grid - 1) / grid);
-  k.sched = k.iters > 1 ? sched_slot((const void*)crnerf_sched_bf16p) : nullptr;
+  k.sched = k.iters > 1 ? sched_slot((const void*)CRNERF_P_RENDER_SCHED) : nullptr;
+#if !CRNERF_P_F16
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_bf16)
     if (a.Ni > 0 && (!a.train_acts_fine || !a.train_raw_fine)) return set_error(-1, "render_rays_train_bf16: fine buffers are NULL");
     if (!a.train_raw_coarse) return set_error(-1, "render_rays_train_bf16: raw_coarse is NULL");
@@ -329,12 +368,13 @@ int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(render_rays_bf16p_fine_kernel, dim3(grid), dim3(512), LDS_TOTAL_P, stream, k);
     return check_launch("render_rays_bf16p_fine_kernel");
   }
-  if (int rc = ensure_dynamic_lds((const void*)render_rays_bf16p_kernel, LDS_TOTAL_P, "render_rays_bf16p_kernel")) return rc;
-  hipLaunchKernelGGL(render_rays_bf16p_kernel, dim3(grid), dim3(512), LDS_TOTAL_P, stream, k);
-  return check_launch("render_rays_bf16p_kernel");
+#endif
+  if (int rc = ensure_dynamic_lds((const void*)CRNERF_P_RENDER_KERNEL, LDS_TOTAL_P, CRNERF_P_RENDER_NAME)) return rc;
+  hipLaunchKernelGGL(CRNERF_P_RENDER_KERNEL, dim3(grid), dim3(512), LDS_TOTAL_P, stream, k);
+  return check_launch(CRNERF_P_RENDER_NAME);
 }
 
-#ifdef CRNERF_TIMING
+#if defined(CRNERF_TIMING) && !CRNERF_P_F16
 extern "C" int crnerf_debug_read_wgtimes_bf16p(unsigned long long* host_out) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(crnerf_wg_times_p), sizeof(unsigned long long) * 2 * 1024);
 }

@@ -93,6 +93,33 @@ def _render_bf16_accurate_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir,
     return out
 
 
+_warned_f16_refused = [False]
+
+
+def _render_bf16_f16_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, chunk, want_z_fine=False):
+    """precision="bf16_fc" (inference, perturb = 0): _render_bf16_accurate_coarse with the coarse pass on ONE-PIECE FP16 operands -- one MFMA per product
+    like bf16 instead of the h2 core's three, 11 significand bits instead of bf16's 8: the coarse weights, and with them the fine depths, land
+    ~7x closer to fp32's than bf16's do (tests/test_gpu_f16_trained.py) at bf16's cost.  Three launches: the coarse-only crnerf_render_rays_f16,
+    crnerf_render_rays_f32x3_repair over its outputs (re-renders the ray quads the fp16 range guard poisoned; leaves at once otherwise -- so the
+    mode returns no NaN that "f32" would not), crnerf_render_rays_bf16_fine on those coarse weights.  A coarse model whose weights do not fit
+    fp16 (the pack refuses them) takes bf16_hc's coarse pass instead; said once in a warning."""
+    try:
+        pk = coarse.packed_weights("f16")
+    except ops.PackRangeError:
+        if not _warned_f16_refused[0]:
+            _warned_f16_refused[0] = True
+            import warnings
+            warnings.warn("crnerf_amd: precision='bf16_fc': a weight of the coarse model does not fit fp16 (|w| <= 65,504, finite); "
+                          "its coarse pass runs as in 'bf16_hc'")
+        return _render_bf16_accurate_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, chunk, want_z_fine)
+    z_steps, u_steps = _linspace_tables(Nc, Ni, rays.device)
+    out = ops.render_rays(pk, None, rays, Nc, 0, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, noise_coarse=noise_c, noise_std=float(noise_std),
+                          precision="f16", repair_x3=(coarse.packed_weights("f32x3"), None))
+    out.update(ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, out["weights_coarse"], Nc, Ni, use_disp=use_disp, view_dir=view_dir,
+                                         z_steps=z_steps, u=u_steps, noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine))
+    return out
+
+
 def _check_embedding(emb, n_freqs, what):
     if not isinstance(emb, PosEmbedding) or emb.N_freqs != n_freqs:
         raise NotImplementedError("crnerf_amd: embeddings['%s'] must be crnerf_amd PosEmbedding(%d, %d); the fused kernel computes "
@@ -105,7 +132,7 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     N_importance > 0, 'fine' (+ 'feature_fine_random', the SAME tensor object as 'feature_fine',
     models/rendering.py:140-141,192).  ts / white_back / test_time / chunk are accepted and, as in the
     reference's arithmetic, do not influence the result (the MLP is point-wise, so chunking is invisible).
-    One keyword beyond the reference's: precision="f32"|"bf16"|"f32x3"|"f32h2"|"auto"|"bf16_hc" (default crnerf_amd.get_precision()) selects the
+    One keyword beyond the reference's: precision="f32"|"bf16"|"f32x3"|"f32h2"|"auto"|"bf16_hc"|"bf16_fc"|"f16" (default crnerf_amd.get_precision()) selects the
     matrix-core arithmetic of NeRF_sigma at inference (include/crnerf.h).  Grad mode trains through the exact-fp32 twins unless
     the caller opted into mixed precision (autograd.set_training_precision("bf16") / CRNERF_TRAIN_BF16=1: bf16-operand GEMM twins,
     fp32 accumulation; autograd.set_wgrad_precision("bf16"): weight gradients only) -- neither has a counterpart in the reference."""
@@ -126,7 +153,9 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         from .. import get_precision
         precision = get_precision()
     bf16_hc = precision in ("bf16_hc", "bf16+h2c") and not train
-    precision = "f32" if train else ("bf16" if bf16_hc else "auto" if ops._is_auto(precision) else "f32h2" if ops._is_h2(precision) else "f32x3" if ops._is_x3(precision)
+    bf16_fc = precision in ("bf16_fc", "bf16+f16c") and not train      # outside its applicability (below): the path plain "bf16" takes
+    # ("f16": both passes on fp16 operands through the fused kernel, NaN rows where a point leaves fp16's range; the un-fused path has no repair either)
+    precision = "f32" if train else ("bf16" if (bf16_hc or bf16_fc) else "f16" if ops._is_f16(precision) else "auto" if ops._is_auto(precision) else "f32h2" if ops._is_h2(precision) else "f32x3" if ops._is_x3(precision)
                                      else ("bf16" if ops._is_bf16(precision) else "f32"))
 
     rays = rays.to(torch.float32).contiguous()
@@ -163,6 +192,8 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
                                      float(noise_std), rng=rng)
     elif bf16_hc and N_importance > 0 and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
         out = _render_bf16_accurate_coarse(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), int(chunk))
+    elif bf16_fc and 0 < N_importance <= _FUSED_MAX and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
+        out = _render_bf16_f16_coarse(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), int(chunk))
     elif train or N_samples > _FUSED_MAX or N_importance > _FUSED_MAX or jitter:
         # general path: the same HIP kernels, un-fused (posenc -> MLP -> compositing -> sample_pdf/merge), for
         # sample counts beyond the fused kernel's LDS scratch and for args.pertubeCord (rendering.py:102-104)

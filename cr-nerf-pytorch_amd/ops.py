@@ -132,7 +132,8 @@ def pack_h2_in_range(packed_h2):
 
 def pack_mlp_weights(state, out=None, precision="f32"):
     """state: mapping name -> device tensor with the 24 NeRF_sigma tensors (models/nerf.py:137-154).
-    precision "f32" -> buffer for the *_f32 entry points, "bf16" -> for the *_bf16 ones, "f32x3" / "f32h2" -> for the *_f32x3 / *_f32h2 ones
+    precision "f32" -> buffer for the *_f32 entry points, "bf16" -> for the *_bf16 ones, "f16" -> for the *_f16 ones (the bf16 layout with fp16
+    elements; PackRangeError when a weight does not fit fp16), "f32x3" / "f32h2" -> for the *_f32x3 / *_f32h2 ones
     (pack_mlp_weights_x3 / pack_mlp_weights_h2; different layouts each), "auto" -> an AutoPack (h2 + x3)."""
     if _is_auto(precision):
         if out is not None:
@@ -150,14 +151,46 @@ def pack_mlp_weights(state, out=None, precision="f32"):
             raise ValueError("crnerf_amd: %s has shape %s, the HIP kernels are built for %s "
                              "(D=8, W=256, N_emb_xyz=15, N_emb_dir=4, nerf_out_dim=64)" % (name, tuple(t.shape), shape))
         tensors.append(_f32c(t.detach(), name))
+    f16 = _is_f16(precision)
     bf16 = _is_bf16(precision)
-    nbytes = lib.crnerf_packed_mlp_bf16_bytes() if bf16 else lib.crnerf_packed_mlp_bytes()
+    nbytes = lib.crnerf_packed_mlp_f16_bytes() if f16 else lib.crnerf_packed_mlp_bf16_bytes() if bf16 else lib.crnerf_packed_mlp_bytes()
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=tensors[0].device)
     arr = _lib.ptr_array(tensors, "mlp tensor")
+    if f16:
+        rc = lib.crnerf_pack_mlp_weights_f16(arr, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr())
+        if rc == _lib.ERR_RANGE:
+            msg = lib.crnerf_last_error()
+            raise PackRangeError("crnerf_pack_mlp_weights_f16 failed (code %d): %s" % (rc, msg.decode() if msg else "?"))
+        _lib.check(rc, "crnerf_pack_mlp_weights_f16")
+        return F16Pack(out)
     fn = lib.crnerf_pack_mlp_weights_bf16 if bf16 else lib.crnerf_pack_mlp_weights
     _lib.check(fn(arr, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()), "crnerf_pack_mlp_weights" + ("_bf16" if bf16 else ""))
     return out
+
+
+class PackRangeError(RuntimeError):
+    """crnerf_pack_mlp_weights_f16 refused the weights: one of them is not finite or beyond fp16's 65,504."""
+
+
+class F16Pack:
+    """An f16 pack.  It has the bf16 pack's size, so unlike the other layouts it cannot be told from one by its length: the type is the tag (`data`: the
+    uint8 buffer)."""
+    __slots__ = ("data",)
+
+    def __init__(self, data):
+        self.data = data
+
+    def data_ptr(self):
+        return self.data.data_ptr()
+
+    def numel(self):
+        return self.data.numel()
+
+
+def _check_packed_f16(packed):
+    if packed is not None and not isinstance(packed, F16Pack):
+        raise ValueError("crnerf_amd: the f16 entry points need packs from pack_mlp_weights(..., precision='f16')")
 
 
 def _is_auto(precision):
@@ -172,12 +205,16 @@ def _is_h2(precision):
     return precision in ("f32h2", "h2")
 
 
+def _is_f16(precision):
+    return precision in ("f16", "fp16", "float16", torch.float16)
+
+
 def _is_bf16(precision):
     if precision in ("bf16", "bfloat16", torch.bfloat16):
         return True
-    if precision in ("f32", "fp32", "float32", torch.float32, None) or _is_x3(precision) or _is_h2(precision) or _is_auto(precision):
+    if precision in ("f32", "fp32", "float32", torch.float32, None) or _is_x3(precision) or _is_h2(precision) or _is_auto(precision) or _is_f16(precision):
         return False
-    raise ValueError("crnerf_amd: precision must be 'f32', 'bf16', 'f32x3', 'f32h2' or 'auto', got %r" % (precision,))
+    raise ValueError("crnerf_amd: precision must be 'f32', 'bf16', 'f16', 'f32x3', 'f32h2' or 'auto', got %r" % (precision,))
 
 
 def _mlp_tensor_list(state):
@@ -433,6 +470,11 @@ def mlp_forward(packed, x, sigma_only=False, precision="f32"):
     if x.dim() != 2 or x.shape[1] != want:
         raise ValueError("mlp_forward expects [n,%d], got %s" % (want, tuple(x.shape)))
     out = torch.empty(x.shape[0], 1 if sigma_only else 65, dtype=torch.float32, device=x.device)
+    if _is_f16(precision):   # one-piece fp16 operands (crnerf_mlp_forward_f16): a point whose operands leave fp16's range comes out as NaN
+        _check_packed_f16(packed)
+        _lib.check(lib.crnerf_mlp_forward_f16(ctypes.c_void_p(packed.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)),
+                                              _lib.stream_ptr()), "crnerf_mlp_forward_f16")
+        return out
     bf16 = _is_bf16(precision)
     _check_packed(packed, bf16)
     fn = lib.crnerf_mlp_forward_bf16 if bf16 else lib.crnerf_mlp_forward_f32
@@ -445,6 +487,8 @@ def _check_packed(packed, bf16):
     """The two packed layouts differ in size, so a mix-up is caught here instead of rendering garbage."""
     lib = _lib.load()
     want = lib.crnerf_packed_mlp_bf16_bytes() if bf16 else lib.crnerf_packed_mlp_bytes()
+    if isinstance(packed, F16Pack):
+        raise ValueError("crnerf_amd: an f16 pack was handed to the %s entry points (it has the bf16 pack's size and another element type)" % ("bf16" if bf16 else "f32"))
     if packed is not None and packed.numel() * packed.element_size() != want:
         raise ValueError("crnerf_amd: packed weights are %d bytes, the %s entry points need %d (pack with precision=%r)"
                          % (packed.numel() * packed.element_size(), "bf16" if bf16 else "f32", want, "bf16" if bf16 else "f32"))
@@ -494,7 +538,8 @@ def sample_pdf_merge(z_coarse, weights_coarse, n_importance, u=None, return_samp
 
 
 def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
-                noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, precision="f32", train=False, launcher=False, rng=None):
+                noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, precision="f32", train=False, launcher=False, rng=None,
+                repair_x3=None):
     """Fused renderer.  Returns a dict of freshly allocated tensors.  train=True: the training twin
     crnerf_render_rays_train_f32 -- the dict additionally holds what the backward needs: z_coarse (as used), z_fine,
     acts_coarse / acts_fine (crnerf_mlp_forward_train_f32 layout, point = ray * N + sample) and raw_coarse / raw_fine [R,N,65].
@@ -505,9 +550,19 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     rng (fp32, f32x3, f32h2, auto): {"seed": int, "ray_offset": int, "perturb": float, "jitter": bool, "u": bool, "noise": bool} -- the stochastic
     steps of rendering.py:125 / :169-176 / :30 drawn INSIDE the kernel (include/crnerf.h CRNERF_RNG_*, csrc/philox.h) instead of
     handed over as tensors; the dict then also holds what was drawn: "z_coarse_used" [R,Nc], and with noise "noise_coarse_used" /
-    "noise_fine_used" (standard normal, before noise_std).  rng_fill() returns the same draws as tensors."""
+    "noise_fine_used" (standard normal, before noise_std).  rng_fill() returns the same draws as tensors.
+    precision="f16": crnerf_render_rays_f16 (packs from pack_mlp_weights(..., precision="f16"); inference only) -- a ray with a point whose operands
+    left fp16's range has a NaN feature row.  repair_x3=(coarse x3 pack, fine x3 pack or None): crnerf_render_rays_f32x3_repair re-renders those
+    ray quads in the same call, as precision="auto" does behind the h2 core."""
     lib = _lib.load()
     repair = None
+    f16 = _is_f16(precision)
+    if repair_x3 is not None:
+        if not f16:
+            raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 packs)")
+        repair = tuple(repair_x3)
+    if f16 and (train or rng is not None):
+        raise ValueError("crnerf_amd: precision='f16' is an inference mode (no training twin, no in-kernel draws)")
     if _is_auto(precision):
         # the h2 core with the x3 core as its safety net: render on h2, then crnerf_render_rays_f32x3_repair re-renders the ray quads that came out NaN
         # (a point's activations left fp16's range).  A refused h2 pack (a weight >= 255): the x3 core throughout.
@@ -533,6 +588,9 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
         for pk in (packed_coarse, packed_fine):
             if pk is not None and pk.numel() != lib.crnerf_packed_mlp_x3_bytes():
                 raise ValueError("crnerf_amd: precision='f32x3' needs packs from pack_mlp_weights_x3")
+    elif f16:
+        _check_packed_f16(packed_coarse)
+        _check_packed_f16(packed_fine)
     else:
         _check_packed(packed_coarse, bf16)
         _check_packed(packed_fine, bf16)
@@ -579,8 +637,8 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     if launcher:      # measurement helper: re-launch the same call on the same buffers with nothing but the C call on the host side
         if train:
             raise ValueError("crnerf_amd: launcher=True is for the inference entry points")
-        fn = lib.crnerf_render_rays_f32h2 if h2 else (lib.crnerf_render_rays_f32x3 if x3 else (lib.crnerf_render_rays_bf16 if bf16 else lib.crnerf_render_rays_f32))
-        name = "crnerf_render_rays_f32h2" if h2 else ("crnerf_render_rays_f32x3" if x3 else ("crnerf_render_rays_bf16" if bf16 else "crnerf_render_rays_f32"))
+        fn = lib.crnerf_render_rays_f16 if f16 else lib.crnerf_render_rays_f32h2 if h2 else (lib.crnerf_render_rays_f32x3 if x3 else (lib.crnerf_render_rays_bf16 if bf16 else lib.crnerf_render_rays_f32))
+        name = "crnerf_render_rays_f16" if f16 else "crnerf_render_rays_f32h2" if h2 else ("crnerf_render_rays_f32x3" if x3 else ("crnerf_render_rays_bf16" if bf16 else "crnerf_render_rays_f32"))
         held = (keep, rays, packed_coarse, packed_fine, out, repair)  # the argument struct holds raw pointers: keep EVERY tensor behind them alive
         # (the outputs too: a caller that drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
         a2 = _repair_args(a, repair)
@@ -609,8 +667,11 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
             _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine"),
                                                                  _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
         return out
-    if h2:
-        _lib.check(lib.crnerf_render_rays_f32h2(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f32h2")
+    if h2 or f16:
+        if f16:
+            _lib.check(lib.crnerf_render_rays_f16(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f16")
+        else:
+            _lib.check(lib.crnerf_render_rays_f32h2(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f32h2")
         a2 = _repair_args(a, repair)
         if a2 is not None:
             _lib.check(lib.crnerf_render_rays_f32x3_repair(ctypes.byref(a2), _lib.stream_ptr()), "crnerf_render_rays_f32x3_repair")

@@ -233,6 +233,34 @@ int crnerf_render_rays_bf16(const crnerf_render_args* args, void* stream);
  * depth_fine and (optional) z_fine.  Nothing per point goes through HBM. */
 int crnerf_render_rays_bf16_fine(const crnerf_render_args* args, void* stream);
 
+/* ---- "f16": the bf16 variants with one-piece FP16 operands (no counterpart in the reference; inference only).  The arithmetic of the bf16
+ * paragraph above with fp16 in place of bf16: the operands of every nn.Linear except static_sigma -- weights, activations after the relu, both
+ * positional embeddings -- rounded to fp16 (round-to-nearest-even, 11 significand bits instead of bf16's 8), ONE v_mfma_f32_32x32x16_f16 per
+ * product, fp32 accumulation; biases, Sigmoid / Softplus, the sigma head (on the un-rounded output of xyz_encoding_8), compositing, sample_pdf and
+ * the merge in fp32 -- oracle.cpu_ref.mlp_forward_bf16 with fp16 rounding in place of bf16 rounding.  Same kernel (the pair core built with fp16
+ * operands), same cost per point as bf16.
+ *   Range.  fp16 ends at 65,504.  crnerf_pack_mlp_weights_f16 refuses (CRNERF_ERR_RANGE, after waiting for the stream like
+ * crnerf_pack_mlp_weights_h2; the pack then carries the h2 packs' range flag and the f16 kernels answer it with NaN) a weight that is not finite
+ * or whose magnitude exceeds 65,504.  A POINT one of whose fp16 operands overflowed (an embedding value or a layer output that converts to inf; a
+ * negative overflow in front of a relu is 0 as in fp32 and is no error) gets all 65 outputs = NaN from crnerf_mlp_forward_f16, and
+ * crnerf_render_rays_f16 writes a NaN feature row for its ray (feature_coarse / feature_fine; the ray's weights and depth are then meaningless) --
+ * exactly what crnerf_render_rays_f32x3_repair looks for, so f16 followed by the repair kernel never returns a NaN or a finite wrong value
+ * that the fp32 entry points would not.
+ *   Subnormals.  Measured on gfx950 through crnerf_mlp_forward_f16 on a layer whose weights all lie below 2^-14
+ * (tests/test_gpu_f16.py::test_subnormal_weights_are_kept): v_mfma_f32_32x32x16_f16 KEEPS subnormal fp16 inputs and v_cvt_pk_f16_f32 produces
+ * them -- the output sits at the summation-order noise of the emulation that keeps subnormals (mean 2.6e-7) and 50x further (1.3e-5) from the one
+ * that flushes them.  So a weight or activation below 2^-14 is rounded to a multiple of 2^-24, not to zero, and no weight scale is applied.
+ *   Embeddings.  fp16 keeps 11 significand bits of sin / cos: the hardware v_sin_f32 / v_cos_f32 the bf16 kernels use are not accurate enough for
+ * that, the f16 render kernel evaluates them with the fp32 kernels' routine (csrc/sincos_pow2.h).
+ *   The packed buffer is the bf16 layout (fp32 consts + fragments in the pair core's order) with fp16 elements, same size.
+ *   precision "bf16_fc" (models/rendering.py): coarse-only crnerf_render_rays_f16, crnerf_render_rays_f32x3_repair over its outputs, then
+ * crnerf_render_rays_bf16_fine on those coarse weights. */
+size_t crnerf_packed_mlp_f16_bytes(void);
+int crnerf_pack_mlp_weights_f16(const float* const* tensors, void* packed_f16, void* stream);
+int crnerf_mlp_forward_f16(const void* packed_f16, const float* x, float* out, int64_t n, int sigma_only, void* stream);
+/* as crnerf_render_rays_bf16 (n_importance == 0: the coarse pass alone); args->packed_{coarse,fine} are f16 packs; rng_flags must be 0 */
+int crnerf_render_rays_f16(const crnerf_render_args* args, void* stream);
+
 /* Training twin of crnerf_render_rays_bf16 for the opt-in mixed-precision training mode (no counterpart in the reference): the same
  * fused launch on the bf16 matrix cores that additionally keeps, per pass, what crnerf_mlp_backward_mixed_ex_f32(..., CRNERF_MIXED_ACTS_FUSED)
  * needs -- acts_*: crnerf_mlp_train_mixed_acts_bytes(R*N) bytes (bf16 activation rows, relu-activity bits, the embedded input; point index
