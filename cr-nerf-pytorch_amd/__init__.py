@@ -40,8 +40,8 @@ def set_precision(precision):
     autograd.set_training_forward_precision("f32") / CRNERF_TRAIN_FWD=f32 and autograd.set_wgrad_precision("f32") / CRNERF_WGRAD_F32=1
     (every product on the fp32 matrix cores); autograd.set_training_precision("bf16") is the opt-in mixed-precision mode."""
     global _precision
-    from .ops import _is_auto, _is_bf16, _is_f16, _is_h2, _is_x3
-    _precision = "bf16_fc" if precision in ("bf16_fc", "bf16+f16c") else "f16" if _is_f16(precision) else "bf16_hc" if precision in ("bf16_hc", "bf16+h2c") else "auto" if _is_auto(precision) else "f32h2" if _is_h2(precision) else ("f32x3" if _is_x3(precision) else ("bf16" if _is_bf16(precision) else "f32"))
+    from .precision import resolve
+    _precision = resolve(precision, composite=True)
 
 
 def get_precision():

@@ -13,6 +13,7 @@ depths -- the latter are .detach()ed at models/rendering.py:184) get no gradient
 import torch
 
 from . import ops
+from .precision import resolve
 
 
 class MlpFn(torch.autograd.Function):
@@ -77,7 +78,7 @@ def set_wgrad_precision(precision=None):
     of the bf16 mode's rounding noise.  Forward, loss, data gradients, biases and all other tensors are unchanged.
     "f16x2": CRNERF_BWD_WGRAD_F16X2 (include/crnerf.h) where the h2 data gradient runs, "bf16x3" elsewhere."""
     _WGRAD_BF16[0] = None if precision is None else (3 if str(precision).lower() in ("f16x2", "h2") else 2 if str(precision).lower() in ("bf16x3", "x3") else
-                                                     (1 if ops._is_bf16(precision) else 0))
+                                                     (1 if resolve(precision) == "bf16" else 0))
 
 
 _TRAIN_BF16 = [False]
@@ -95,8 +96,8 @@ def set_training_forward_precision(precision=None):
     "auto": "f32h2" with the scale-free f32x3 twins as its safety net -- poisoned ray quads are rendered again (saved rows included) by
     crnerf_render_rays_train_f32x3_repair on the device; a weight >= 255 leaves a flag in the (asynchronous) pack that makes the h2 kernels hand
     the whole step to the f32x3 ones, also on the device: no host round trip, no NaN of the h2 core's making in the loss."""
-    _TRAIN_FWD[0] = (None if precision is None else "f32x3" if ops._is_x3(precision) else "f32h2" if ops._is_h2(precision) else
-                     "auto" if ops._is_auto(precision) else ("f32" if not ops._is_bf16(precision) else _bad_fwd_precision(precision)))
+    name = None if precision is None else resolve(precision)
+    _TRAIN_FWD[0] = name if name in (None, "f32", "f32x3", "f32h2", "auto") else _bad_fwd_precision(precision)
 
 
 def _bad_fwd_precision(precision):
@@ -145,7 +146,7 @@ def set_training_precision(precision="f32"):
     in grad mode (include/crnerf.h): forward in the arithmetic of the bf16 inference kernels, data and weight gradients from
     bf16-rounded operands, fp32 accumulation; activations and deltas are kept as bf16 rows.  The forward is the fused bf16 renderer's
     training twin (crnerf_render_rays_train_bf16); the backward runs per-layer bf16 GEMMs (crnerf_mlp_backward_mixed_ex_f32)."""
-    _TRAIN_BF16[0] = ops._is_bf16(precision)
+    _TRAIN_BF16[0] = resolve(precision) == "bf16"
 
 
 def get_training_bf16():

@@ -8,6 +8,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..precision import resolve
 
 _XYZ_FREQS, _DIR_FREQS, _W, _OUT = 15, 4, 256, 64
 
@@ -81,18 +82,15 @@ class NeRF_sigma(nn.Module):
         """Packed buffer for the crnerf_*_f32 (default), crnerf_*_bf16, crnerf_*_f16, crnerf_*_f32x3 or crnerf_*_f32h2 entry points ("auto": an ops.AutoPack
         holding the h2 and the x3 pack; "f16": an ops.F16Pack, or ops.PackRangeError when a weight does not fit fp16 -- asked again on every call, the
         refusal is not cached); re-packed when a parameter changes."""
-        bf16 = ("auto" if ops._is_auto(precision) else "h2" if ops._is_h2(precision) else "x3" if ops._is_x3(precision) else "f16" if ops._is_f16(precision)
-                else ops._is_bf16(precision))
+        name = resolve(precision)
         params = dict(zip(ops.MLP_TENSOR_NAMES, ops.mlp_params(self)))
         key = tuple((p.data_ptr(), p._version, p.device) for p in params.values())
         if self._packed is None or key != self._packed_key:
             self._packed = {}
             self._packed_key = key
-        if bf16 not in self._packed:
-            self._packed[bf16] = (ops.pack_mlp_weights_auto(params) if bf16 == "auto" else ops.pack_mlp_weights_h2(params) if bf16 == "h2" else ops.pack_mlp_weights_x3(params) if bf16 == "x3"
-                                  else ops.pack_mlp_weights(params, out=None, precision="f16") if bf16 == "f16"
-                                  else ops.pack_mlp_weights(params, out=None, precision="bf16" if bf16 else "f32"))
-        return self._packed[bf16]
+        if name not in self._packed:
+            self._packed[name] = ops.pack_mlp_weights(params, precision=name)
+        return self._packed[name]
 
     def forward(self, x, sigma_only=False, output_random=True, precision=None):
         """precision: None -> crnerf_amd.get_precision(); an extension of the reference signature (nerf.py:157)."""
@@ -104,10 +102,4 @@ class NeRF_sigma(nn.Module):
         if precision is None:
             from .. import get_precision
             precision = get_precision()
-        if ops._is_auto(precision):
-            return ops.mlp_forward_auto(self.packed_weights(precision), x, sigma_only=sigma_only)
-        if ops._is_h2(precision):
-            return ops.mlp_forward_h2(self.packed_weights(precision), x, sigma_only=sigma_only)
-        if ops._is_x3(precision):
-            return ops.mlp_forward_x3(self.packed_weights(precision), x, sigma_only=sigma_only)
         return ops.mlp_forward(self.packed_weights(precision), x, sigma_only=sigma_only, precision=precision)

@@ -4,6 +4,7 @@ appearance_modification_video.py:82-95 -- all pass the first 11 arguments positi
 import torch
 
 from .. import ops
+from ..precision import resolve
 from .nerf import NeRF_sigma, PosEmbedding
 
 __all__ = ['render_rays_cross_ray']
@@ -152,11 +153,11 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     if precision is None:
         from .. import get_precision
         precision = get_precision()
-    bf16_hc = precision in ("bf16_hc", "bf16+h2c") and not train
-    bf16_fc = precision in ("bf16_fc", "bf16+f16c") and not train      # outside its applicability (below): the path plain "bf16" takes
+    name = "f32" if train else resolve(precision, composite=True)      # grad mode does not read the setting (crnerf_amd.set_precision)
+    bf16_hc, bf16_fc = name == "bf16_hc", name == "bf16_fc"
+    # outside their applicability (below) the composite modes take the path plain "bf16" takes
     # ("f16": both passes on fp16 operands through the fused kernel, NaN rows where a point leaves fp16's range; the un-fused path has no repair either)
-    precision = "f32" if train else ("bf16" if (bf16_hc or bf16_fc) else "f16" if ops._is_f16(precision) else "auto" if ops._is_auto(precision) else "f32h2" if ops._is_h2(precision) else "f32x3" if ops._is_x3(precision)
-                                     else ("bf16" if ops._is_bf16(precision) else "f32"))
+    precision = "bf16" if (bf16_hc or bf16_fc) else name
 
     rays = rays.to(torch.float32).contiguous()
     R = rays.shape[0]

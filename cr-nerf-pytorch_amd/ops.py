@@ -1,11 +1,13 @@
 """Tensor-level wrappers over the C ABI: allocate outputs with torch, enqueue the HIP kernels on the
 current stream.  Every function here runs on the GPU or raises."""
+import collections
 import ctypes
 import os
 
 import torch
 
 from . import _lib
+from .precision import resolve
 
 MLP_TENSOR_NAMES = (
     [n for i in range(1, 9) for n in ("xyz_encoding_%d.0.weight" % i, "xyz_encoding_%d.0.bias" % i)]
@@ -102,73 +104,6 @@ class AutoPack:
         self.h2, self.x3 = h2, x3
 
 
-def pack_mlp_weights_auto(state, check=True):
-    """check=False (training: a pack per optimiser step): crnerf_pack_mlp_weights_h2_async -- no wait for the stream; a refused pack carries its verdict
-    as a flag word the h2 kernels read on the device (they then leave everything to the f32x3 repair), so `h2` is never None."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    h2 = torch.empty(lib.crnerf_packed_mlp_h2_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    if not check:
-        _lib.check(lib.crnerf_pack_mlp_weights_h2_async(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(h2.data_ptr()), _lib.stream_ptr()),
-                   "crnerf_pack_mlp_weights_h2_async")
-        return AutoPack(h2, pack_mlp_weights_x3(state))
-    rc = lib.crnerf_pack_mlp_weights_h2(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(h2.data_ptr()), _lib.stream_ptr())
-    if rc == _lib.ERR_RANGE:
-        h2 = None
-    else:
-        _lib.check(rc, "crnerf_pack_mlp_weights_h2")
-    return AutoPack(h2, pack_mlp_weights_x3(state))
-
-
-def pack_h2_in_range(packed_h2):
-    """True when the h2 / transposed-h2 pack carries no range flag (crnerf_pack_h2_status; waits for the stream)."""
-    lib = _lib.load()
-    rc = lib.crnerf_pack_h2_status(ctypes.c_void_p(packed_h2.data_ptr()), _lib.stream_ptr())
-    if rc == _lib.ERR_RANGE:
-        return False
-    _lib.check(rc, "crnerf_pack_h2_status")
-    return True
-
-
-def pack_mlp_weights(state, out=None, precision="f32"):
-    """state: mapping name -> device tensor with the 24 NeRF_sigma tensors (models/nerf.py:137-154).
-    precision "f32" -> buffer for the *_f32 entry points, "bf16" -> for the *_bf16 ones, "f16" -> for the *_f16 ones (the bf16 layout with fp16
-    elements; PackRangeError when a weight does not fit fp16), "f32x3" / "f32h2" -> for the *_f32x3 / *_f32h2 ones
-    (pack_mlp_weights_x3 / pack_mlp_weights_h2; different layouts each), "auto" -> an AutoPack (h2 + x3)."""
-    if _is_auto(precision):
-        if out is not None:
-            raise ValueError("crnerf_amd: out= is for the f32 / bf16 packs")
-        return pack_mlp_weights_auto(state)
-    if _is_h2(precision) or _is_x3(precision):
-        if out is not None:
-            raise ValueError("crnerf_amd: out= is for the f32 / bf16 packs")
-        return pack_mlp_weights_h2(state) if _is_h2(precision) else pack_mlp_weights_x3(state)
-    lib = _lib.load()
-    tensors = []
-    for name, shape in zip(MLP_TENSOR_NAMES, MLP_TENSOR_SHAPES):
-        t = state[name]
-        if tuple(t.shape) != shape:
-            raise ValueError("crnerf_amd: %s has shape %s, the HIP kernels are built for %s "
-                             "(D=8, W=256, N_emb_xyz=15, N_emb_dir=4, nerf_out_dim=64)" % (name, tuple(t.shape), shape))
-        tensors.append(_f32c(t.detach(), name))
-    f16 = _is_f16(precision)
-    bf16 = _is_bf16(precision)
-    nbytes = lib.crnerf_packed_mlp_f16_bytes() if f16 else lib.crnerf_packed_mlp_bf16_bytes() if bf16 else lib.crnerf_packed_mlp_bytes()
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=tensors[0].device)
-    arr = _lib.ptr_array(tensors, "mlp tensor")
-    if f16:
-        rc = lib.crnerf_pack_mlp_weights_f16(arr, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr())
-        if rc == _lib.ERR_RANGE:
-            msg = lib.crnerf_last_error()
-            raise PackRangeError("crnerf_pack_mlp_weights_f16 failed (code %d): %s" % (rc, msg.decode() if msg else "?"))
-        _lib.check(rc, "crnerf_pack_mlp_weights_f16")
-        return F16Pack(out)
-    fn = lib.crnerf_pack_mlp_weights_bf16 if bf16 else lib.crnerf_pack_mlp_weights
-    _lib.check(fn(arr, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()), "crnerf_pack_mlp_weights" + ("_bf16" if bf16 else ""))
-    return out
-
-
 class PackRangeError(RuntimeError):
     """crnerf_pack_mlp_weights_f16 refused the weights: one of them is not finite or beyond fp16's 65,504."""
 
@@ -188,33 +123,38 @@ class F16Pack:
         return self.data.numel()
 
 
-def _check_packed_f16(packed):
-    if packed is not None and not isinstance(packed, F16Pack):
-        raise ValueError("crnerf_amd: the f16 entry points need packs from pack_mlp_weights(..., precision='f16')")
+# One record per arithmetic a kernel family exists for (precision.CORES): the library's entry points BY NAME (looked up on the loaded library, so
+# importing this module does not load it) and `tag`, the type a pack of that core has where its byte size cannot tell it from another's.
+_Core = collections.namedtuple("_Core", "bytes pack forward render render_train tag")
+_CORES = {
+    "f32": _Core("crnerf_packed_mlp_bytes", "crnerf_pack_mlp_weights", "crnerf_mlp_forward_f32", "crnerf_render_rays_f32", "crnerf_render_rays_train_f32", None),
+    "bf16": _Core("crnerf_packed_mlp_bf16_bytes", "crnerf_pack_mlp_weights_bf16", "crnerf_mlp_forward_bf16", "crnerf_render_rays_bf16",
+                  "crnerf_render_rays_train_bf16", None),
+    # one-piece fp16 operands: a point whose operands leave fp16's range comes out as NaN; inference only
+    "f16": _Core("crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16", None, F16Pack),
+    # fp32 on the bf16 matrix cores: every weight as three bf16 pieces, k-step-major fragment stream; six MFMAs per product
+    "f32x3": _Core("crnerf_packed_mlp_x3_bytes", "crnerf_pack_mlp_weights_x3", "crnerf_mlp_forward_f32x3", "crnerf_render_rays_f32x3",
+                   "crnerf_render_rays_train_f32x3", None),
+    # fp32 on the fp16 matrix cores: every weight, scaled by 2^8, as two fp16 pieces; three MFMAs per product
+    "f32h2": _Core("crnerf_packed_mlp_h2_bytes", "crnerf_pack_mlp_weights_h2", "crnerf_mlp_forward_f32h2", "crnerf_render_rays_f32h2",
+                   "crnerf_render_rays_train_f32h2", None),
+}
 
 
-def _is_auto(precision):
-    return precision in ("auto", "f32auto")
-
-
-def _is_x3(precision):
-    return precision in ("f32x3", "x3")
-
-
-def _is_h2(precision):
-    return precision in ("f32h2", "h2")
-
-
-def _is_f16(precision):
-    return precision in ("f16", "fp16", "float16", torch.float16)
-
-
-def _is_bf16(precision):
-    if precision in ("bf16", "bfloat16", torch.bfloat16):
-        return True
-    if precision in ("f32", "fp32", "float32", torch.float32, None) or _is_x3(precision) or _is_h2(precision) or _is_auto(precision) or _is_f16(precision):
-        return False
-    raise ValueError("crnerf_amd: precision must be 'f32', 'bf16', 'f16', 'f32x3', 'f32h2' or 'auto', got %r" % (precision,))
+def _check_pack(lib, name, packed):
+    """The packed layouts differ in size (the f16 one in type), so a mix-up is caught here instead of rendering garbage."""
+    if packed is None:
+        return
+    core = _CORES[name]
+    if core.tag is not None:
+        if not isinstance(packed, core.tag):
+            raise ValueError("crnerf_amd: the %s entry points need packs from pack_mlp_weights(..., precision=%r)" % (name, name))
+        return
+    if isinstance(packed, F16Pack):
+        raise ValueError("crnerf_amd: an f16 pack was handed to the %s entry points (it has the bf16 pack's size and another element type)" % name)
+    got, want = packed.numel() * packed.element_size(), getattr(lib, core.bytes)()
+    if got != want:
+        raise ValueError("crnerf_amd: packed weights are %d bytes, the %s entry points need %d (pack with precision=%r)" % (got, name, want, name))
 
 
 def _mlp_tensor_list(state):
@@ -222,59 +162,82 @@ def _mlp_tensor_list(state):
     for name, shape in zip(MLP_TENSOR_NAMES, MLP_TENSOR_SHAPES):
         t = state[name]
         if tuple(t.shape) != shape:
-            raise ValueError("crnerf_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            raise ValueError("crnerf_amd: %s has shape %s, the HIP kernels are built for %s "
+                             "(D=8, W=256, N_emb_xyz=15, N_emb_dir=4, nerf_out_dim=64)" % (name, tuple(t.shape), shape))
         tensors.append(t if (t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda) else _f32c(t.detach(), name))
     return tensors
 
 
-def pack_mlp_weights_x3(state):
-    """Packed weights for the "f32x3" entry points (include/crnerf.h): every weight as three bf16 pieces, k-step-major fragment stream."""
+def _pack(state, bytes_fn, pack_fn, out=None, range_ok=False):
+    """The 24 tensors of `state` (mapping name -> device tensor, models/nerf.py:137-154) through the library's `pack_fn` into `out` (default: a new
+    buffer of `bytes_fn`() bytes).  range_ok: None instead of an error when the library refuses the weights' range (CRNERF_ERR_RANGE)."""
     lib = _lib.load()
     tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_x3_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_x3(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_x3")
+    if out is None:
+        out = torch.empty(getattr(lib, bytes_fn)(), dtype=torch.uint8, device=tensors[0].device)
+    rc = getattr(lib, pack_fn)(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr())
+    if rc == _lib.ERR_RANGE and range_ok:
+        return None
+    _lib.check(rc, pack_fn)
     return out
+
+
+def pack_mlp_weights_auto(state, check=True):
+    """check=False (training: a pack per optimiser step): crnerf_pack_mlp_weights_h2_async -- no wait for the stream; a refused pack carries its verdict
+    as a flag word the h2 kernels read on the device (they then leave everything to the f32x3 repair), so `h2` is never None."""
+    core = _CORES["f32h2"]
+    h2 = _pack(state, core.bytes, core.pack, range_ok=True) if check else _pack(state, core.bytes, "crnerf_pack_mlp_weights_h2_async")
+    return AutoPack(h2, pack_mlp_weights_x3(state))
+
+
+def pack_h2_in_range(packed_h2):
+    """True when the h2 / transposed-h2 pack carries no range flag (crnerf_pack_h2_status; waits for the stream)."""
+    lib = _lib.load()
+    rc = lib.crnerf_pack_h2_status(ctypes.c_void_p(packed_h2.data_ptr()), _lib.stream_ptr())
+    if rc == _lib.ERR_RANGE:
+        return False
+    _lib.check(rc, "crnerf_pack_h2_status")
+    return True
+
+
+def pack_mlp_weights(state, out=None, precision="f32"):
+    """state: mapping name -> device tensor with the 24 NeRF_sigma tensors (models/nerf.py:137-154).
+    precision "f32" -> buffer for the *_f32 entry points, "bf16" -> for the *_bf16 ones, "f16" -> for the *_f16 ones (the bf16 layout with fp16
+    elements; PackRangeError when a weight does not fit fp16), "f32x3" / "f32h2" -> for the *_f32x3 / *_f32h2 ones
+    (pack_mlp_weights_x3 / pack_mlp_weights_h2; different layouts each), "auto" -> an AutoPack (h2 + x3)."""
+    name = resolve(precision)
+    if out is not None and name in ("auto", "f32x3", "f32h2"):
+        raise ValueError("crnerf_amd: out= is for the f32 / bf16 packs")
+    if name == "auto":
+        return pack_mlp_weights_auto(state)
+    core = _CORES[name]
+    if name != "f16":
+        return _pack(state, core.bytes, core.pack, out)
+    out = _pack(state, core.bytes, core.pack, out, range_ok=True)
+    if out is None:
+        msg = _lib.load().crnerf_last_error()
+        raise PackRangeError("%s failed (code %d): %s" % (core.pack, _lib.ERR_RANGE, msg.decode() if msg else "?"))
+    return F16Pack(out)
+
+
+def pack_mlp_weights_x3(state):
+    """Packed weights for the "f32x3" entry points (include/crnerf.h): every weight as three bf16 pieces, k-step-major fragment stream."""
+    return _pack(state, *_CORES["f32x3"][:2])
 
 
 def mlp_forward_x3(packed_x3, x, sigma_only=False):
     """NeRF_sigma.forward in fp32 on the bf16 matrix cores (three-piece splits, six MFMAs per product; crnerf_mlp_forward_f32x3)."""
-    lib = _lib.load()
-    x = _f32c(x, "x")
-    want = 93 if sigma_only else 120
-    if x.dim() != 2 or x.shape[1] != want:
-        raise ValueError("mlp_forward_x3 expects [n,%d], got %s" % (want, tuple(x.shape)))
-    if packed_x3.numel() != lib.crnerf_packed_mlp_x3_bytes():
-        raise ValueError("crnerf_amd: packed weights are not an x3 pack (pack_mlp_weights_x3)")
-    out = torch.empty(x.shape[0], 1 if sigma_only else 65, dtype=torch.float32, device=x.device)
-    _lib.check(lib.crnerf_mlp_forward_f32x3(ctypes.c_void_p(packed_x3.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)),
-                                            _lib.stream_ptr()), "crnerf_mlp_forward_f32x3")
-    return out
+    return mlp_forward(packed_x3, x, sigma_only=sigma_only, precision="f32x3")
 
 
 def pack_mlp_weights_h2(state):
     """Packed weights for the "f32h2" entry points (include/crnerf.h): every weight, scaled by 2^8, as two fp16 pieces."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_h2_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_h2(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_h2")
-    return out
+    return _pack(state, *_CORES["f32h2"][:2])
 
 
 def mlp_forward_h2(packed_h2, x, sigma_only=False):
     """NeRF_sigma.forward in fp32 on the fp16 matrix cores (two-piece splits, three MFMAs per product; crnerf_mlp_forward_f32h2)."""
-    lib = _lib.load()
-    x = _f32c(x, "x")
-    want = 93 if sigma_only else 120
-    if x.dim() != 2 or x.shape[1] != want:
-        raise ValueError("mlp_forward_h2 expects [n,%d], got %s" % (want, tuple(x.shape)))
-    if packed_h2.numel() != lib.crnerf_packed_mlp_h2_bytes():
-        raise ValueError("crnerf_amd: packed weights are not an h2 pack (pack_mlp_weights_h2)")
-    out = torch.empty(x.shape[0], 1 if sigma_only else 65, dtype=torch.float32, device=x.device)
-    _lib.check(lib.crnerf_mlp_forward_f32h2(ctypes.c_void_p(packed_h2.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)),
-                                            _lib.stream_ptr()), "crnerf_mlp_forward_f32h2")
-    return out
+    return mlp_forward(packed_h2, x, sigma_only=sigma_only, precision="f32h2")
 
 
 def render_rays_x3(packed_coarse, packed_fine, rays, n_samples, n_importance, **kw):
@@ -284,12 +247,7 @@ def render_rays_x3(packed_coarse, packed_fine, rays, n_samples, n_importance, **
 
 def pack_mlp_weights_t(state):
     """Transposed fragment stream for the backward-data kernel."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_t_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_t(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_t")
-    return out
+    return _pack(state, "crnerf_packed_mlp_t_bytes", "crnerf_pack_mlp_weights_t")
 
 
 def mlp_forward_train(packed, x):
@@ -306,23 +264,13 @@ def mlp_forward_train(packed, x):
 
 def pack_mlp_weights_t_x3(state):
     """Transposed x3 fragment stream for the backward-data kernel on the x3 core (crnerf_mlp_backward_x3_f32)."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_t_x3_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_t_x3(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_t_x3")
-    return out
+    return _pack(state, "crnerf_packed_mlp_t_x3_bytes", "crnerf_pack_mlp_weights_t_x3")
 
 
 def pack_mlp_weights_t_h2(state):
     """Transposed h2 fragment stream for the backward-data kernel on the h2 core (crnerf_mlp_backward_h2_f32): two fp16 pieces of 2^8 w.  No range
     check of its own -- pack_mlp_weights_h2 / pack_mlp_weights(..., precision="auto") of the same weights is the check."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_t_h2_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_t_h2(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_t_h2")
-    return out
+    return _pack(state, "crnerf_packed_mlp_t_h2_bytes", "crnerf_pack_mlp_weights_t_h2")
 
 
 BWD_PHASE_DGRAD, BWD_PHASE_WGRAD = 8, 16      # CRNERF_BWD_PHASE_* (include/crnerf.h)
@@ -379,12 +327,7 @@ def mlp_backward(packed_t, x, out, d_out, acts, wgrad_bf16=False, dgrad_x3=False
 def pack_mlp_weights_mixed(state):
     """bf16 B-operand fragment streams of every nn.Linear (forward and transposed) for the mixed-precision training twins
     (crnerf_mlp_*_mixed_f32, include/crnerf.h).  Returns (packed, tensors): the twins also read the fp32 biases / sigma head."""
-    lib = _lib.load()
-    tensors = _mlp_tensor_list(state)
-    out = torch.empty(lib.crnerf_packed_mlp_mixed_bytes(), dtype=torch.uint8, device=tensors[0].device)
-    _lib.check(lib.crnerf_pack_mlp_weights_mixed(_lib.ptr_array(tensors, "mlp tensor"), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr()),
-               "crnerf_pack_mlp_weights_mixed")
-    return out, tensors
+    return _pack(state, "crnerf_packed_mlp_mixed_bytes", "crnerf_pack_mlp_weights_mixed"), _mlp_tensor_list(state)
 
 
 def mlp_forward_train_mixed(packed_mixed, tensors, x):
@@ -445,53 +388,31 @@ def embed_points(rays, z, dir_emb):
 
 
 def mlp_forward_auto(pack, x, sigma_only=False):
-    """precision="auto": the h2 core, then crnerf_mlp_forward_f32x3_repair over the same output -- the 128-point groups in which a point left
-    fp16's range are evaluated again on the scale-free x3 core (nothing else is touched; no host round trip).  A refused h2 pack: x3 throughout."""
-    if pack.h2 is None:
-        return mlp_forward_x3(pack.x3, x, sigma_only=sigma_only)
-    lib = _lib.load()
-    x = _f32c(x, "x")
-    out = mlp_forward_h2(pack.h2, x, sigma_only=sigma_only)
-    _lib.check(lib.crnerf_mlp_forward_f32x3_repair(ctypes.c_void_p(pack.x3.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)),
-                                                   _lib.stream_ptr()), "crnerf_mlp_forward_f32x3_repair")
-    return out
+    """mlp_forward(..., precision="auto")."""
+    return mlp_forward(pack, x, sigma_only=sigma_only, precision="auto")
 
 
 def mlp_forward(packed, x, sigma_only=False, precision="f32"):
-    if _is_auto(precision):
-        return mlp_forward_auto(packed, x, sigma_only=sigma_only)
-    if _is_h2(precision):
-        return mlp_forward_h2(packed, x, sigma_only=sigma_only)
-    if _is_x3(precision):
-        return mlp_forward_x3(packed, x, sigma_only=sigma_only)
+    """NeRF_sigma.forward on the core `precision` names.  "auto" (an AutoPack): the h2 core, then crnerf_mlp_forward_f32x3_repair over the same
+    output -- the 128-point groups in which a point left fp16's range are evaluated again on the scale-free x3 core (nothing else is touched; no host
+    round trip).  A refused h2 pack: x3 throughout."""
+    name = resolve(precision)
     lib = _lib.load()
     x = _f32c(x, "x")
     want = 93 if sigma_only else 120
     if x.dim() != 2 or x.shape[1] != want:
         raise ValueError("mlp_forward expects [n,%d], got %s" % (want, tuple(x.shape)))
+    repair = None
+    if name == "auto":
+        name, packed, repair = ("f32x3", packed.x3, None) if packed.h2 is None else ("f32h2", packed.h2, packed.x3)
+    _check_pack(lib, name, packed)
     out = torch.empty(x.shape[0], 1 if sigma_only else 65, dtype=torch.float32, device=x.device)
-    if _is_f16(precision):   # one-piece fp16 operands (crnerf_mlp_forward_f16): a point whose operands leave fp16's range comes out as NaN
-        _check_packed_f16(packed)
-        _lib.check(lib.crnerf_mlp_forward_f16(ctypes.c_void_p(packed.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)),
-                                              _lib.stream_ptr()), "crnerf_mlp_forward_f16")
-        return out
-    bf16 = _is_bf16(precision)
-    _check_packed(packed, bf16)
-    fn = lib.crnerf_mlp_forward_bf16 if bf16 else lib.crnerf_mlp_forward_f32
-    _lib.check(fn(ctypes.c_void_p(packed.data_ptr()), _lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)), _lib.stream_ptr()),
-               "crnerf_mlp_forward_bf16" if bf16 else "crnerf_mlp_forward_f32")
+    tail = (_lib.dev_ptr(x), _lib.dev_ptr(out), x.shape[0], int(bool(sigma_only)))
+    fn = _CORES[name].forward
+    _lib.check(getattr(lib, fn)(ctypes.c_void_p(packed.data_ptr()), *tail, _lib.stream_ptr()), fn)
+    if repair is not None:
+        _lib.check(lib.crnerf_mlp_forward_f32x3_repair(ctypes.c_void_p(repair.data_ptr()), *tail, _lib.stream_ptr()), "crnerf_mlp_forward_f32x3_repair")
     return out
-
-
-def _check_packed(packed, bf16):
-    """The two packed layouts differ in size, so a mix-up is caught here instead of rendering garbage."""
-    lib = _lib.load()
-    want = lib.crnerf_packed_mlp_bf16_bytes() if bf16 else lib.crnerf_packed_mlp_bytes()
-    if isinstance(packed, F16Pack):
-        raise ValueError("crnerf_amd: an f16 pack was handed to the %s entry points (it has the bf16 pack's size and another element type)" % ("bf16" if bf16 else "f32"))
-    if packed is not None and packed.numel() * packed.element_size() != want:
-        raise ValueError("crnerf_amd: packed weights are %d bytes, the %s entry points need %d (pack with precision=%r)"
-                         % (packed.numel() * packed.element_size(), "bf16" if bf16 else "f32", want, "bf16" if bf16 else "f32"))
 
 
 def composite(raw, z, noise=None, noise_std=0.0):
@@ -554,46 +475,34 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     precision="f16": crnerf_render_rays_f16 (packs from pack_mlp_weights(..., precision="f16"); inference only) -- a ray with a point whose operands
     left fp16's range has a NaN feature row.  repair_x3=(coarse x3 pack, fine x3 pack or None): crnerf_render_rays_f32x3_repair re-renders those
     ray quads in the same call, as precision="auto" does behind the h2 core."""
+    name = resolve(precision)
     lib = _lib.load()
     repair = None
-    f16 = _is_f16(precision)
     if repair_x3 is not None:
-        if not f16:
+        if name != "f16":
             raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 packs)")
         repair = tuple(repair_x3)
-    if f16 and (train or rng is not None):
+    if name == "f16" and (train or rng is not None):
         raise ValueError("crnerf_amd: precision='f16' is an inference mode (no training twin, no in-kernel draws)")
-    if _is_auto(precision):
+    if launcher and train:
+        raise ValueError("crnerf_amd: launcher=True is for the inference entry points")
+    if name == "auto":
         # the h2 core with the x3 core as its safety net: render on h2, then crnerf_render_rays_f32x3_repair re-renders the ray quads that came out NaN
         # (a point's activations left fp16's range).  A refused h2 pack (a weight >= 255): the x3 core throughout.
         packs = [pk for pk in (packed_coarse, packed_fine) if pk is not None]
         if any(not isinstance(pk, AutoPack) for pk in packs):
             raise ValueError("crnerf_amd: precision='auto' needs packs from pack_mlp_weights(..., precision='auto')")
         if any(pk.h2 is None for pk in packs):
-            precision = "f32x3"
+            name = "f32x3"
             packed_coarse, packed_fine = packed_coarse.x3, (packed_fine.x3 if packed_fine is not None else None)
         else:
-            precision = "f32h2"
+            name = "f32h2"
             repair = (packed_coarse.x3, packed_fine.x3 if packed_fine is not None else None)
             packed_coarse, packed_fine = packed_coarse.h2, (packed_fine.h2 if packed_fine is not None else None)
-    h2 = _is_h2(precision)                       # fp32 on the fp16 matrix cores (crnerf_render_rays_f32h2; packs from pack_mlp_weights_h2)
-    x3 = _is_x3(precision)                       # fp32 on the bf16 matrix cores (crnerf_render_rays_f32x3; packs from pack_mlp_weights_x3)
-    bf16 = False if (x3 or h2) else _is_bf16(precision)
+    core = _CORES[name]
     want_z_fine = want_z_fine or train
-    if h2:
-        for pk in (packed_coarse, packed_fine):
-            if pk is not None and pk.numel() != lib.crnerf_packed_mlp_h2_bytes():
-                raise ValueError("crnerf_amd: precision='f32h2' needs packs from pack_mlp_weights_h2")
-    elif x3:
-        for pk in (packed_coarse, packed_fine):
-            if pk is not None and pk.numel() != lib.crnerf_packed_mlp_x3_bytes():
-                raise ValueError("crnerf_amd: precision='f32x3' needs packs from pack_mlp_weights_x3")
-    elif f16:
-        _check_packed_f16(packed_coarse)
-        _check_packed_f16(packed_fine)
-    else:
-        _check_packed(packed_coarse, bf16)
-        _check_packed(packed_fine, bf16)
+    _check_pack(lib, name, packed_coarse)
+    _check_pack(lib, name, packed_fine)
     rays = _f32c(rays, "rays")
     if rays.dim() != 2 or rays.shape[1] != 8:
         raise ValueError("rays must be [R,8], got %s" % (tuple(rays.shape),))
@@ -622,7 +531,7 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     for k in ("weights_coarse", "feature_coarse", "depth_coarse", "weights_fine", "feature_fine", "depth_fine", "z_fine"):
         setattr(a, k, out[k].data_ptr() if k in out else None)
     if rng is not None:
-        if bf16:
+        if name == "bf16":
             raise ValueError("crnerf_amd: in-kernel random draws exist in the fp32 kernels only")
         flags = (_lib.RNG_JITTER if rng.get("jitter") else 0) | (_lib.RNG_U if (rng.get("u") and Ni > 0) else 0) | (_lib.RNG_NOISE if rng.get("noise") else 0)
         a.rng_seed, a.rng_ray_offset, a.rng_flags, a.perturb = int(rng["seed"]) & (2 ** 64 - 1), int(rng.get("ray_offset", 0)), flags, float(rng.get("perturb", 1.0))
@@ -634,50 +543,33 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
             if Ni > 0:
                 out["noise_fine_used"] = new(R, Nc + Ni)
                 a.noise_fine_out = out["noise_fine_used"].data_ptr()
-    if launcher:      # measurement helper: re-launch the same call on the same buffers with nothing but the C call on the host side
-        if train:
-            raise ValueError("crnerf_amd: launcher=True is for the inference entry points")
-        fn = lib.crnerf_render_rays_f16 if f16 else lib.crnerf_render_rays_f32h2 if h2 else (lib.crnerf_render_rays_f32x3 if x3 else (lib.crnerf_render_rays_bf16 if bf16 else lib.crnerf_render_rays_f32))
-        name = "crnerf_render_rays_f16" if f16 else "crnerf_render_rays_f32h2" if h2 else ("crnerf_render_rays_f32x3" if x3 else ("crnerf_render_rays_bf16" if bf16 else "crnerf_render_rays_f32"))
-        held = (keep, rays, packed_coarse, packed_fine, out, repair)  # the argument struct holds raw pointers: keep EVERY tensor behind them alive
-        # (the outputs too: a caller that drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
-        a2 = _repair_args(a, repair)
-
-        def launch(_held=held):
-            _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), name)
-            if a2 is not None:
-                _lib.check(lib.crnerf_render_rays_f32x3_repair(ctypes.byref(a2), _lib.stream_ptr()), "crnerf_render_rays_f32x3_repair")
-        return launch, out
     if train:
         Nf = Nc + Ni
-        acts_bytes = lib.crnerf_mlp_train_mixed_acts_bytes if bf16 else lib.crnerf_mlp_train_acts_bytes
+        acts_bytes = lib.crnerf_mlp_train_mixed_acts_bytes if name == "bf16" else lib.crnerf_mlp_train_acts_bytes
         out["acts_coarse"] = torch.empty(acts_bytes(R * Nc), dtype=torch.uint8, device=dev)
         out["raw_coarse"] = new(R, Nc, 65)
         if Ni > 0:
             out["acts_fine"] = torch.empty(acts_bytes(R * Nf), dtype=torch.uint8, device=dev)
             out["raw_fine"] = new(R, Nf, 65)
         vp = lambda k: ctypes.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
-        fn, name = ((lib.crnerf_render_rays_train_f32h2, "crnerf_render_rays_train_f32h2") if h2 else
-                    (lib.crnerf_render_rays_train_f32x3, "crnerf_render_rays_train_f32x3") if x3 else
-                    (lib.crnerf_render_rays_train_bf16, "crnerf_render_rays_train_bf16") if bf16 else
-                    (lib.crnerf_render_rays_train_f32, "crnerf_render_rays_train_f32"))
-        _lib.check(fn(ctypes.byref(a), vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine"), _lib.stream_ptr()), name)
+        saved = (vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine"))
+        _lib.check(getattr(lib, core.render_train)(ctypes.byref(a), *saved, _lib.stream_ptr()), core.render_train)
         a2 = _repair_args(a, repair)
         if a2 is not None:        # precision="auto": the ray quads the h2 twin poisoned, once more on the scale-free core -- outputs AND saved state
-            _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine"),
-                                                                 _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
+            _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), *saved, _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
         return out
-    if h2 or f16:
-        if f16:
-            _lib.check(lib.crnerf_render_rays_f16(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f16")
-        else:
-            _lib.check(lib.crnerf_render_rays_f32h2(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f32h2")
-        a2 = _repair_args(a, repair)
-        if a2 is not None:
+    fn, a2 = getattr(lib, core.render), _repair_args(a, repair)
+    # the argument structs hold raw pointers: a launcher that outlives this call keeps EVERY tensor behind them alive (the outputs too: a caller that
+    # drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
+    held = (keep, rays, packed_coarse, packed_fine, out, repair)
+
+    def launch(_held=held):
+        _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), core.render)
+        if a2 is not None:        # "auto" / repair_x3=: the ray quads the fp16 range guard poisoned, once more on the scale-free core
             _lib.check(lib.crnerf_render_rays_f32x3_repair(ctypes.byref(a2), _lib.stream_ptr()), "crnerf_render_rays_f32x3_repair")
-        return out
-    fn = lib.crnerf_render_rays_f32x3 if x3 else (lib.crnerf_render_rays_bf16 if bf16 else lib.crnerf_render_rays_f32)
-    _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_f32x3" if x3 else ("crnerf_render_rays_bf16" if bf16 else "crnerf_render_rays_f32"))
+    if launcher:      # measurement helper: re-launch the same call on the same buffers with nothing but the C call on the host side
+        return launch, out
+    launch()
     return out
 
 
@@ -686,7 +578,7 @@ def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_i
     """crnerf_render_rays_bf16_fine: sample_pdf + z merge on `weights_coarse` [R,Nc] (rendered by another core, e.g. render_rays(..., n_importance=0,
     precision="auto")) and the fine model on the bf16 matrix cores, fused -- {"weights_fine", "feature_fine", "depth_fine"[, "z_fine"]}."""
     lib = _lib.load()
-    _check_packed(packed_fine_bf16, True)
+    _check_pack(lib, "bf16", packed_fine_bf16)
     rays, weights_coarse = _f32c(rays, "rays"), _f32c(weights_coarse, "weights_coarse")
     R, dev = rays.shape[0], rays.device
     Nc, Ni = int(n_samples), int(n_importance)

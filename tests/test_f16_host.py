@@ -3,7 +3,7 @@ import os
 import re
 
 import crnerf_amd
-from crnerf_amd import _lib, ops
+from crnerf_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F16_SYMBOLS = ["crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16"]
@@ -34,8 +34,9 @@ def test_f16_symbols_are_declared_and_bound():
 
 
 def test_f16_is_a_precision_of_its_own():
-    assert ops._is_f16("f16") and not ops._is_f16("bf16") and not ops._is_f16("f32h2")
-    assert ops._is_bf16("f16") is False                     # not an unknown string, and not bf16
+    from crnerf_amd.precision import resolve
+    assert resolve("f16") == "f16" and resolve("bf16") != "f16" and resolve("f32h2") != "f16"
+    assert resolve("f16") != "bf16"                         # not an unknown string, and not bf16
 
 
 def test_new_units_are_audited_and_built():

@@ -871,3 +871,55 @@ def test_sharded_decode_phases_match_fused_decode_single_rank():
         close(decode_sharded(net, feat, style), ref.cpu(), atol=2e-6)
     finally:
         dist.destroy_process_group()
+
+
+# ------------------------------------------------------------------ every spelling of a precision is the same call (precision.py)
+@torch.no_grad()
+def test_every_spelling_of_a_precision_is_the_same_call():
+    """6 rays = one full ray quad and a ragged one (what the repair launches group by), 4 + 4 samples, weights well inside fp16's range."""
+    from crnerf_amd.models.nerf import NeRF_sigma, PosEmbedding
+    from crnerf_amd.models.rendering import render_rays_cross_ray
+    from crnerf_amd.precision import ALIASES, COMPOSITE, CORES
+    R, Nc, Ni = 6, 4, 4
+
+    class Args:
+        nerf_out_dim, img_wh, pertubeCord = 64, [3, 2], False
+    states = [{k: C(v) for k, v in synth.mlp_state(seed, 1.5).items()} for seed in (41, 42)]
+    models = {}
+    for typ, st in zip(("coarse", "fine"), states):
+        models[typ] = NeRF_sigma(typ, Args(), in_channels_xyz=93, in_channels_dir=27).to(DEV)
+        models[typ].load_state_dict(st)
+    emb = {"xyz": PosEmbedding(14, 15), "dir": PosEmbedding(3, 4)}
+    rays = C(synth.rays(R, seed=3))
+    zt, ut = torch.linspace(0, 1, Nc, device=DEV), torch.linspace(0, 1, Ni, device=DEV)
+    x = C(np.random.default_rng(7).uniform(-1, 1, (R * Nc, 120)).astype(np.float32))
+    spellings = lambda name: [s for s, n in ALIASES.items() if n == name]  # noqa: E731
+
+    def same(got, want, what):
+        assert list(got.keys()) == list(want.keys()), what
+        for k in want:
+            assert torch.equal(got[k], want[k]), (what, k)
+
+    for name in CORES + ("auto",):
+        pc, pf = (ops.pack_mlp_weights(st, precision=name) for st in states)
+        want_r = ops.render_rays(pc, pf, rays, Nc, Ni, z_steps=zt, u=ut, precision=name)
+        want_m = ops.mlp_forward(pc, x, precision=name)
+        assert all(bool(torch.isfinite(v).all()) for v in want_r.values()) and bool(torch.isfinite(want_m).all()), name
+        assert len(spellings(name)) >= 2
+        for s in spellings(name):
+            same(ops.render_rays(pc, pf, rays, Nc, Ni, z_steps=zt, u=ut, precision=s), want_r, (name, s))
+            assert torch.equal(ops.mlp_forward(pc, x, precision=s), want_m), (name, s)
+            assert torch.equal(models["coarse"](x, precision=s), want_m), (name, s)
+            assert models["coarse"].packed_weights(s) is models["coarse"].packed_weights(name), (name, s)      # one cache slot per core
+
+    def call(prec, ni=Ni, perturb=0):
+        torch.manual_seed(5)                                     # perturb > 0 outside grad mode draws with torch's generators
+        return render_rays_cross_ray(models, emb, rays, None, Nc, False, perturb, 0, ni, 32768, False, test_time=True, args=Args(), precision=prec)
+    bf16 = call("bf16")
+    for name in COMPOSITE:
+        want = call(name)
+        assert not torch.equal(want["weights_coarse"], bf16["weights_coarse"]), name      # the mode itself, not its fall-through
+        for s in spellings(name):
+            same(call(s), want, (name, s))
+            same(call(s, ni=0), call("bf16", ni=0), (name, s, "N_importance=0"))
+            same(call(s, perturb=1.0), call("bf16", perturb=1.0), (name, s, "perturb>0"))
