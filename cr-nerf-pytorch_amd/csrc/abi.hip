@@ -298,6 +298,26 @@ int crnerf_render_rays_bf16_fine(const crnerf_render_args* a, void* stream) {
   return launch_render_rays_bf16p(r, (hipStream_t)stream);
 }
 
+int crnerf_render_rays_lean_f32(const crnerf_render_args* a, void* stream) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: negative n_rays");
+  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_importance must be in [1, 256]");
+  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_samples must be in [3, 256]");
+  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays");
+  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
+  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
+    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean: no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)");
+  RenderArgs r;
+  r.packed_coarse = a->packed_coarse; r.packed_fine = a->packed_fine; r.rays = a->rays; r.view_dir = a->view_dir;
+  r.z_coarse = a->z_coarse; r.z_steps = a->z_steps; r.u = a->u; r.u_stride = (long)a->u_stride; r.noise_coarse = a->noise_coarse; r.noise_fine = a->noise_fine;
+  r.noise_std = a->noise_std; r.use_disp = a->use_disp; r.R = (long)a->n_rays; r.Nc = a->n_samples; r.Ni = a->n_importance;
+  r.weights_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr;   // ignored, whatever the caller passed
+  r.feature_fine = a->feature_fine; r.depth_fine = a->depth_fine; r.z_fine = a->z_fine;
+  r.lean = 1;
+  return launch_render_rays16(r, (hipStream_t)stream);
+}
+
 size_t crnerf_packed_mlp_mixed_bytes(void) { return gemm_packed_bytes(); }
 size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_acts_bytes((long)n); }
 size_t crnerf_mlp_train_mixed_scratch_bytes(int64_t n) { return mlp_train_mixed_scratch_bytes((long)n); }

@@ -121,6 +121,8 @@ struct RenderArgs {
   int repair = 0;
   // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT (rendered by another core); sample_pdf + merge + the fine pass only
   int fine_only = 0;
+  // crnerf_render_rays_lean_f32 (render_fused16.hip): trunk-only coarse pass; writes feature_fine, depth_fine and (optional) z_fine only
+  int lean = 0;
   // training twin (crnerf_render_rays_train_f32; all null for inference): saved activations + raw MLP outputs per pass
   void* train_acts_coarse = nullptr;   // crnerf_mlp_train_acts_bytes(R*Nc)
   void* train_acts_fine = nullptr;     // crnerf_mlp_train_acts_bytes(R*(Nc+Ni))

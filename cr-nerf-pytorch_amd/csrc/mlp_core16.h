@@ -32,7 +32,15 @@ constexpr int U_DIR = DIR_PAD / 16;   // 2
 constexpr int U_HALF = 128 / 16;      // 8
 
 // Same ring protocol as WeightPipe (mlp_core.h), 8 waves x 2 pieces per stage.
-struct WeightPipe16 {
+// TRUNK0 (the lean renderer, render_fused16.hip): a walk of stream 0 (pass index < passes0) ends with xyz_encoding_8 -- mlp_tile16 leaves after the
+// sigma head -- so it is TRUNK_STAGES long and the prefetcher turns to the base of the next walk's stream there.  Nothing else moves: the ring, the
+// look-ahead queue and the vmcnt windows count stages and pieces in flight, never a position in the stream.  A template parameter, so that every
+// other user of the pipe compiles to the code it had.
+constexpr int TRUNK_STAGES = OFF_FIN / STAGE_FRAGS;   // 124 of the 151
+static_assert(OFF_FIN % STAGE_FRAGS == 0, "the trunk must be whole stages");
+template <bool TRUNK0>
+struct WeightPipe16T {
+  static constexpr bool trunk0 = TRUNK0;
   lds_char* lds;
   const char* base[2];   // wave-uniform: packed streams + this wave's 2 KiB column (the lane offset rides in the VGPR-offset operand)
   const char* pf_ptr;
@@ -54,6 +62,7 @@ struct WeightPipe16 {
         pf_left = stages_per_pass;
         pf_pass = (pf_pass + 1 == passes) ? 0 : pf_pass + 1;
         pf_ptr = (pf_pass < passes0) ? base[0] : base[1];
+        if (TRUNK0 && pf_pass < passes0) pf_left = TRUNK_STAGES;
       }
     }
   }
@@ -71,7 +80,7 @@ struct WeightPipe16 {
     passes0 = passes0_;
     passes = passes_;
     pf_pass = 0;
-    pf_left = stages_per_pass;
+    pf_left = (TRUNK0 && passes0 > 0) ? TRUNK_STAGES : stages_per_pass;
     pf_ptr = (passes0 > 0) ? base[0] : base[1];
     pf_slot = 0;
     rd_slot = 0;
@@ -107,6 +116,7 @@ struct WeightPipe16 {
     for (int i = 0; i < V16_AHEAD; ++i) q[i] = read_slot(i);
   }
 };
+typedef WeightPipe16T<false> WeightPipe16;
 
 // acc[T][r] = bias[16T + 4g + r]
 template <int NT>
@@ -133,8 +143,8 @@ struct DeferredActs {   // the ND tiles of `a` go to `row`, one piece per call
   __device__ __forceinline__ void piece(int T) const { save.piece(row, T, a[T]); }
 };
 
-template <int NT, int NGA, int NGB, int NA, int NB, class DEF = NoDeferred>
-__device__ __forceinline__ void mma_layer16(WeightPipe16& p, const f32x4 (&srcA)[NA], const f32x4 (&srcB)[NB], f32x4 (&acc)[NT],
+template <int NT, int NGA, int NGB, int NA, int NB, class DEF = NoDeferred, class PIPE>
+__device__ __forceinline__ void mma_layer16(PIPE& p, const f32x4 (&srcA)[NA], const f32x4 (&srcB)[NB], f32x4 (&acc)[NT],
                                             f32x4 (&q)[V16_AHEAD], const DEF& def = DEF()) {
   static_assert(NGA <= NA && NGB <= NB, "source too small");
   constexpr int NF = (NGA + NGB) * NT;
@@ -202,8 +212,10 @@ struct DirLds {
   }
 };
 
-template <class DIR, class SAVE = NoSave>
-__device__ __forceinline__ void mlp_tile16(WeightPipe16& p, int model, const f32x4 (&pe)[6], const DIR& dir,
+// A WeightPipe16T<true> pipe: model 0 is walked trunk-only -- the tile returns behind the sigma head, feat[] = 0.  `model` is
+// wave-uniform and the same in all eight waves (the ring's barriers need identical control flow).
+template <class DIR, class SAVE = NoSave, class PIPE>
+__device__ __forceinline__ void mlp_tile16(PIPE& p, int model, const f32x4 (&pe)[6], const DIR& dir,
                                            f32x4 (&feat)[4], float& sigma, int g, f32x4 (&q)[V16_AHEAD], PhaseTimer& tm,
                                            const SAVE& save = SAVE()) {
   const lds_float* C = (const lds_float*)(p.lds + (model ? LDS_CONST1 : LDS_CONST0));
@@ -260,6 +272,11 @@ __device__ __forceinline__ void mlp_tile16(WeightPipe16& p, int model, const f32
     sigma = softplus_ref(s + C[C_BSIG]);
   }
   tm.tick(T_SIGMA);
+  if (PIPE::trunk0 && model == 0) {                      // q[] already holds the first fragments of the next walk
+#pragma unroll
+    for (int T = 0; T < 4; ++T) feat[T] = f32x4{0, 0, 0, 0};   // defined, not read: left undefined, the merge costs the caller 20 more spilled registers
+    return;
+  }
   init_acc16<16>(acc, C + C_BFIN, g);                    // xyz_encoding_final (no activation)
   mma_layer16<16, U_HID, 0>(p, act, act, acc, q, Def16{save, row, act});
   tm.tick(T_MMA);

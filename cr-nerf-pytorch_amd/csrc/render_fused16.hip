@@ -58,7 +58,12 @@ struct TrainHook {
 // RNG: the instantiation with the in-kernel random draws (philox.h).  It is a template parameter, not a runtime flag: the keys, the
 // global ray index and three more output pointers would otherwise be live across the MLP of EVERY launch (measured: 10 -> 20
 // spilled registers in the inference kernel, 77 -> 90 in the training twin).
-template <bool RNG, class HOOK>
+// LEAN (crnerf_render_rays_lean_f32): the inference render that keeps only what an image needs.  The coarse pass exists for its compositing
+// weights alone (they feed sample_pdf) and those depend on sigma alone, so its tiles walk the trunk only (WeightPipe16T<true>: 124 of the 151
+// stages), no feature is composited and nothing of it is stored; the fine pass is the full one without the weights_fine store.  What is left
+// executes the full kernel's instructions in the full kernel's order: feature_fine / depth_fine / z_fine are bit-identical.  A template
+// parameter for the reason RNG is one: the other instantiations keep their code.
+template <bool RNG, class HOOK, bool LEAN = false>
 __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, const HOOK& hook) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* lds = (lds_char*)smem;
@@ -75,7 +80,7 @@ __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, cons
   lds_float* dirbuf = (lds_float*)(lds + LDS_SCRATCH + 4 * PAIR_BYTES) + wave * 32;   // 32 floats per wave
 
   const int steps_c = (Nc + 31) >> 5, steps_f = Ni > 0 ? (Nf + 31) >> 5 : 0;
-  WeightPipe16 pipe;
+  WeightPipe16T<LEAN> pipe;
   pipe.start(lds, a.packed0 + CONST_BYTES, a.packed1 + CONST_BYTES, steps_c, steps_c + steps_f, lane, wave);
   f32x4 q[V16_AHEAD];
   pipe.prime(q);
@@ -132,7 +137,8 @@ __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, cons
       const int N = pass ? Nf : Nc;
       const lds_float* zsrc = pass ? scr.zs : scr.zc;
       const float* noise_row = pass ? (a.noise_f ? a.noise_f + r * Nf : nullptr) : (a.noise_c ? a.noise_c + r * Nc : nullptr);
-      float* weights_row = pass ? a.weights_f + r * Nf : a.weights_c + r * Nc;
+      float* weights_row = LEAN ? nullptr : (pass ? a.weights_f + r * Nf : a.weights_c + r * Nc);
+      const bool compose = !LEAN || pass;     // wave-uniform, and the same in all eight waves
       double carry = 1.0;
       f32x4 facc[4];
 #pragma unroll
@@ -178,33 +184,37 @@ __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, cons
         const float Tr = (float)(half ? carry * prod_a * excl : carry * excl);
         carry = carry * prod_a * prod_b;
         const float w = alpha * Tr;
+        if (compose) {
 #pragma unroll
-        for (int T = 0; T < 4; ++T)
+          for (int T = 0; T < 4; ++T)
 #pragma unroll
-          for (int rr2 = 0; rr2 < 4; ++rr2) facc[T][rr2] += w * feat[T][rr2];
-        dacc += w * zn;
+            for (int rr2 = 0; rr2 < 4; ++rr2) facc[T][rr2] += w * feat[T][rr2];
+          dacc += w * zn;
+        }
         if (valid && g == 0) {
-          if (ray_ok) weights_row[n] = w;
+          if (!LEAN && ray_ok) weights_row[n] = w;
           if (pass == 0) scr.wc[n] = w;
         }
         tm.tick(T_COMPOSITE);
       }
-      // per-wave reduction over the 16 point lanes, then pair combine through LDS
+      // per-wave reduction over the 16 point lanes, then pair combine through LDS (compose is tested per round: the form that spills least)
+      {
 #pragma unroll
-      for (int d = 8; d >= 1; d >>= 1) {
+        for (int d = 8; d >= 1; d >>= 1) if (compose) {
 #pragma unroll
-        for (int T = 0; T < 4; ++T)
+          for (int T = 0; T < 4; ++T)
 #pragma unroll
-          for (int rr2 = 0; rr2 < 4; ++rr2) facc[T][rr2] += __shfl_xor(facc[T][rr2], d);
-        dacc += __shfl_xor(dacc, d);
+            for (int rr2 = 0; rr2 < 4; ++rr2) facc[T][rr2] += __shfl_xor(facc[T][rr2], d);
+          dacc += __shfl_xor(dacc, d);
+        }
+        if (compose && half == 1 && p == 0) {
+#pragma unroll
+          for (int T = 0; T < 4; ++T) *(__attribute__((address_space(3))) f32x4*)(scr.xfeat + 16 * T + 4 * g) = facc[T];
+          if (g == 0) scr.xfeat[64] = dacc;
+        }
       }
-      if (half == 1 && p == 0) {
-#pragma unroll
-        for (int T = 0; T < 4; ++T) *(__attribute__((address_space(3))) f32x4*)(scr.xfeat + 16 * T + 4 * g) = facc[T];
-        if (g == 0) scr.xfeat[64] = dacc;
-      }
-      wg_barrier();
-      if (half == 0 && p == 0 && ray_ok) {
+      wg_barrier();   // (a lean coarse pass too: the last step's scr.wc[] must be in LDS before sample_pdf_pair reads it)
+      if (compose && half == 0 && p == 0 && ray_ok) {
         float* frow = (pass ? a.feature_f : a.feature_c) + r * FEAT_DIM;
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
@@ -237,6 +247,7 @@ __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, cons
 
 __global__ __launch_bounds__(512, 2) void render_rays16_kernel(RenderParams16 a) { render_rays16_impl<false>(a, NoHook{}); }
 __global__ __launch_bounds__(512, 2) void render_rays16_rng_kernel(RenderParams16 a) { render_rays16_impl<true>(a, NoHook{}); }
+__global__ __launch_bounds__(512, 2) void render_rays16_lean_kernel(RenderParams16 a) { render_rays16_impl<false, NoHook, true>(a, NoHook{}); }
 
 // Fused TRAINING forward: the same launch (posenc -> MLP -> compositing, coarse -> sample_pdf -> fine) that also keeps what
 // the backward twins need -- no [P,93] / [P,120] embeddings and no separate compositing pass ever exist in HBM.
@@ -265,6 +276,13 @@ int launch_render_rays16(const RenderArgs& a, hipStream_t stream) {
   k.iters = (int)((quads + grid - 1) / grid);
   k.sched = k.iters > 1 ? sched_slot((const void*)crnerf_sched16) : nullptr;
   const size_t shmem = LDS_SCRATCH + 4 * PAIR_BYTES + V16_WAVES * 32 * sizeof(float) + 16;
+  if (a.lean) {   // crnerf_render_rays_lean_f32: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
+    if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
+    if (a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
+    if (int rc = ensure_dynamic_lds((const void*)render_rays16_lean_kernel, shmem, "render_rays16_lean_kernel")) return rc;
+    hipLaunchKernelGGL(render_rays16_lean_kernel, dim3(grid), dim3(512), shmem, stream, k);
+    return check_launch("render_rays16_lean_kernel");
+  }
   if (a.train_acts_coarse) {
     if (a.Ni > 0 && (!a.train_acts_fine || !a.train_raw_fine)) return set_error(-1, "render_rays_train: fine buffers are NULL");
     if (!a.train_raw_coarse) return set_error(-1, "render_rays_train: raw_coarse is NULL");

@@ -136,7 +136,12 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     One keyword beyond the reference's: precision="f32"|"bf16"|"f32x3"|"f32h2"|"auto"|"bf16_hc"|"bf16_fc"|"f16" (default crnerf_amd.get_precision()) selects the
     matrix-core arithmetic of NeRF_sigma at inference (include/crnerf.h).  Grad mode trains through the exact-fp32 twins unless
     the caller opted into mixed precision (autograd.set_training_precision("bf16") / CRNERF_TRAIN_BF16=1: bf16-operand GEMM twins,
-    fp32 accumulation; autograd.set_wgrad_precision("bf16"): weight gradients only) -- neither has a counterpart in the reference."""
+    fp32 accumulation; autograd.set_wgrad_precision("bf16"): weight gradients only) -- neither has a counterpart in the reference.
+    lean=True (another keyword of this mirror; inference only, ValueError in grad mode with trainable models): the caller reads the fine image alone.
+    With N_importance > 0 the result holds exactly feature_<fine.typ>, depth_<fine.typ> and (under its usual condition) feature_fine_random, with
+    the values of the ordinary call.  precision "f32", no pertubeCord, 3 <= N_samples <= 256, N_importance <= 256: crnerf_render_rays_lean_f32 --
+    the coarse pass stops behind the sigma head and nothing of it goes to HBM; every other case renders as without the flag and drops the other
+    keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
     args = kwargs['args']
     jitter = bool(getattr(args, 'pertubeCord', False))
     if getattr(args, 'nerf_out_dim', 64) != 64:
@@ -149,6 +154,10 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         if m is not None and not isinstance(m, NeRF_sigma):
             raise NotImplementedError("crnerf_amd: models must be crnerf_amd NeRF_sigma instances")
     train = torch.is_grad_enabled() and any(ops.any_requires_grad(m) for m in (coarse, fine) if m is not None)
+    lean = bool(kwargs.get('lean', False))
+    if lean and train:
+        raise ValueError("crnerf_amd: lean=True is an inference render; call it under torch.no_grad() (or with frozen models)")
+    lean = lean and N_importance > 0
     precision = kwargs.get('precision', None)
     if precision is None:
         from .. import get_precision
@@ -205,8 +214,16 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         out = ops.render_rays(coarse.packed_weights(precision), fine.packed_weights(precision) if fine is not None else None, rays,
                               N_samples, N_importance, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse,
                               z_steps=tables[0], u=u if u is not None else tables[1],
-                              noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std), precision=precision)
+                              noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std), precision=precision,
+                              lean=lean and precision == "f32" and N_samples >= 3)
 
+    if lean:    # the lean kernel wrote nothing else; the other paths rendered as usual and their other tensors are dropped here
+        typ_f = fine.typ
+        results = {'feature_%s' % typ_f: out['feature_fine']}
+        if kwargs.get('output_random', True) and fine.encode_random:
+            results['feature_fine_random'] = out['feature_fine']
+        results['depth_%s' % typ_f] = out['depth_fine']
+        return results
     typ_c = coarse.typ
     results = {'weights_%s' % typ_c: out['weights_coarse'], 'feature_%s' % typ_c: out['feature_coarse'],
                'depth_%s' % typ_c: out['depth_coarse']}

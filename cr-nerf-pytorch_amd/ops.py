@@ -460,7 +460,7 @@ def sample_pdf_merge(z_coarse, weights_coarse, n_importance, u=None, return_samp
 
 def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
                 noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, precision="f32", train=False, launcher=False, rng=None,
-                repair_x3=None):
+                repair_x3=None, lean=False):
     """Fused renderer.  Returns a dict of freshly allocated tensors.  train=True: the training twin
     crnerf_render_rays_train_f32 -- the dict additionally holds what the backward needs: z_coarse (as used), z_fine,
     acts_coarse / acts_fine (crnerf_mlp_forward_train_f32 layout, point = ray * N + sample) and raw_coarse / raw_fine [R,N,65].
@@ -474,10 +474,19 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     "noise_fine_used" (standard normal, before noise_std).  rng_fill() returns the same draws as tensors.
     precision="f16": crnerf_render_rays_f16 (packs from pack_mlp_weights(..., precision="f16"); inference only) -- a ray with a point whose operands
     left fp16's range has a NaN feature row.  repair_x3=(coarse x3 pack, fine x3 pack or None): crnerf_render_rays_f32x3_repair re-renders those
-    ray quads in the same call, as precision="auto" does behind the h2 core."""
+    ray quads in the same call, as precision="auto" does behind the h2 core.
+    lean=True (precision="f32", inference, n_importance > 0): crnerf_render_rays_lean_f32 -- the coarse pass stops behind the sigma head and nothing of
+    it reaches HBM; the dict holds feature_fine, depth_fine and (want_z_fine) z_fine only, bit-identical to the full call's."""
     name = resolve(precision)
     lib = _lib.load()
     repair = None
+    if lean:
+        if train or rng is not None:
+            raise ValueError("crnerf_amd: lean=True is an inference render (no training twin, no in-kernel draws: hand them over as tensors)")
+        if name != "f32":
+            raise ValueError("crnerf_amd: lean=True exists for precision='f32' (the trunk-only coarse walk is built on the fp32 core), got %r" % (name,))
+        if int(n_importance) <= 0:
+            raise ValueError("crnerf_amd: lean=True needs n_importance > 0 (it returns the fine pass only)")
     if repair_x3 is not None:
         if name != "f16":
             raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 packs)")
@@ -509,11 +518,14 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     R, dev = rays.shape[0], rays.device
     Nc, Ni = int(n_samples), int(n_importance)
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    out = {"weights_coarse": new(R, Nc), "feature_coarse": new(R, 64), "depth_coarse": new(R)}
-    if Ni > 0:
-        out.update({"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)})
-        if want_z_fine:
-            out["z_fine"] = new(R, Nc + Ni)
+    if lean:
+        out = {"feature_fine": new(R, 64), "depth_fine": new(R)}
+    else:
+        out = {"weights_coarse": new(R, Nc), "feature_coarse": new(R, 64), "depth_coarse": new(R)}
+        if Ni > 0:
+            out.update({"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)})
+    if Ni > 0 and want_z_fine:
+        out["z_fine"] = new(R, Nc + Ni)
     if R == 0:
         return out
     keep = [t if t is None else _f32c(t, n) for t, n in ((view_dir, "view_dir"), (z_coarse, "z_coarse"), (z_steps, "z_steps"), (u, "u"),
@@ -558,13 +570,14 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
         if a2 is not None:        # precision="auto": the ray quads the h2 twin poisoned, once more on the scale-free core -- outputs AND saved state
             _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), *saved, _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
         return out
-    fn, a2 = getattr(lib, core.render), _repair_args(a, repair)
+    fn_name = "crnerf_render_rays_lean_f32" if lean else core.render
+    fn, a2 = getattr(lib, fn_name), _repair_args(a, repair)
     # the argument structs hold raw pointers: a launcher that outlives this call keeps EVERY tensor behind them alive (the outputs too: a caller that
     # drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
     held = (keep, rays, packed_coarse, packed_fine, out, repair)
 
     def launch(_held=held):
-        _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), core.render)
+        _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), fn_name)
         if a2 is not None:        # "auto" / repair_x3=: the ray quads the fp16 range guard poisoned, once more on the scale-free core
             _lib.check(lib.crnerf_render_rays_f32x3_repair(ctypes.byref(a2), _lib.stream_ptr()), "crnerf_render_rays_f32x3_repair")
     if launcher:      # measurement helper: re-launch the same call on the same buffers with nothing but the C call on the host side

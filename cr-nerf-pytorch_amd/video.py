@@ -76,15 +76,15 @@ def define_camera(img_wh):
 
 @torch.no_grad()
 def render_video(models, embeddings, enc_a, style_img, hparams_, scene="brandenburg_gate", n_frames=N_FRAMES, rank=0, world_size=1,
-                 chunk=32768, precision=None, near=0.0, far=5.0):
+                 chunk=32768, precision=None, near=0.0, far=5.0, lean=False):
     """Frames rank, rank + world_size, ... of the fly-through as uint8 [H,W,3] arrays (the reference writes PNGs + a GIF,
-    :255-262).  style_img: [1,3,h,w] in [0,1] (the 1/8-scale example image, :236-246)."""
+    :255-262).  style_img: [1,3,h,w] in [0,1] (the 1/8-scale example image, :236-246).  lean: pipeline.render_frame's (same frames, less work)."""
     w, h = hparams_.img_wh
     K, poses = define_camera(hparams_.img_wh), define_poses(scene, n_frames)
     frames = {}
     a_emb = enc_a(style_img)            # once per style image, as the reference (appearance_modification_video.py:239)
     for i in range(rank, n_frames, world_size):
         img = pipeline.render_frame(models, embeddings, enc_a, style_img, h, w, K, poses[i].astype(np.float32), hparams_, near=near, far=far,
-                                    chunk=chunk, precision=precision, a_emb=a_emb)
+                                    chunk=chunk, precision=precision, a_emb=a_emb, lean=lean)
         frames[i] = (img.clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
     return frames

@@ -202,7 +202,19 @@ typedef struct crnerf_render_args {
 int crnerf_rng_fill_f32(float* out, int64_t n_rays, int n, uint64_t seed, int stream, int64_t ray_offset, void* stream_handle);
 int crnerf_render_rays_f32(const crnerf_render_args* args, void* stream);
 
-/* Training twin of the call above (the reference trains THROUGH render_rays_cross_ray under autograd, rendering.py:100-143):
+/* Lean inference render (no counterpart in the reference, whose test_time flag, models/rendering.py:61, is carried and unused): crnerf_render_rays_f32
+ * for a caller that reads only the fine image.  The coarse pass is evaluated for its compositing weights alone -- they feed sample_pdf, and they
+ * depend on sigma alone -- so its points stop behind xyz_encoding_8 / static_sigma (124 of the 151 stages of the weight stream; xyz_encoding_final,
+ * dir_encoding and static_rgb are skipped), no coarse feature is composited, and neither the coarse outputs nor weights_fine go to HBM.
+ *   Same struct, same packs (crnerf_pack_mlp_weights).  Requires n_importance in [1,256], n_samples in [3,256] (CRNERF_ERR_SHAPE) and packed_fine.
+ * weights_coarse, feature_coarse, depth_coarse and weights_fine are ignored (may be NULL); feature_fine and depth_fine are required, z_fine is
+ * optional.  z_coarse, z_steps, u / u_stride, noise_coarse / noise_fine, noise_std, view_dir and use_disp as in crnerf_render_rays_f32.
+ * rng_flags != 0 or any *_out pointer returns CRNERF_ERR_CONFIG (random draws come as tensors; crnerf_rng_fill_f32 makes the in-kernel ones).
+ *   feature_fine, depth_fine and z_fine are BIT-IDENTICAL to crnerf_render_rays_f32's on the same arguments: what is left runs the same
+ * instructions in the same order (tests/test_gpu_lean.py). */
+int crnerf_render_rays_lean_f32(const crnerf_render_args* args, void* stream);
+
+/* Training twin of crnerf_render_rays_f32 (the reference trains THROUGH render_rays_cross_ray under autograd, rendering.py:100-143):
  * the same fused launch -- positional encoding, both NeRF_sigma passes, compositing, sample_pdf + merge -- that additionally
  * keeps what the backward twins need: per pass the layer activations in the crnerf_mlp_forward_train_f32 layout
  * (acts_*: crnerf_mlp_train_acts_bytes(R*N) bytes, point index = ray*N + sample) and the raw MLP outputs raw_*[R*N,65].
