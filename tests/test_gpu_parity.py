@@ -35,9 +35,10 @@ def close(got, want, atol, rtol=0.0):
     torch.testing.assert_close(got.detach().float().cpu(), torch.as_tensor(want).float(), atol=atol, rtol=rtol)
 
 
-def assert_depths(z_got, z_ref, z_coarse, w_coarse, tight=3e-5):
+def assert_depths(z_got, z_ref, z_coarse, w_coarse, tight=3e-5, min_well=0.5):
     """Sorted fine depths: |dz| <= tight wherever the coarse pdf around the sample is well-conditioned;
-    everywhere else the sample must stay inside the coarse interval the reference put it in."""
+    everywhere else the sample must stay inside the coarse interval the reference put it in.
+    min_well: the share of well-conditioned depths the case must have (a guard on the inputs, not on the kernel)."""
     z_got, z_ref = z_got.detach().cpu().double(), torch.as_tensor(z_ref).double()
     zc, w = torch.as_tensor(z_coarse).double(), torch.as_tensor(w_coarse).double()
     d = (z_got - z_ref).abs()
@@ -48,7 +49,7 @@ def assert_depths(z_got, z_ref, z_coarse, w_coarse, tight=3e-5):
     mass = pdf.gather(1, idx)
     bin_w = (mid[:, 1:] - mid[:, :-1]).gather(1, idx)
     well = mass > 2e-3
-    assert float(well.double().mean()) > 0.5
+    assert float(well.double().mean()) > min_well
     assert float(d[well].max()) <= tight, "well-conditioned depths differ by %g" % float(d[well].max())
     assert bool((d[~well] <= bin_w[~well] + tight).all()), "ill-conditioned depth left its coarse interval"
     assert bool((z_got[:, 1:] >= z_got[:, :-1]).all()), "depths not ascending"
@@ -284,6 +285,10 @@ def test_render_other_sample_counts_vs_oracle(nc, ni):
     close(out["weights_coarse"], ref["weights_coarse"], atol=3e-6)
     close(out["feature_coarse"], ref["feature_coarse"], atol=1e-5)
     zf = out["z_fine"].cpu()
+    # the sampler alone: the oracle's depths on the kernel's OWN coarse weights
+    z_coarse, w_own = O.coarse_depths(rays, nc, False, zt), out["weights_coarse"].cpu()
+    # (33, 1): 33 of the 34 depths are the coarse depths themselves, and under this peaky net most of their bins hold little mass (share 0.31)
+    assert_depths(zf, O.fine_depths(z_coarse, w_own, ni, u=ut)[0], z_coarse, w_own, min_well=0.5 if ni > 1 else 0.25)
     raw = O._run_model(O.to_torch(st_f), rays, zf, O.posenc(rays[:, 3:6], 4), 32768)
     w2, f2, _ = O.composite(raw, zf)
     close(out["weights_fine"], w2, atol=3e-6), close(out["feature_fine"], f2, atol=1e-5)
