@@ -41,6 +41,7 @@ EXPORTS = [
     "crnerf_peer_window_bytes", "crnerf_peer_window_create", "crnerf_peer_window_open", "crnerf_peer_window_close", "crnerf_peer_window_destroy",
     "crnerf_peer_window_status", "crnerf_peer_allreduce_f32",
     "crnerf_cus_per_xcd", "crnerf_stream_create_cu_share", "crnerf_stream_destroy",
+    "crnerf_image_metrics_workspace_bytes", "crnerf_image_metrics_f32",
 ]
 
 _c_fp = ctypes.c_void_p  # device float*
@@ -97,6 +98,20 @@ class BatchArgs(ctypes.Structure):
         ("scale", ctypes.c_float), ("h_offset", ctypes.c_float), ("w_offset", ctypes.c_float),
         ("rays", _c_fp), ("ts", ctypes.c_void_p), ("rgbs", _c_fp), ("rgb_idx", ctypes.c_void_p), ("uv_sample", _c_fp),
     ]
+
+
+class ImageMetricsArgs(ctypes.Structure):
+    """struct crnerf_image_metrics_args."""
+    _fields_ = [
+        ("pred", _c_fp), ("pred_stride_c", ctypes.c_int64), ("pred_stride_y", ctypes.c_int64), ("pred_stride_x", ctypes.c_int64),
+        ("gt", _c_fp), ("gt_stride_c", ctypes.c_int64), ("gt_stride_y", ctypes.c_int64), ("gt_stride_x", ctypes.c_int64),
+        ("channels", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+        ("quantize_pred", ctypes.c_int32),
+    ]
+
+
+METRICS_TILE_H, METRICS_TILE_W = 16, 64     # CRNERF_METRICS_TILE_H / _W (include/crnerf.h)
 
 
 class ConvGeom(ctypes.Structure):
@@ -240,6 +255,8 @@ def load():
             "crnerf_cus_per_xcd": (ctypes.c_int, []),
             "crnerf_stream_create_cu_share": (ctypes.c_int, [pp, i32, i32]),
             "crnerf_stream_destroy": (ctypes.c_int, [vp]),
+            "crnerf_image_metrics_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32]),
+            "crnerf_image_metrics_f32": (ctypes.c_int, [ctypes.POINTER(ImageMetricsArgs), vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h

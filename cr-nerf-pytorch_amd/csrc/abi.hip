@@ -780,6 +780,29 @@ int crnerf_adam_step_f32(float* params, float* exp_avg, float* exp_avg_sq, const
   return launch_adam_step(params, exp_avg, exp_avg_sq, blocks, n_blocks, grads, n_tensors, h, (hipStream_t)stream);
 }
 
+static_assert(METRICS_TILE_H == CRNERF_METRICS_TILE_H && METRICS_TILE_W == CRNERF_METRICS_TILE_W, "metrics tile: kernels.h vs crnerf.h");
+
+size_t crnerf_image_metrics_workspace_bytes(int32_t channels, int32_t w, int32_t h) {
+  if (channels <= 0 || w <= 0 || h <= 0) return 0;
+  return image_metrics_workspace_bytes(channels, w, h);
+}
+
+int crnerf_image_metrics_f32(const crnerf_image_metrics_args* a, double* out2, float* ssim_map, void* workspace, void* stream) {
+  REQUIRE(a, "args"); REQUIRE(out2, "out2"); REQUIRE(workspace, "workspace");
+  REQUIRE(a->pred, "pred"); REQUIRE(a->gt, "gt");
+  if (a->channels <= 0 || a->width <= 0 || a->height <= 0) return set_error(CRNERF_ERR_SHAPE, "image_metrics: channels, width and height must be positive");
+  if (a->w <= 0 || a->h <= 0) return set_error(CRNERF_ERR_SHAPE, "image_metrics: empty region of interest");
+  if (a->w < 2 || a->h < 2) return set_error(-1, "image_metrics: the region of interest must be at least 2x2 (reflect border of the 3x3 window)");
+  if (a->x0 < 0 || a->y0 < 0 || a->x0 > a->width - a->w || a->y0 > a->height - a->h)
+    return set_error(CRNERF_ERR_SHAPE, "image_metrics: the region of interest leaves the image");
+  const long tiles = (long)((a->w + METRICS_TILE_W - 1) / METRICS_TILE_W) * ((a->h + METRICS_TILE_H - 1) / METRICS_TILE_H) * a->channels;
+  if (tiles > 0x7fffffffL) return set_error(CRNERF_ERR_SHAPE, "image_metrics: more tiles than one launch holds");
+  const MetricsArgs k{a->pred, (long)a->pred_stride_c, (long)a->pred_stride_y, (long)a->pred_stride_x,
+                      a->gt, (long)a->gt_stride_c, (long)a->gt_stride_y, (long)a->gt_stride_x,
+                      a->channels, a->x0, a->y0, a->w, a->h, a->quantize_pred ? 1 : 0};
+  return launch_image_metrics(k, out2, ssim_map, workspace, (hipStream_t)stream);
+}
+
 static int to_geom(const crnerf_conv_geom* a, ConvGeom& g) {
   if (a->cin <= 0 || a->cout <= 0 || a->H <= 0 || a->W <= 0 || a->k <= 0 || a->stride <= 0 || a->dil <= 0 || a->pad < 0)
     return set_error(CRNERF_ERR_SHAPE, "conv2d: non-positive geometry");

@@ -239,4 +239,15 @@ struct AdamHyper { float step_size, beta1, beta2, eps, weight_decay, bias_correc
 int launch_adam_step(float* p, float* m, float* v, const int* blocks, int n_blocks, const float* const* grads, int n_tensors,
                      const AdamHyper& h, hipStream_t stream);
 
+// ---- evaluation metrics (metrics.hip): sse and SSIM of a region of interest, images read in place through element strides
+constexpr int METRICS_TILE_H = 16, METRICS_TILE_W = 64;   // pixels of one workgroup's tile (CRNERF_METRICS_TILE_H / _W)
+struct MetricsArgs {
+  const float* pred; long p_sc, p_sy, p_sx;         // element strides (channel, row, column)
+  const float* gt;   long g_sc, g_sy, g_sx;
+  int channels, x0, y0, w, h;                       // ROI (x0, y0, w, h) inside both images, w >= 2, h >= 2
+  int quantize_pred;
+};
+size_t image_metrics_workspace_bytes(int channels, int w, int h);
+int launch_image_metrics(const MetricsArgs& a, double* out2, float* ssim_map, void* workspace, hipStream_t stream);
+
 }  // namespace crnerf

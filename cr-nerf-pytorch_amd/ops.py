@@ -1004,6 +1004,59 @@ def loss_backward(args, upstream, want, strides=None):
     return out
 
 
+METRICS_TILE = (_lib.METRICS_TILE_H, _lib.METRICS_TILE_W)    # rows, columns of one workgroup's tile of the ROI (csrc/metrics.hip)
+_metrics_ws = {}
+
+
+def _chw_view(t, name):
+    """(C,H,W) view of an image given as (1,C,H,W) or (C,H,W); any strides (the kernel reads the image in place)."""
+    if not torch.is_tensor(t):
+        raise TypeError("crnerf_amd: %s must be a tensor" % name)
+    if not t.is_cuda:
+        raise RuntimeError("crnerf_amd: %s is on %s; the HIP path needs GPU tensors and has no CPU fallback" % (name, t.device))
+    if t.device.index != _lib._current_device():
+        raise _lib._bad_tensor(t, name, torch.float32)
+    if t.dtype != torch.float32:
+        raise TypeError("crnerf_amd: %s must be float32, got %s" % (name, t.dtype))
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 3:
+        raise ValueError("crnerf_amd: %s must be (1,C,H,W) or (C,H,W), got %s" % (name, tuple(t.shape)))
+    return t.detach()
+
+
+def image_metrics(pred, gt, roi=None, quantize_pred=False, want_map=False):
+    """crnerf_image_metrics_f32 on the region of interest roi = (x0, y0, w, h) (None: the whole image) of an image pair given as
+    (1,C,H,W) or (C,H,W) views of ANY strides -- the reference's NCHW, decode_image's [H*W,3] seen as CHW, a slice of a wider image --
+    read in place.  Returns (sse, ssim_sum, n, map): two 0-dim float64 device tensors (sum of squared differences, sum of the SSIM
+    map), n = C*h*w, and the [C,h,w] map (None unless want_map).  quantize_pred: the prediction goes through the uint8 round trip
+    of the reference's PNG files on load."""
+    lib = _lib.load()
+    p, g = _chw_view(pred, "image_pred"), _chw_view(gt, "image_gt")
+    if p.shape != g.shape:
+        raise ValueError("crnerf_amd: image_pred %s and image_gt %s differ in shape" % (tuple(p.shape), tuple(g.shape)))
+    C, H, W = (int(v) for v in p.shape)
+    x0, y0, w, h = (0, 0, W, H) if roi is None else (int(v) for v in roi)
+    if w < 2 or h < 2 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError("crnerf_amd: roi (x0=%d, y0=%d, w=%d, h=%d) must be at least 2x2 and lie inside the %dx%d image" % (x0, y0, w, h, W, H))
+    a = _lib.ImageMetricsArgs()
+    a.pred, a.pred_stride_c, a.pred_stride_y, a.pred_stride_x = p.data_ptr(), p.stride(0), p.stride(1), p.stride(2)
+    a.gt, a.gt_stride_c, a.gt_stride_y, a.gt_stride_x = g.data_ptr(), g.stride(0), g.stride(1), g.stride(2)
+    a.channels, a.width, a.height = C, W, H
+    a.x0, a.y0, a.w, a.h = x0, y0, w, h
+    a.quantize_pred = int(bool(quantize_pred))
+    dev = p.device
+    need = lib.crnerf_image_metrics_workspace_bytes(C, w, h)
+    ws = _metrics_ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _metrics_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)     # stream-ordered reuse, like the loss workspace
+    out2 = torch.empty(2, dtype=torch.float64, device=dev)
+    ssim_map = torch.empty((C, h, w), dtype=torch.float32, device=dev) if want_map else None
+    _lib.check(lib.crnerf_image_metrics_f32(ctypes.byref(a), ctypes.c_void_p(out2.data_ptr()), _lib.dev_ptr(ssim_map, "ssim_map"),
+                                            ctypes.c_void_p(ws.data_ptr()), _lib.stream_ptr()), "crnerf_image_metrics_f32")
+    return out2[0], out2[1], C * h * w, ssim_map
+
+
 def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset):
     lib = _lib.load()
     all_rays, all_rgbs = _f32c(all_rays, "all_rays"), _f32c(all_rgbs, "all_rgbs")

@@ -6,6 +6,7 @@ reference's drivers can be re-created without Lightning / imageio / torchvision:
     batched_inference(...)        eval.py:29-59 / appearance_modification_video.py:71-102 (ray-chunk loop, dict concat)
     decode_image(...)             eval.py:288-295 (feature -> [1,64,H,W] view -> decoder -> [H*W,3])
     render_frame(...)             one video frame: rays generated on the device, style from the appearance encoder
+    evaluate_image(...)           eval.py:271-299 + eval_metric.py:87-93 for one test sample: render, decode, PSNR / SSIM (no PNG, no host copy)
     TrainingSystem                NeRFSystem.decode / forward / training_step, train_mask_grid_sample.py:127-226, :268-290
                                   (command/train.sh's configuration: encode_a, encode_random, encode_c, use_mask)
 """
@@ -13,6 +14,7 @@ from collections import defaultdict
 
 import torch
 
+from . import metrics
 from .datasets.ray_utils import generate_rays
 from .models.linearStyleTransfer import encoder_sameoutputsize, style_net
 from .models.nerf import NeRF_sigma, PosEmbedding
@@ -115,6 +117,30 @@ def render_frame(models, embeddings, enc_a, style_img, H, W, K, c2w, hparams_, n
     res = batched_inference(models, embeddings, rays, None, hparams_.N_samples, hparams_.N_importance, hparams_.use_disp,
                             chunk, False, args=hparams_, a_embedded_from_img=a_emb, precision=precision, lean=lean)
     return decode_image(models, res, H, W, a_emb).reshape(int(H), int(W), 3).clamp(0, 1)
+
+
+@torch.no_grad()
+def evaluate_image(models, embeddings, enc_a, sample, hparams_, chunk=32768, precision=None, lean=False, half='right', quantize_pred=True):
+    """One sample of PhototourismDataset(split='test_test') scored the reference's way without its PNG files: the body of eval.py:271-299
+    (appearance from `whole_img`, ray-chunk loop, decode) followed by eval_metric.py:87-93 (PSNR / SSIM / MSE against `rgbs`, on the right
+    half of the image -- the left half is what the appearance encoder saw).  The image stays on the device: the prediction's uint8 round
+    trip through the PNG (eval.py:296-297) is applied by the metrics kernel on load (quantize_pred=True, what makes the numbers comparable
+    with the reference's result.txt; False scores the raw decode).  half=None scores the whole image (eval_metric.py:95-98, blender).
+    sample: 'rays' [H*W,8], 'ts' [H*W], 'rgbs' [H*W,3], 'whole_img' [3,h,w] in [-1,1], 'img_wh' (w, h).
+    Returns {'rgb': [H*W,3] (the raw decode), 'psnr', 'ssim', 'mse'} -- 0-dim device tensors."""
+    device = next(models["coarse"].parameters()).device
+    W, H = (int(v) for v in torch.as_tensor(sample['img_wh']).reshape(-1)[:2])              # eval.py:287
+    whole_img = (sample['whole_img'].to(device).unsqueeze(0) + 1) / 2                       # :276-277
+    a_emb = enc_a(whole_img)                                                                # :278
+    ts = sample.get('ts')
+    res = batched_inference(models, embeddings, sample['rays'].to(device), ts.to(device) if ts is not None else None, hparams_.N_samples,
+                            hparams_.N_importance, hparams_.use_disp, chunk, False, args=hparams_, a_embedded_from_img=a_emb,
+                            precision=precision, lean=lean)
+    rgb = decode_image(models, res, H, W, a_emb)                                            # :288-295
+    as_chw = lambda t: t.view(H, W, 3).permute(2, 0, 1)[None]  # noqa: E731  eval_metric.py:88-91 -- a view, the kernel reads it in place
+    out = metrics.image_metrics(as_chw(rgb), as_chw(sample['rgbs'].to(device=device, dtype=torch.float32)), half=half, quantize_pred=quantize_pred)
+    out['rgb'] = rgb
+    return out
 
 
 class _Branches:
@@ -373,11 +399,13 @@ class TrainingSystem:
         return loss, loss_d, results
 
     @torch.no_grad()
-    def validation_step(self, batch, batch_nb=0):                                           # :339-402
+    def validation_step(self, batch, batch_nb=0, ssim=False):                               # :339-402
         """One whole validation image (PhototourismDataset split='val' hands over every ray of the image, `img_wh` = its size):
         forward in val_mode, the training loss terms, PSNR of the finest decode (metrics.py:12-13).  Returns the reference's log
         dict -- 'val_loss', the loss terms, 'val_psnr' -- plus 'results' for callers that want the images (the reference sends
-        img_gt / prediction / random-appearance prediction / mask to wandb here, :371-391; its 'val_ssim' is kornia's, out of scope)."""
+        img_gt / prediction / random-appearance prediction / mask to wandb here, :371-391).  ssim=True adds the reference's
+        'val_ssim' right after 'val_psnr': the (1,3,H,W) SSIM map of the finest decode against the image (:397-400, metrics.ssim --
+        kornia's ssim(.., 3) restated in csrc/metrics.hip, computed on the device); off by default, the dict is then as before."""
         rays, ts, rgbs = batch['rays'].squeeze(), batch['ts'].squeeze(), batch['rgbs'].squeeze()
         W, H = (int(v) for v in torch.as_tensor(batch['img_wh']).reshape(-1)[:2])          # :346-347
         was_training = self.training
@@ -391,9 +419,12 @@ class TrainingSystem:
         log.update(loss_d)
         typ = 'fine' if 'rgb_fine' in results else 'coarse'
         log['val_psnr'] = -10.0 * torch.log10(((results['rgb_%s' % typ] - rgbs) ** 2).mean())
+        if ssim:
+            as_img = lambda t: t.view(H, W, 3).permute(2, 0, 1)[None]  # noqa: E731  (:370-372), a view
+            log['val_ssim'] = metrics.ssim(as_img(results['rgb_%s' % typ]), as_img(rgbs))
         log['results'] = results
         return log
 
 
-__all__ = ["get_model", "get_embeddings", "load_ckpt", "extract_model_state_dict", "batched_inference", "decode_image", "render_frame",
+__all__ = ["get_model", "get_embeddings", "load_ckpt", "extract_model_state_dict", "batched_inference", "decode_image", "render_frame", "evaluate_image",
            "encoder_sameoutputsize", "TrainingSystem"]

@@ -542,6 +542,35 @@ int crnerf_adam_step_f32(float* params, float* exp_avg, float* exp_avg_sq, const
                          const float* const* grads, int32_t n_tensors, float step_size, float beta1, float beta2, float eps,
                          float weight_decay, float bias_correction2_sqrt, void* stream);
 
+/* -------- evaluation metrics: metrics.py:4-20 (mse / psnr / ssim) on a region of interest of an image pair, e.g. the
+ * right half that eval_metric.py:87-93 scores.  pred / gt: C-channel images of width x height pixels addressed by ELEMENT strides
+ * (channel, row, column), so the reference's (1,3,H,W) and a pixel-major [H*W,3] are both read in place; the ROI (x0, y0, w, h)
+ * lies inside them, w >= 2 and h >= 2 (torch's reflect padding rejects less).  One pass reads both images once and gives
+ * out2[0] = sum over channels and ROI pixels of (pred - gt)^2, out2[1] = sum of the SSIM map (two doubles on the device; mse =
+ * out2[0] / (C w h), psnr = -10 log10(mse), mean ssim = out2[1] / (C w h)), and -- ssim_map not NULL -- the map itself, [C,h,w] fp32.
+ * Both sums are accumulated in double in a fixed order: the same call gives the same bits.
+ * SSIM is kornia.metrics.ssim(img1, img2, window_size=3) with its defaults, restated: g = exp(-x^2 / (2 1.5^2)), x = -1, 0, 1,
+ * normalised ([0.30780134, 0.38439736, 0.30780134]); 2-D window g g^T applied per channel as a correlation; border reflected
+ * without repeating the edge (-1 -> 1, n -> n-2) RELATIVE TO THE ROI (the reference crops, then filters); mu1 = g*a, mu2 = g*b,
+ * s11 = g*(a^2) - mu1^2, s22 = g*(b^2) - mu2^2, s12 = g*(ab) - mu1 mu2; C1 = 0.01^2, C2 = 0.03^2, eps = 1e-12;
+ * map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2) + eps).  The second moments are evaluated in fp32 in
+ * their centred form, sum w (a - mu1)^2 ..., the same numbers without the cancellation of E[x^2] - mu^2.
+ * quantize_pred != 0: the prediction is replaced on load by truncf(min(max(p, 0), 1) * 255) / 255, the PNG round trip of
+ * eval.py:296-297 / eval_metric.py:75-76 (uint8 and back; a true division, bit-identical to torch's uint8 -> / 255 on the host).
+ * workspace: crnerf_image_metrics_workspace_bytes(channels, w, h) bytes (of the ROI).  Returns -1 for a NULL pointer and for a
+ * region with w < 2 or h < 2, CRNERF_ERR_SHAPE for an empty region or one that leaves the image. */
+typedef struct crnerf_image_metrics_args {
+  const float* pred; int64_t pred_stride_c, pred_stride_y, pred_stride_x;
+  const float* gt;   int64_t gt_stride_c, gt_stride_y, gt_stride_x;
+  int32_t channels, width, height;
+  int32_t x0, y0, w, h;
+  int32_t quantize_pred;
+} crnerf_image_metrics_args;
+#define CRNERF_METRICS_TILE_H 16    /* one workgroup's tile of the ROI: sizes around its multiples are the ones worth testing */
+#define CRNERF_METRICS_TILE_W 64
+size_t crnerf_image_metrics_workspace_bytes(int32_t channels, int32_t w, int32_t h);
+int crnerf_image_metrics_f32(const crnerf_image_metrics_args* args, double* out2, float* ssim_map, void* workspace, void* stream);
+
 /* Operators of the transient-mask network: Context_Guided_Network(classes=1, M=2, N=2, input_channel=3),
  * models/lightweight_seg.py:274-368, applied once per step to the 1/8-scale photo (train_mask_grid_sample.py:170-176).
  * All tensors NCHW fp32, batch 1, contiguous; every backward OVERWRITES its gradient outputs. */
