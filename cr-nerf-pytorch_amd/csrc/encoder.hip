@@ -141,6 +141,8 @@ __global__ __launch_bounds__(256) void conv_kernel(const float* __restrict__ in,
 // its four waves split K (fixed ranges; partial tiles are added in wave order through LDS: deterministic).  v_mfma_f32_32x32x2_f32:
 // lane (i, kk) loads 16 bytes of row i of A and of row i of B at k = 8s + 4kk .. + 3 and issues four MFMAs (k pairs {8s + t,
 // 8s + 4 + t}; the order of k inside a dot product is free as long as both operands agree).  K % 8 == 0, lda / ldb % 4 == 0.
+// (The encoder calls this with K in {64, 128, 576, 1152} only: chunks = K / 8 is a multiple of 4 every time, so the `r = chunks & 3` remainder
+// of the wave split below is never taken and no test of the suite reaches it -- tests/test_gpu_encoder_exact.py pins the rest bit for bit.)
 template <bool ACT>
 __global__ __launch_bounds__(256) void enc_gemm_nt_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                           const float* __restrict__ bias, float* __restrict__ C, int ldc, int M, int N, int K) {
