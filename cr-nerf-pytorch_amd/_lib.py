@@ -42,6 +42,7 @@ EXPORTS = [
     "crnerf_peer_window_status", "crnerf_peer_allreduce_f32",
     "crnerf_cus_per_xcd", "crnerf_stream_create_cu_share", "crnerf_stream_destroy",
     "crnerf_image_metrics_workspace_bytes", "crnerf_image_metrics_f32",
+    "crnerf_lpips_workspace_bytes", "crnerf_lpips_f32",
 ]
 
 _c_fp = ctypes.c_void_p  # device float*
@@ -108,6 +109,18 @@ class ImageMetricsArgs(ctypes.Structure):
         ("channels", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
         ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
         ("quantize_pred", ctypes.c_int32),
+    ]
+
+
+class LpipsArgs(ctypes.Structure):
+    """struct crnerf_lpips_args."""
+    _fields_ = [
+        ("pred", _c_fp), ("pred_stride_c", ctypes.c_int64), ("pred_stride_y", ctypes.c_int64), ("pred_stride_x", ctypes.c_int64),
+        ("gt", _c_fp), ("gt_stride_c", ctypes.c_int64), ("gt_stride_y", ctypes.c_int64), ("gt_stride_x", ctypes.c_int64),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+        ("quantize_pred", ctypes.c_int32), ("normalize", ctypes.c_int32),
+        ("conv_w", _c_fp * 5), ("conv_b", _c_fp * 5), ("lin", _c_fp * 5), ("shift", _c_fp), ("scale", _c_fp),
     ]
 
 
@@ -257,6 +270,8 @@ def load():
             "crnerf_stream_destroy": (ctypes.c_int, [vp]),
             "crnerf_image_metrics_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32]),
             "crnerf_image_metrics_f32": (ctypes.c_int, [ctypes.POINTER(ImageMetricsArgs), vp, vp, vp, vp]),
+            "crnerf_lpips_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
+            "crnerf_lpips_f32": (ctypes.c_int, [ctypes.POINTER(LpipsArgs), vp, pp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h

@@ -803,6 +803,32 @@ int crnerf_image_metrics_f32(const crnerf_image_metrics_args* a, double* out2, f
   return launch_image_metrics(k, out2, ssim_map, workspace, (hipStream_t)stream);
 }
 
+size_t crnerf_lpips_workspace_bytes(int32_t w, int32_t h) {
+  if (w < 31 || h < 31 || !lpips_fits_one_launch(w, h)) return 0;
+  return lpips_workspace_bytes(w, h);
+}
+
+int crnerf_lpips_f32(const crnerf_lpips_args* a, double* out6, float* const* features, void* workspace, void* stream) {
+  REQUIRE(a, "args"); REQUIRE(out6, "out6"); REQUIRE(workspace, "workspace");
+  REQUIRE(a->pred, "pred"); REQUIRE(a->gt, "gt"); REQUIRE(a->shift, "shift"); REQUIRE(a->scale, "scale");
+  for (int l = 0; l < 5; ++l) { REQUIRE(a->conv_w[l], "conv_w[l]"); REQUIRE(a->conv_b[l], "conv_b[l]"); REQUIRE(a->lin[l], "lin[l]"); }
+  if (features)
+    for (int l = 0; l < 10; ++l) REQUIRE(features[l], "features[l]");
+  if (a->width <= 0 || a->height <= 0) return set_error(CRNERF_ERR_SHAPE, "lpips: width and height must be positive");
+  if (a->w <= 0 || a->h <= 0) return set_error(CRNERF_ERR_SHAPE, "lpips: empty region of interest");
+  if (a->x0 < 0 || a->y0 < 0 || a->x0 > a->width - a->w || a->y0 > a->height - a->h)
+    return set_error(CRNERF_ERR_SHAPE, "lpips: the region of interest leaves the image");
+  if (a->w < 31 || a->h < 31) return set_error(CRNERF_ERR_SHAPE, "lpips: the region of interest must be at least 31x31 (31 -> 7 -> 3 -> 1 through conv1 and the two pools)");
+  if (!lpips_fits_one_launch(a->w, a->h)) return set_error(CRNERF_ERR_SHAPE, "lpips: more patch-matrix blocks than one launch holds");
+  for (int l = 0; l < 5; ++l)
+    if ((uintptr_t)a->conv_w[l] & 15) return set_error(CRNERF_ERR_SHAPE, "lpips: conv_w[l] must be 16-byte aligned");
+  LpipsArgs k{a->pred, (long)a->pred_stride_c, (long)a->pred_stride_y, (long)a->pred_stride_x,
+              a->gt, (long)a->gt_stride_c, (long)a->gt_stride_y, (long)a->gt_stride_x,
+              a->x0, a->y0, a->w, a->h, a->quantize_pred ? 1 : 0, a->normalize ? 1 : 0, {}, {}, {}, a->shift, a->scale};
+  for (int l = 0; l < 5; ++l) { k.conv_w[l] = a->conv_w[l]; k.conv_b[l] = a->conv_b[l]; k.lin[l] = a->lin[l]; }
+  return launch_lpips(k, out6, features, workspace, (hipStream_t)stream);
+}
+
 static int to_geom(const crnerf_conv_geom* a, ConvGeom& g) {
   if (a->cin <= 0 || a->cout <= 0 || a->H <= 0 || a->W <= 0 || a->k <= 0 || a->stride <= 0 || a->dil <= 0 || a->pad < 0)
     return set_error(CRNERF_ERR_SHAPE, "conv2d: non-positive geometry");

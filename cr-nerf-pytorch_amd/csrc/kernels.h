@@ -250,4 +250,18 @@ struct MetricsArgs {
 size_t image_metrics_workspace_bytes(int channels, int w, int h);
 int launch_image_metrics(const MetricsArgs& a, double* out2, float* ssim_map, void* workspace, hipStream_t stream);
 
+// ---- LPIPS, AlexNet backbone (lpips.hip): both images of the pair read in place, as above; ROI at least 31 x 31
+struct LpipsArgs {
+  const float* pred; long p_sc, p_sy, p_sx;
+  const float* gt;   long g_sc, g_sy, g_sx;
+  int x0, y0, w, h;
+  int quantize_pred, normalize;
+  const float* conv_w[5]; const float* conv_b[5]; const float* lin[5];
+  const float* shift; const float* scale;
+};
+size_t lpips_workspace_bytes(int w, int h);
+bool lpips_fits_one_launch(int w, int h);
+// features: null, or a HOST array of 10 device pointers (F1..F5 of pred, then of gt, each [C,h,w])
+int launch_lpips(const LpipsArgs& a, double* out6, float* const* features, void* workspace, hipStream_t stream);
+
 }  // namespace crnerf

@@ -1057,6 +1057,62 @@ def image_metrics(pred, gt, roi=None, quantize_pred=False, want_map=False):
     return out2[0], out2[1], C * h * w, ssim_map
 
 
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)      # channels of the five AlexNet taps (csrc/lpips.hip)
+_lpips_ws = {}
+
+
+def lpips_map_sizes(h, w):
+    """[(h_l, w_l)] of F1..F5 for an h x w region: conv1 gives (n - 7) // 4 + 1, each 3/2 pool (m - 3) // 2 + 1 (31 -> 7 -> 3 -> 1)."""
+    s1 = ((h - 7) // 4 + 1, (w - 7) // 4 + 1)
+    s2 = tuple((m - 3) // 2 + 1 for m in s1)
+    s3 = tuple((m - 3) // 2 + 1 for m in s2)
+    return [s1, s2, s3, s3, s3]
+
+
+def lpips(pred, gt, weights, roi=None, quantize_pred=False, normalize=True, want_features=False):
+    """crnerf_lpips_f32 (LPIPS, AlexNet backbone; include/crnerf.h restates the definition) on the region of interest roi = (x0, y0, w, h)
+    (None: the whole image; at least 31 x 31) of an image pair given as (1,3,H,W) or (3,H,W) float32 GPU views of ANY strides, read in
+    place like image_metrics.  weights: a metrics.LPIPSWeights (the 17 float32 device tensors).  quantize_pred: the prediction goes
+    through the uint8 round trip of the reference's PNG on load; normalize: both images are in [0,1] and go through * 2 - 1 first.
+    Returns (total, per_layer, features): a 0-dim and a [5] float64 device tensor (per_layer = d_1..d_5, total their sum) and, with
+    want_features, [[F1..F5 of pred], [F1..F5 of gt]] as [C,h,w] float32 tensors (None otherwise)."""
+    lib = _lib.load()
+    p, g = _chw_view(pred, "image_pred"), _chw_view(gt, "image_gt")
+    if p.shape != g.shape:
+        raise ValueError("crnerf_amd: image_pred %s and image_gt %s differ in shape" % (tuple(p.shape), tuple(g.shape)))
+    C, H, W = (int(v) for v in p.shape)
+    if C != 3:
+        raise ValueError("crnerf_amd: lpips takes 3-channel images, got %d channels" % C)
+    x0, y0, w, h = (0, 0, W, H) if roi is None else (int(v) for v in roi)
+    if w < 31 or h < 31 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError("crnerf_amd: roi (x0=%d, y0=%d, w=%d, h=%d) must be at least 31x31 and lie inside the %dx%d image" % (x0, y0, w, h, W, H))
+    a = _lib.LpipsArgs()
+    a.pred, a.pred_stride_c, a.pred_stride_y, a.pred_stride_x = p.data_ptr(), p.stride(0), p.stride(1), p.stride(2)
+    a.gt, a.gt_stride_c, a.gt_stride_y, a.gt_stride_x = g.data_ptr(), g.stride(0), g.stride(1), g.stride(2)
+    a.width, a.height = W, H
+    a.x0, a.y0, a.w, a.h = x0, y0, w, h
+    a.quantize_pred, a.normalize = int(bool(quantize_pred)), int(bool(normalize))
+    for l in range(5):
+        a.conv_w[l] = _lib.dev_ptr(weights.conv_w[l], "conv_w[%d]" % l)
+        a.conv_b[l] = _lib.dev_ptr(weights.conv_b[l], "conv_b[%d]" % l)
+        a.lin[l] = _lib.dev_ptr(weights.lin[l], "lin[%d]" % l)
+    a.shift, a.scale = _lib.dev_ptr(weights.shift, "shift"), _lib.dev_ptr(weights.scale, "scale")
+    dev = p.device
+    need = lib.crnerf_lpips_workspace_bytes(w, h)
+    ws = _lpips_ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _lpips_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)     # stream-ordered reuse, like the metrics workspace
+    out6 = torch.empty(6, dtype=torch.float64, device=dev)
+    features, fptr = None, None
+    if want_features:
+        sizes = lpips_map_sizes(h, w)
+        features = [[torch.empty((LPIPS_CHANNELS[l],) + sizes[l], dtype=torch.float32, device=dev) for l in range(5)] for _ in range(2)]
+        fptr = _lib.ptr_array(features[0] + features[1], "features")
+    _lib.check(lib.crnerf_lpips_f32(ctypes.byref(a), ctypes.c_void_p(out6.data_ptr()), fptr, ctypes.c_void_p(ws.data_ptr()), _lib.stream_ptr()),
+               "crnerf_lpips_f32")
+    return out6[5], out6[:5], features
+
+
 def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset):
     lib = _lib.load()
     all_rays, all_rgbs = _f32c(all_rays, "all_rays"), _f32c(all_rgbs, "all_rgbs")

@@ -7,6 +7,7 @@ reference's drivers can be re-created without Lightning / imageio / torchvision:
     decode_image(...)             eval.py:288-295 (feature -> [1,64,H,W] view -> decoder -> [H*W,3])
     render_frame(...)             one video frame: rays generated on the device, style from the appearance encoder
     evaluate_image(...)           eval.py:271-299 + eval_metric.py:87-93 for one test sample: render, decode, PSNR / SSIM (no PNG, no host copy)
+    evaluate_lpips(...)           eval_metric.py:92 on evaluate_image's output: the LPIPS column, given the network's weights
     TrainingSystem                NeRFSystem.decode / forward / training_step, train_mask_grid_sample.py:127-226, :268-290
                                   (command/train.sh's configuration: encode_a, encode_random, encode_c, use_mask)
 """
@@ -141,6 +142,17 @@ def evaluate_image(models, embeddings, enc_a, sample, hparams_, chunk=32768, pre
     out = metrics.image_metrics(as_chw(rgb), as_chw(sample['rgbs'].to(device=device, dtype=torch.float32)), half=half, quantize_pred=quantize_pred)
     out['rgb'] = rgb
     return out
+
+
+def evaluate_lpips(weights, rgb, sample, half='right', quantize_pred=True):
+    """The LPIPS column of the reference's result.txt (eval_metric.py:92, lpips.LPIPS(net='alex')) for one test sample, from
+    evaluate_image's 'rgb' ([H*W,3], the raw decode) and the sample's 'rgbs' / 'img_wh': both images are read in place as CHW views,
+    the prediction through the PNG's uint8 round trip (quantize_pred=True), both through * 2 - 1, cropped to the right half before
+    the network sees them.  weights: metrics.load_lpips_weights(...).  Returns a 0-dim float32 device tensor."""
+    W, H = (int(v) for v in torch.as_tensor(sample['img_wh']).reshape(-1)[:2])
+    as_chw = lambda t: t.view(H, W, 3).permute(2, 0, 1)[None]  # noqa: E731
+    return metrics.lpips(as_chw(rgb), as_chw(sample['rgbs'].to(device=rgb.device, dtype=torch.float32)), weights, half=half,
+                         quantize_pred=quantize_pred, normalize=True)
 
 
 class _Branches:
@@ -426,5 +438,5 @@ class TrainingSystem:
         return log
 
 
-__all__ = ["get_model", "get_embeddings", "load_ckpt", "extract_model_state_dict", "batched_inference", "decode_image", "render_frame", "evaluate_image",
+__all__ = ["get_model", "get_embeddings", "load_ckpt", "extract_model_state_dict", "batched_inference", "decode_image", "render_frame", "evaluate_image", "evaluate_lpips",
            "encoder_sameoutputsize", "TrainingSystem"]

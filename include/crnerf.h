@@ -571,6 +571,41 @@ typedef struct crnerf_image_metrics_args {
 size_t crnerf_image_metrics_workspace_bytes(int32_t channels, int32_t w, int32_t h);
 int crnerf_image_metrics_f32(const crnerf_image_metrics_args* args, double* out2, float* ssim_map, void* workspace, void* stream);
 
+/* -------- LPIPS, AlexNet backbone, version 0.1 (eval_metric.py:92, lpips.LPIPS(net='alex')) of a region of interest of an image pair:
+ * the third number of the reference's result.txt.  No weights are shipped and none are fetched: the caller hands in the 17 tensors
+ * (crnerf_amd.metrics.load_lpips_weights reads them from the lpips package's / torchvision's files).  Restated from the definition
+ * (neither package is needed):
+ *   inputs   x0 = pred, x1 = gt: 3-channel images addressed by ELEMENT strides like crnerf_image_metrics_args, ROI (x0, y0, w, h)
+ *            inside them, w >= 31 and h >= 31.  quantize_pred != 0: pred goes through the uint8 round trip of the reference's PNG on
+ *            load (crnerf_image_metrics_f32's expression, bit-identical).  normalize != 0: x <- x * 2 - 1 ([0,1] -> [-1,1]).
+ *   scaling  s = (x - shift[c]) / scale[c], a true division (the package's constants: shift (-.030, -.088, -.188), scale (.458, .448, .450))
+ *   features torchvision AlexNet features[0..11], tapped after each ReLU, zero padding, pooling in floor mode without padding:
+ *            F1 = relu(conv(s; 3->64, k 11, stride 4, pad 2)), F2 = relu(conv(maxpool(F1; 3, 2); 64->192, k 5, pad 2)),
+ *            F3 = relu(conv(maxpool(F2; 3, 2); 192->384, k 3, pad 1)), F4 = relu(conv(F3; 384->256, k 3, pad 1)),
+ *            F5 = relu(conv(F4; 256->256, k 3, pad 1)); conv1 output side (n - 7) / 4 + 1, a pool gives (m - 3) / 2 + 1 (31 -> 7 -> 3 -> 1).
+ *            The zero padding of conv1 sits at the ROI's border (the reference crops, then scores); nothing outside the ROI is read.
+ *   distance n(F) = F / (sqrt(sum_c F^2) + 1e-10) per pixel; d_l = mean over pixels of sum_c lin_l[c] (n(F_l(x0)) - n(F_l(x1)))^2
+ *   result   out6 = {d_1, ..., d_5, d_1 + ... + d_5} (six doubles on the device).
+ * conv_w[l]: the module's own [cout][cin][k][k] tensor (16-byte aligned), conv_b[l]: [cout], lin[l]: [C_l], shift / scale: [3]; all fp32, device.
+ * Every convolution is a GEMM on the fp32 matrix cores with both images stacked along m; the order of k inside a dot product
+ * depends on K alone, the head sums in double in a fixed order without atomics: repeated calls give the same bits, swapping pred
+ * and gt (quantize_pred = 0) gives the same bits, and an image against itself gives exactly 0.
+ * features: NULL, or a HOST array of 10 device pointers that receive F1..F5 of pred, then F1..F5 of gt, each [C_l, h_l, w_l] fp32.
+ * workspace: crnerf_lpips_workspace_bytes(w, h) bytes for a w x h ROI (0 when the ROI is under 31 x 31): the patch matrix of the
+ * widest layer, the ten pixel-major maps, the two pooled maps, the head's partial sums.
+ * Returns -1 for a NULL pointer; CRNERF_ERR_SHAPE for an empty ROI, one that leaves the image or one under 31 x 31. */
+typedef struct crnerf_lpips_args {
+  const float* pred; int64_t pred_stride_c, pred_stride_y, pred_stride_x;
+  const float* gt;   int64_t gt_stride_c, gt_stride_y, gt_stride_x;
+  int32_t width, height;
+  int32_t x0, y0, w, h;
+  int32_t quantize_pred, normalize;
+  const float* conv_w[5]; const float* conv_b[5]; const float* lin[5];
+  const float* shift; const float* scale;
+} crnerf_lpips_args;
+size_t crnerf_lpips_workspace_bytes(int32_t w, int32_t h);
+int crnerf_lpips_f32(const crnerf_lpips_args* args, double* out6, float* const* features_or_null, void* workspace, void* stream);
+
 /* Operators of the transient-mask network: Context_Guided_Network(classes=1, M=2, N=2, input_channel=3),
  * models/lightweight_seg.py:274-368, applied once per step to the 1/8-scale photo (train_mask_grid_sample.py:170-176).
  * All tensors NCHW fp32, batch 1, contiguous; every backward OVERWRITES its gradient outputs. */
