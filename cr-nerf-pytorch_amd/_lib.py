@@ -43,6 +43,7 @@ EXPORTS = [
     "crnerf_cus_per_xcd", "crnerf_stream_create_cu_share", "crnerf_stream_destroy",
     "crnerf_image_metrics_workspace_bytes", "crnerf_image_metrics_f32",
     "crnerf_lpips_workspace_bytes", "crnerf_lpips_f32",
+    "crnerf_lanczos_workspace_bytes", "crnerf_lanczos_resize_u8",
 ]
 
 _c_fp = ctypes.c_void_p  # device float*
@@ -125,6 +126,8 @@ class LpipsArgs(ctypes.Structure):
 
 
 METRICS_TILE_H, METRICS_TILE_W = 16, 64     # CRNERF_METRICS_TILE_H / _W (include/crnerf.h)
+LANCZOS_TILE_H, LANCZOS_TILE_W, LANCZOS_VBLOCK = 8, 32, 256     # CRNERF_LANCZOS_TILE_H / _W / _VBLOCK
+LANCZOS_OUT = {"u8": 0, "rows": 1, "chw": 2, "chw_signed": 3}   # CRNERF_LANCZOS_OUT_*
 
 
 class ConvGeom(ctypes.Structure):
@@ -272,6 +275,8 @@ def load():
             "crnerf_image_metrics_f32": (ctypes.c_int, [ctypes.POINTER(ImageMetricsArgs), vp, vp, vp, vp]),
             "crnerf_lpips_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
             "crnerf_lpips_f32": (ctypes.c_int, [ctypes.POINTER(LpipsArgs), vp, pp, vp, vp]),
+            "crnerf_lanczos_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32, i32]),
+            "crnerf_lanczos_resize_u8": (ctypes.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h

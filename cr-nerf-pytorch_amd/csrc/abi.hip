@@ -829,6 +829,36 @@ int crnerf_lpips_f32(const crnerf_lpips_args* a, double* out6, float* const* fea
   return launch_lpips(k, out6, features, workspace, (hipStream_t)stream);
 }
 
+static_assert(LANCZOS_TILE_H == CRNERF_LANCZOS_TILE_H && LANCZOS_TILE_W == CRNERF_LANCZOS_TILE_W && LANCZOS_VBLOCK == CRNERF_LANCZOS_VBLOCK,
+              "lanczos tiles: kernels.h vs crnerf.h");
+static_assert(LANCZOS_U8 == CRNERF_LANCZOS_OUT_U8 && LANCZOS_ROWS == CRNERF_LANCZOS_OUT_ROWS && LANCZOS_CHW == CRNERF_LANCZOS_OUT_CHW &&
+              LANCZOS_CHW_SIGNED == CRNERF_LANCZOS_OUT_CHW_SIGNED, "lanczos output modes: kernels.h vs crnerf.h");
+
+size_t crnerf_lanczos_workspace_bytes(int32_t H, int32_t W, int32_t w, int32_t h) {
+  if (H < 1 || W < 1 || w < 1 || h < 1) return 0;
+  return lanczos_workspace_bytes(H, W, w, h);
+}
+
+int crnerf_lanczos_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t w, int32_t h, const int32_t* kx, const int32_t* bounds_x, int32_t ksize_x,
+                             const int32_t* ky, const int32_t* bounds_y, int32_t ksize_y, int32_t out_mode, void* dst, void* workspace, void* stream) {
+  REQUIRE(src, "src"); REQUIRE(dst, "dst");
+  if (H < 1 || W < 1 || w < 1 || h < 1) return set_error(CRNERF_ERR_SHAPE, "lanczos_resize: H, W, w and h must be positive");
+  if (out_mode < CRNERF_LANCZOS_OUT_U8 || out_mode > CRNERF_LANCZOS_OUT_CHW_SIGNED) return set_error(CRNERF_ERR_CONFIG, "lanczos_resize: unknown output mode");
+  if (w != W) {
+    REQUIRE(kx, "kx"); REQUIRE(bounds_x, "bounds_x");
+    if (ksize_x != lanczos_ksize(W, w)) return set_error(CRNERF_ERR_CONFIG, "lanczos_resize: ksize_x is not the kernel size of W -> w");
+    if ((uintptr_t)kx & 15) return set_error(CRNERF_ERR_SHAPE, "lanczos_resize: kx must be 16-byte aligned");
+  }
+  if (h != H) {
+    REQUIRE(ky, "ky"); REQUIRE(bounds_y, "bounds_y");
+    if (ksize_y != lanczos_ksize(H, h)) return set_error(CRNERF_ERR_CONFIG, "lanczos_resize: ksize_y is not the kernel size of H -> h");
+  }
+  if (w != W && h != H) REQUIRE(workspace, "workspace");
+  if (!lanczos_fits(H, W, w, h))
+    return set_error(CRNERF_ERR_SHAPE, "lanczos_resize: image over 2^31 bytes or 65,535 output rows, or a horizontal downscale whose tile does not fit the LDS (above ~32x)");
+  return launch_lanczos_resize(src, H, W, w, h, kx, bounds_x, ksize_x, ky, bounds_y, ksize_y, out_mode, dst, workspace, (hipStream_t)stream);
+}
+
 static int to_geom(const crnerf_conv_geom* a, ConvGeom& g) {
   if (a->cin <= 0 || a->cout <= 0 || a->H <= 0 || a->W <= 0 || a->k <= 0 || a->stride <= 0 || a->dil <= 0 || a->pad < 0)
     return set_error(CRNERF_ERR_SHAPE, "conv2d: non-positive geometry");

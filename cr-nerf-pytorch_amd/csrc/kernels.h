@@ -264,4 +264,14 @@ bool lpips_fits_one_launch(int w, int h);
 // features: null, or a HOST array of 10 device pointers (F1..F5 of pred, then of gt, each [C,h,w])
 int launch_lpips(const LpipsArgs& a, double* out6, float* const* features, void* workspace, hipStream_t stream);
 
+// ---- image preparation (imageprep.hip): Pillow's 8-bit LANCZOS resize of a [H,W,3] uint8 photo + torchvision's conversions in the store
+constexpr int LANCZOS_TILE_H = 8, LANCZOS_TILE_W = 32;    // rows x output columns of one workgroup of the horizontal pass (CRNERF_LANCZOS_TILE_H / _W)
+constexpr int LANCZOS_VBLOCK = 256;                       // bytes of one output row one workgroup of the vertical pass writes (CRNERF_LANCZOS_VBLOCK)
+enum { LANCZOS_U8 = 0, LANCZOS_ROWS = 1, LANCZOS_CHW = 2, LANCZOS_CHW_SIGNED = 3 };   // CRNERF_LANCZOS_OUT_*
+int lanczos_ksize(int in_size, int out_size);
+size_t lanczos_workspace_bytes(int H, int W, int w, int h);
+bool lanczos_fits(int H, int W, int w, int h);            // sizes, grid and the horizontal pass's LDS within one launch's limits
+int launch_lanczos_resize(const uint8_t* src, int H, int W, int w, int h, const int* kx, const int* bx, int ksize_x, const int* ky, const int* by,
+                          int ksize_y, int mode, void* dst, void* workspace, hipStream_t stream);
+
 }  // namespace crnerf

@@ -5,7 +5,8 @@ by one HIP gather kernel (crnerf_grid_sample_batch_f32) instead of host indexing
 
 What is mirrored: the sampling arithmetic and its RNG stream (numpy seed per (epoch, idx), torch's global CPU generator
 for scale / offsets) and the sample dict.  What is NOT here: COLMAP / image file reading (out of scope) --
-the caller supplies all_rays[N,9], all_rgbs[N,3], all_imgs_wh[n_img,2] as the reference builds them (:139-200).
+the caller supplies all_rays[N,9], all_rgbs[N,3], all_imgs_wh[n_img,2] as the reference builds them (:139-200);
+datasets.images.build_train_buffers builds them on the device from decoded photos and their cameras.
 """
 from math import exp, sqrt
 

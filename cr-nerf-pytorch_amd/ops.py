@@ -1113,6 +1113,71 @@ def lpips(pred, gt, weights, roi=None, quantize_pred=False, normalize=True, want
     return out6[5], out6[:5], features
 
 
+LANCZOS_TILE = (_lib.LANCZOS_TILE_H, _lib.LANCZOS_TILE_W)   # rows, output columns of one workgroup of the horizontal pass (csrc/imageprep.hip)
+LANCZOS_VBLOCK = _lib.LANCZOS_VBLOCK                         # bytes of an output row of one workgroup of the vertical pass
+_lanczos_ws = {}
+_lanczos_tables = {}
+
+
+def _lanczos_axis(dev, in_size, out_size):
+    """(k, bounds, ksize) of one axis on the device, built once per (device, size pair); (None, None, 0) for a pass that is skipped."""
+    if in_size == out_size:
+        return None, None, 0
+    key = (dev, in_size, out_size)
+    got = _lanczos_tables.get(key)
+    if got is None:
+        from .datasets.images import lanczos_coeffs
+        k, bounds = lanczos_coeffs(in_size, out_size)
+        if len(_lanczos_tables) >= 256:
+            _lanczos_tables.clear()
+        got = _lanczos_tables[key] = (torch.from_numpy(k).to(dev), torch.from_numpy(bounds).to(dev), int(k.shape[1]))
+    return got
+
+
+def lanczos_resize(img_u8, size_wh, out="u8", signed=False, dst=None):
+    """crnerf_lanczos_resize_u8: PIL.Image.resize(size_wh, Image.LANCZOS) of a decoded photo, bit for bit, with the reference's tensor
+    conversions fused into the store.  img_u8: contiguous uint8 [H, W, 3] on the GPU; size_wh = (w, h).
+    out="u8": uint8 [h, w, 3]; "rows": float32 [h*w, 3] = ToTensor(img).view(3, -1).permute(1, 0) (the rgbs / all_rgbs layout);
+    "chw": float32 [3, h, w] = ToTensor(img), with signed=True Normalize(0.5, 0.5) of it ([-1, 1], the whole_img layout).
+    dst: write there instead of a fresh tensor -- contiguous, of the output's dtype and shape (a slice of rows of a larger buffer is).
+    A size that equals the source's skips that pass; with both skipped the call is the conversion alone."""
+    if not torch.is_tensor(img_u8) or not img_u8.is_cuda:
+        raise ValueError("crnerf_amd: lanczos_resize needs a GPU tensor (got %s); the HIP path has no CPU fallback"
+                         % (img_u8.device if torch.is_tensor(img_u8) else type(img_u8).__name__))
+    if img_u8.dtype != torch.uint8:
+        raise ValueError("crnerf_amd: lanczos_resize takes a uint8 image, got %s" % img_u8.dtype)
+    if img_u8.dim() != 3 or img_u8.shape[2] != 3 or img_u8.shape[0] < 1 or img_u8.shape[1] < 1:
+        raise ValueError("crnerf_amd: lanczos_resize takes an image of shape [H, W, 3], got %s" % (tuple(img_u8.shape),))
+    if not img_u8.is_contiguous():
+        raise ValueError("crnerf_amd: lanczos_resize takes a contiguous image")
+    if img_u8.device.index != _lib._current_device():
+        raise _lib._bad_tensor(img_u8, "img_u8", torch.uint8)
+    if out not in ("u8", "rows", "chw") or (signed and out != "chw"):
+        raise ValueError("crnerf_amd: out must be 'u8', 'rows' or 'chw' (signed=True with 'chw' only), got %r" % (out,))
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    w, h = (int(v) for v in size_wh)
+    if w < 1 or h < 1:
+        raise ValueError("crnerf_amd: lanczos_resize to a size below 1x1: %s" % ((w, h),))
+    dev = img_u8.device
+    shape, dtype = {"u8": ((h, w, 3), torch.uint8), "rows": ((h * w, 3), torch.float32), "chw": ((3, h, w), torch.float32)}[out]
+    if dst is None:
+        dst = torch.empty(shape, dtype=dtype, device=dev)
+    elif (not torch.is_tensor(dst) or dst.device != dev or dst.dtype != dtype or tuple(dst.shape) != shape or not dst.is_contiguous()):
+        raise ValueError("crnerf_amd: dst must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
+    lib = _lib.load()
+    kx, bx, ksx = _lanczos_axis(dev, W, w)
+    ky, by, ksy = _lanczos_axis(dev, H, h)
+    need = lib.crnerf_lanczos_workspace_bytes(H, W, w, h)
+    ws = _lanczos_ws.get(dev)
+    if need and (ws is None or ws.numel() < need):
+        ws = _lanczos_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)     # stream-ordered reuse, like the metrics workspace
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _lib.check(lib.crnerf_lanczos_resize_u8(p(img_u8), H, W, w, h, p(kx), p(bx), ksx, p(ky), p(by), ksy,
+                                            _lib.LANCZOS_OUT["chw_signed" if signed else out], p(dst), p(ws) if need else None, _lib.stream_ptr()),
+               "crnerf_lanczos_resize_u8")
+    return dst
+
+
 def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset):
     lib = _lib.load()
     all_rays, all_rgbs = _f32c(all_rays, "all_rays"), _f32c(all_rgbs, "all_rgbs")

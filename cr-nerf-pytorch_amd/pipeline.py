@@ -127,7 +127,8 @@ def evaluate_image(models, embeddings, enc_a, sample, hparams_, chunk=32768, pre
     half of the image -- the left half is what the appearance encoder saw).  The image stays on the device: the prediction's uint8 round
     trip through the PNG (eval.py:296-297) is applied by the metrics kernel on load (quantize_pred=True, what makes the numbers comparable
     with the reference's result.txt; False scores the raw decode).  half=None scores the whole image (eval_metric.py:95-98, blender).
-    sample: 'rays' [H*W,8], 'ts' [H*W], 'rgbs' [H*W,3], 'whole_img' [3,h,w] in [-1,1], 'img_wh' (w, h).
+    sample: 'rays' [H*W,8], 'ts' [H*W], 'rgbs' [H*W,3], 'whole_img' [3,h,w] in [-1,1], 'img_wh' (w, h) -- datasets.images.make_eval_sample
+    builds it on the device from a decoded photo and its camera.
     Returns {'rgb': [H*W,3] (the raw decode), 'psnr', 'ssim', 'mse'} -- 0-dim device tensors."""
     device = next(models["coarse"].parameters()).device
     W, H = (int(v) for v in torch.as_tensor(sample['img_wh']).reshape(-1)[:2])              # eval.py:287

@@ -606,6 +606,42 @@ typedef struct crnerf_lpips_args {
 size_t crnerf_lpips_workspace_bytes(int32_t w, int32_t h);
 int crnerf_lpips_f32(const crnerf_lpips_args* args, double* out6, float* const* features_or_null, void* workspace, void* stream);
 
+/* -------- image preparation: PIL.Image.resize((w, h), Image.LANCZOS) of a decoded 8-bit RGB photo, bit for bit, with
+ * torchvision's ToTensor / Normalize(0.5, 0.5) fused into the store -- what datasets/phototourism_mask_grid_sample.py:183-199, :288-320 and
+ * eval.py:140-151 do on the host to build rgbs, whole_img and the style image.
+ * Pillow's 8-bit path, restated.  Per axis, in_size -> out_size, in float64 on the HOST (crnerf_amd.datasets.images.lanczos_coeffs):
+ *   scale = in_size / out_size, fs = max(scale, 1), support = 3 fs, ksize = (int)ceil(support) * 2 + 1; for every output xx:
+ *   center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in_size) - xmin,
+ *   w[x] = lanczos((x + xmin - center + 0.5) / fs), x < xmax, lanczos(t) = sinc(t) sinc(t / 3) on -3 <= t < 3, else 0; w /= sum(w) (summed
+ *   in order, unless 0); k[x] = (int)(w[x] * 2^22 + 0.5) (- 0.5 for w[x] < 0); k[xmax ... ksize-1] = 0.
+ *   table: int32 k[out_size][ksize], int32 bounds[out_size][2] = (xmin, xmax).
+ * One pass along an axis, per channel: acc = 2^21 + sum_{x < xmax} in[xmin + x] * k[x] in int32 (sum |k| * 255 + 2^21 < 2^31 is the
+ * table builder's to assert), out = clamp(acc >> 22, 0, 255), an arithmetic shift.  The horizontal pass runs first, when w != W, into a
+ * uint8 image [H, w, 3]; the vertical pass second, when h != H, on that image; a pass that keeps its size is skipped.
+ * src: [H, W, 3] uint8, contiguous, device.  kx / bounds_x: the tables of W -> w, ky / bounds_y: of H -> h (device; those of a skipped
+ * pass are not read and may be NULL; kx 16-byte aligned); ksize_x / ksize_y must be the ksize of their size pair (CRNERF_ERR_CONFIG).
+ * out_mode selects what the last pass that runs stores to dst (with both passes skipped the conversion is the whole call):
+ *   CRNERF_LANCZOS_OUT_U8          uint8 [h, w, 3]
+ *   CRNERF_LANCZOS_OUT_ROWS        fp32 [h*w, 3] = ToTensor(img).view(3, -1).permute(1, 0): v / 255, a correctly rounded division
+ *   CRNERF_LANCZOS_OUT_CHW         fp32 [3, h, w] = ToTensor(img)
+ *   CRNERF_LANCZOS_OUT_CHW_SIGNED  fp32 [3, h, w] = Normalize(0.5, 0.5)(ToTensor(img)): (v / 255 - 0.5) / 0.5
+ * each bit-identical to the torch expression evaluated on the host.  dst is a base pointer: a slice of a larger buffer is a valid target.
+ * workspace: crnerf_lanczos_workspace_bytes(H, W, w, h) bytes -- the uint8 image between the passes, H * w * 3, or 0 when at most one pass
+ * runs (then it may be NULL).  The tables are read with their windows clamped to the image: no table content makes the kernels leave src.
+ * Returns CRNERF_ERR_NULL for a missing pointer, CRNERF_ERR_SHAPE for a size < 1, an image of 2^31 bytes or more, more than 65,535 output
+ * rows, or a horizontal downscale beyond what one tile's rows fit in 64 KiB of LDS (W / w up to 32 always fits). */
+#define CRNERF_LANCZOS_OUT_U8 0
+#define CRNERF_LANCZOS_OUT_ROWS 1
+#define CRNERF_LANCZOS_OUT_CHW 2
+#define CRNERF_LANCZOS_OUT_CHW_SIGNED 3
+#define CRNERF_LANCZOS_TILE_H 8      /* rows x output columns of one workgroup of the horizontal pass ...                  */
+#define CRNERF_LANCZOS_TILE_W 32
+#define CRNERF_LANCZOS_VBLOCK 256    /* ... and bytes of an output row of one workgroup of the vertical pass: sizes worth testing */
+size_t crnerf_lanczos_workspace_bytes(int32_t H, int32_t W, int32_t w, int32_t h);
+int crnerf_lanczos_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t w, int32_t h, const int32_t* kx, const int32_t* bounds_x,
+                             int32_t ksize_x, const int32_t* ky, const int32_t* bounds_y, int32_t ksize_y, int32_t out_mode, void* dst,
+                             void* workspace, void* stream);
+
 /* Operators of the transient-mask network: Context_Guided_Network(classes=1, M=2, N=2, input_channel=3),
  * models/lightweight_seg.py:274-368, applied once per step to the 1/8-scale photo (train_mask_grid_sample.py:170-176).
  * All tensors NCHW fp32, batch 1, contiguous; every backward OVERWRITES its gradient outputs. */
