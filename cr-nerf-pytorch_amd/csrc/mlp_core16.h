@@ -25,6 +25,17 @@ constexpr int V16_WAVES = 8;
 constexpr int V16_PIECES = STAGE_FRAGS / V16_WAVES;   // LDS-DMA pieces per wave per stage (2)
 constexpr int V16_AHEAD = 4;                          // fragments read ahead of use (crosses stage barriers)
 
+// The schedule levers of the INFERENCE kernels (render_rays16 / _rng / _lean, mlp_forward16; WeightPipe16T below), as compile-time switches so that
+// tools/variants.py can build each alone: -DCRNERF_CORE16_LAG=0|2|4|6, -DCRNERF_CORE16_PRIO=0|1.  The training twins keep LAG = 0, PRIO = 0.
+// Shipped: LAG = 6 (-1.6 % kernel time on 1,024 x (64+128); LAG 2 and 4 gained 0.7 % / 0.8 %, inside twice the run-to-run spread), PRIO = 0
+// (no gain alone, a loss on top of LAG = 6): profiles/r8/core16_ab.txt, DESIGN Appendix A.
+#ifndef CRNERF_CORE16_LAG
+#define CRNERF_CORE16_LAG 6
+#endif
+#ifndef CRNERF_CORE16_PRIO
+#define CRNERF_CORE16_PRIO 0
+#endif
+
 // k-groups (16 k-values) and output tiles (16 rows) per layer
 constexpr int U_XYZ = XYZ_PAD / 16;   // 6
 constexpr int U_HID = W_HIDDEN / 16;  // 16
@@ -38,9 +49,57 @@ constexpr int U_HALF = 128 / 16;      // 8
 // other user of the pipe compiles to the code it had.
 constexpr int TRUNK_STAGES = OFF_FIN / STAGE_FRAGS;   // 124 of the 151
 static_assert(OFF_FIN % STAGE_FRAGS == 0, "the trunk must be whole stages");
-template <bool TRUNK0>
+//
+// LAG (fragments, even; 0: the unstaggered ring, every wave meets the barrier behind the last step of a stage): sub-stage stagger of the two waves
+// of a SIMD.  All eight waves pass one s_barrier per stage and every layer is a whole number of stages, so with LAG = 0 partners w and w+4 are
+// phase-locked: both drain their MFMAs, run the 64 v_max and reload 16 bias fragments at the same instant, eleven times a tile, and the SIMD's
+// matrix pipe idles.  With LAG > 0 waves 4..7 (the "late half", stagger == 1) execute the s_waitcnt + s_barrier of stage c IN FRONT of step
+// LATE_S = STAGE_FRAGS - 2 - LAG of that stage, waves 0..3 (the "early half") where they always did, behind step STAGE_FRAGS - 2.  Still exactly
+// one ring barrier per wave and stage, in the same order relative to every other barrier of the kernel (a stage never spans a layer, so no ring
+// barrier moves across a wg_barrier) -- only its place in the wave's own stream differs, and the barrier now releases the late half LAG + 2
+// fragments behind the early one: one partner's layer epilogue and barrier wait fall under the other's MFMAs.  The slot bookkeeping (rd_slot,
+// rd_addr) stays behind step STAGE_FRAGS - 2 in both halves.  Both rendezvous sit in wave-uniform branches of their own, so they are
+// exact points of the wave's stream: hipcc schedules inside basic blocks and moves no MFMA or LDS read across them.
+// Why that is safe (b_c: the barrier of stage c; a wave has "consumed" a fragment when the MFMAs that use it have been issued):
+//   Refill.  Wave w's pieces write fragments 2w, 2w+1 of a slot: the early half refills fragments 0..7, the late half 8..15.  The pieces a wave
+//     issues during stage c carry stage c + 5 into slot(c - 1).
+//     - Early half: in front of steps EARLY_P0 / EARLY_P1 of stage c, i.e. after b_(c-1).  Every early wave was then behind the last step of
+//       stage c - 1; every late wave in front of its step LATE_S, where it has consumed every fragment below LATE_S.
+//       LATE_S >= STAGE_FRAGS / 2  <=>  LAG <= 6: fragments 0..7 are free.
+//     - Late half: a late wave's pieces must wait for the OTHER late waves too, and b_(c-1) only says that those had consumed stage c - 1 below
+//       LATE_S.  So the late half issues its pieces of stage c behind its own b_c, in front of steps LATE_S and LATE_S + 2: b_c is released when
+//       every late wave is at step LATE_S of stage c and every early wave behind the last step of stage c -- all of stage c - 1 is consumed.
+//       (With the LAG = 0 positions, steps 4 and 12, a late wave could rewrite fragments 8..15 while another late wave still has LAG of them
+//       to read: right by timing only.)
+//     - The two halves' pieces never issue together: the late positions are the early half's steps 0 and 2 in time, the early ones 4 and 10.
+//   Certification.  vmcnt counts pieces in issue order.  At b_c an early wave has issued every piece up to stage c + 5 and allows
+//     V16_PIECES * (RING_SLOTS - 4) = 4 in flight: stages c + 4 and c + 5, so its pieces of stage c + 3 have landed ("c+2 certified" while
+//     stage c is read, mlp_core.h: that was b_(c-1)).  A late wave has at b_c issued every piece up to stage c + 4 and none of stage c + 5; it
+//     allows V16_PIECES in flight, stage c + 4: its pieces of stage c + 3 have landed.  Both halves certify the same stage at the same barrier.
+//     (start() certifies stages 0, 1; a late wave's b_0 comes with all ten start-up pieces issued and nothing else: stages 0..3.)
+//   Look-ahead.  Reads cross into stage c + 1 from step STAGE_FRAGS - V16_AHEAD = 12 of stage c on, in both halves; stage c + 1 was certified
+//     by b_(c-2), and every wave at stage c has passed b_(c-1).  The stagger does not enter.
+// tests/test_core16_ring_model.py steps a host model of this ring through adversarial orders for LAG 0, 2, 4, 6 and shows LAG 8 failing.
+// PRIO: waves 4..7 raise their issue priority once (s_setprio 1) when the pipe starts -- a measured trial, DESIGN Appendix A.
+template <bool TRUNK0, int LAG = 0, bool PRIO = false>
 struct WeightPipe16T {
   static constexpr bool trunk0 = TRUNK0;
+  static constexpr int SYNC_S = STAGE_FRAGS - 2;               // the step BEHIND which the early half (and everyone at LAG = 0) meets the barrier
+  static constexpr int LATE_S = SYNC_S - LAG;                  // the step IN FRONT of which the late half meets it (LAG > 0)
+  static constexpr int EARLY_P0 = 4, EARLY_P1 = 10;            // LAG > 0: an early wave issues its two pieces in front of these steps,
+  static constexpr int LATE_P0 = LATE_S, LATE_P1 = LATE_S + 2; //          a late wave in front of these (LAG = 0: steps 0, 8 and 4, 12)
+  static constexpr int SYNC_VMCNT = V16_PIECES * (RING_SLOTS - 4);
+  static constexpr int LATE_VMCNT = V16_PIECES * (RING_SLOTS - 5);
+  static_assert(LAG >= 0 && LAG % 2 == 0, "the barrier sits between fragment-pair steps");
+  static_assert(V16_WAVES == 8 && V16_PIECES * (V16_WAVES / 2) == STAGE_FRAGS / 2, "refill: waves 0..3 own fragments 0..7, waves 4..7 own 8..15");
+  static_assert(LATE_S >= STAGE_FRAGS / 2, "refill: behind b_(c-1) the early half rewrites fragments 0..7 of slot(c-1); the late half must have consumed them");
+  static_assert(LAG == 0 || (LATE_P0 >= LATE_S && LATE_P1 > LATE_P0 && LATE_P1 <= SYNC_S), "refill: the late half's pieces of stage c come behind its own b_c, inside stage c");
+  static_assert(EARLY_P0 >= 0 && EARLY_P1 > EARLY_P0 && EARLY_P1 <= SYNC_S, "certification: both early pieces of a stage are issued in front of its barrier");
+  static_assert(SYNC_VMCNT == 2 * V16_PIECES && LATE_VMCNT == V16_PIECES,
+                "certification: in flight at b_c are stage c + 4 and what the wave has issued of stage c + 5 (early: all, late: none); stage c + 3 has landed");
+  static_assert(LAG == 0 || ((LATE_P0 + LAG + 2) % STAGE_FRAGS != EARLY_P0 && (LATE_P0 + LAG + 2) % STAGE_FRAGS != EARLY_P1 &&
+                             (LATE_P1 + LAG + 2) % STAGE_FRAGS != EARLY_P0 && (LATE_P1 + LAG + 2) % STAGE_FRAGS != EARLY_P1),
+                "the partners' ~66-cycle piece issues must not coincide");
   lds_char* lds;
   const char* base[2];   // wave-uniform: packed streams + this wave's 2 KiB column (the lane offset rides in the VGPR-offset operand)
   const char* pf_ptr;
@@ -75,6 +134,7 @@ struct WeightPipe16T {
     wave2k = (uint32_t)wave * (V16_PIECES * FRAG_BYTES);
     lds_ring = (uint32_t)(uintptr_t)lds_ + LDS_RING + wave2k;
     stagger = (wave >> 2) & 1;   // waves w and w+4 of a 512-thread workgroup share a SIMD
+    if (PRIO && stagger) __builtin_amdgcn_s_setprio(1);
     base[0] = stream0 + wave2k;
     base[1] = stream1 + wave2k;
     passes0 = passes0_;
@@ -98,11 +158,47 @@ struct WeightPipe16T {
     return LDS_RING + n * STAGE_BYTES + lane16;
   }
 
-  __device__ __forceinline__ void advance() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(V16_PIECES * (RING_SLOTS - 4)) : "memory");
+  // The two halves of a stage turn: the rendezvous (this wave's pieces of stage c + 3 have landed; everyone is where the ring needs them) ...
+  __device__ __forceinline__ void rendezvous() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SYNC_VMCNT) : "memory");
     __builtin_amdgcn_s_barrier();
+  }
+  __device__ __forceinline__ void rendezvous_late() {   // the same barrier, LAG + 2 fragments earlier in a late wave's stream
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LATE_VMCNT) : "memory");
+    __builtin_amdgcn_s_barrier();
+  }
+  // ... and the step to the next slot
+  __device__ __forceinline__ void bump() {
     rd_slot = (rd_slot + 1 == RING_SLOTS) ? 0u : rd_slot + 1;
     rd_addr = LDS_RING + rd_slot * STAGE_BYTES + lane16;
+  }
+  __device__ __forceinline__ void advance() {
+    rendezvous();
+    bump();
+  }
+  // in front of step s of the current stage: the late half's rendezvous, this wave's LDS-DMA pieces
+  __device__ __forceinline__ void before_step(int s) {
+    if (LAG == 0) {
+      // the two waves sharing a SIMD issue their LDS-DMA pieces at different fragment slots, so one's
+      // ~66-cycle issue stall is covered by the other's MFMAs
+      if (s % 4 == 0 && ((s >> 2) & 1) == stagger) issue_piece(s >> 3);
+    } else if (stagger) {                  // (a step may be a piece position of both halves: each half looks at its own)
+      if (s == LATE_S) rendezvous_late();
+      if (s == LATE_P0) issue_piece(0);
+      if (s == LATE_P1) issue_piece(1);
+    } else {
+      if (s == EARLY_P0) issue_piece(0);
+      if (s == EARLY_P1) issue_piece(1);
+    }
+  }
+  // behind step s
+  __device__ __forceinline__ void after_step(int s) {
+    if (s != SYNC_S) return;
+    if (LAG == 0) advance();
+    else {
+      if (!stagger) rendezvous();
+      bump();
+    }
   }
 
   // fragment at stream position (slot-in-stage) s of the current stage; s >= 16 reads ahead into the next stage
@@ -116,7 +212,8 @@ struct WeightPipe16T {
     for (int i = 0; i < V16_AHEAD; ++i) q[i] = read_slot(i);
   }
 };
-typedef WeightPipe16T<false> WeightPipe16;
+typedef WeightPipe16T<false> WeightPipe16;                                                  // training kernels (mlp_train16.hip)
+typedef WeightPipe16T<false, CRNERF_CORE16_LAG, CRNERF_CORE16_PRIO != 0> WeightPipe16Infer;   // mlp_forward16.hip
 
 // acc[T][r] = bias[16T + 4g + r]
 template <int NT>
@@ -158,9 +255,7 @@ __device__ __forceinline__ void mma_layer16(PIPE& p, const f32x4 (&srcA)[NA], co
     for (int T = 0; T < NT; T += 2) {   // two fragments (tiles T, T+1 of k-group u) per step: two independent MFMA chains
       const int f = u * NT + T;
       const int s = f % STAGE_FRAGS;
-      // the two waves sharing a SIMD issue their LDS-DMA pieces at different fragment slots, so one's
-      // ~66-cycle issue stall is covered by the other's MFMAs
-      if (s % 4 == 0 && ((s >> 2) & 1) == p.stagger) p.issue_piece(s >> 3);
+      p.before_step(s);
       const f32x4 a0 = q[f % V16_AHEAD], a1 = q[(f + 1) % V16_AHEAD];
       q[f % V16_AHEAD] = p.read_slot(s + V16_AHEAD);
       q[(f + 1) % V16_AHEAD] = p.read_slot(s + 1 + V16_AHEAD);
@@ -170,7 +265,7 @@ __device__ __forceinline__ void mma_layer16(PIPE& p, const f32x4 (&srcA)[NA], co
         acc[T] = CRNERF_MFMA16(a0[r], b, acc[T]);
         acc[T + 1] = CRNERF_MFMA16(a1[r], b, acc[T + 1]);
       }
-      if (s == STAGE_FRAGS - 2) p.advance();
+      p.after_step(s);
       if (DEF::pieces > 0) {          // one deferred store every STRIDE steps (>= 8 x 64 cycles of store data path between a wave's stores)
         const int step = f / 2;
         if (step % STRIDE == 0 && step / STRIDE < DEF::pieces) def.piece(step / STRIDE);

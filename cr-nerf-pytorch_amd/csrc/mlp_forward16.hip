@@ -14,7 +14,7 @@ __global__ __launch_bounds__(512, 2) void mlp_forward16_kernel(const char* __res
   const int p = lane & 15, g = lane >> 4;
 
   load_consts(lds, packed, packed);
-  WeightPipe16 pipe;
+  WeightPipe16Infer pipe;
   pipe.start(lds, packed + CONST_BYTES, packed + CONST_BYTES, 1, 1, lane, wave);
   f32x4 q[V16_AHEAD];
   pipe.prime(q);

@@ -34,10 +34,12 @@ static __device__ unsigned int crnerf_sched16[SCHED_SLOTS][2];   // kernels.h "D
 // What the training twin adds to the renderer (crnerf_render_rays_train_f32): every tile's layer activations + relu bits
 // (ActSaver, mlp_train16.h) and its raw MLP output row, per pass.  The inference kernel instantiates the no-op hook.
 struct NoHook {
+  static constexpr bool train = false;
   __device__ __forceinline__ NoSave saver(int, long, int, int, bool, int) const { return NoSave(); }
   __device__ __forceinline__ void raw(int, long, int, int, bool, int, const f32x4 (&)[4], float) const {}
 };
 struct TrainHook {
+  static constexpr bool train = true;
   float* acts[2];   // [10][R*N][256] + masks, pass 0 = coarse (N = Nc), pass 1 = fine (N = Nc+Ni)
   float* rawo[2];   // [R*N][65]
   long R;
@@ -80,7 +82,8 @@ __device__ __forceinline__ void render_rays16_impl(const RenderParams16& a, cons
   lds_float* dirbuf = (lds_float*)(lds + LDS_SCRATCH + 4 * PAIR_BYTES) + wave * 32;   // 32 floats per wave
 
   const int steps_c = (Nc + 31) >> 5, steps_f = Ni > 0 ? (Nf + 31) >> 5 : 0;
-  WeightPipe16T<LEAN> pipe;
+  // the schedule levers (mlp_core16.h) are for the inference kernels; the training twins keep the unstaggered ring and compile to the code they had
+  WeightPipe16T<LEAN, HOOK::train ? 0 : CRNERF_CORE16_LAG, !HOOK::train && CRNERF_CORE16_PRIO != 0> pipe;
   pipe.start(lds, a.packed0 + CONST_BYTES, a.packed1 + CONST_BYTES, steps_c, steps_c + steps_f, lane, wave);
   f32x4 q[V16_AHEAD];
   pipe.prime(q);

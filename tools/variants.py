@@ -4,7 +4,8 @@
 
 compiles the named units with build.py's flags + the extra ones into cr-nerf-pytorch_amd/build_NAME/, links them with the shipped build's other
 objects into cr-nerf-pytorch_amd/variants/libcrnerf_NAME.so (git-ignored, travels to the GPU box with the snapshot) -- cross-compiled here, so no
-GPU-minute is spent on hipcc.  On the box: CRNERF_LIB_PATH=cr-nerf-pytorch_amd/variants/libcrnerf_NAME.so python tools/<bench>.py"""
+GPU-minute is spent on hipcc; hipcc's output for each unit (e.g. the remarks of -Rpass-analysis=kernel-resource-usage) is kept as build_NAME/<unit>.log.
+On the box: CRNERF_LIB_PATH=cr-nerf-pytorch_amd/variants/libcrnerf_NAME.so python tools/<bench>.py"""
 import importlib.util
 import os
 import subprocess
@@ -34,6 +35,8 @@ def main(name, extra, units):
         out, _ = p.communicate()
         if p.returncode != 0:
             raise SystemExit("hipcc failed on %s:\n%s" % (u, out.decode(errors="replace")[-3000:]))
+        with open(obj[:-2] + ".log", "wb") as f:             # hipcc's remarks, e.g. of -Rpass-analysis=kernel-resource-usage
+            f.write(out)
         objs[u] = obj
     link = [objs.get(s, os.path.join(PKG, "build", s.replace(".hip", ".o"))) for s in b.SOURCES]
     lib = os.path.join(PKG, "variants", "libcrnerf_%s.so" % name)
