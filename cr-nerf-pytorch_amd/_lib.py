@@ -44,6 +44,7 @@ EXPORTS = [
     "crnerf_image_metrics_workspace_bytes", "crnerf_image_metrics_f32",
     "crnerf_lpips_workspace_bytes", "crnerf_lpips_f32",
     "crnerf_lanczos_workspace_bytes", "crnerf_lanczos_resize_u8",
+    "crnerf_scene_bounds_workspace_bytes", "crnerf_scene_bounds_f64",
 ]
 
 _c_fp = ctypes.c_void_p  # device float*
@@ -277,6 +278,8 @@ def load():
             "crnerf_lpips_f32": (ctypes.c_int, [ctypes.POINTER(LpipsArgs), vp, pp, vp, vp]),
             "crnerf_lanczos_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32, i32]),
             "crnerf_lanczos_resize_u8": (ctypes.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
+            "crnerf_scene_bounds_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
+            "crnerf_scene_bounds_f64": (ctypes.c_int, [vp, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h

@@ -859,6 +859,31 @@ int crnerf_lanczos_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t w
   return launch_lanczos_resize(src, H, W, w, h, kx, bounds_x, ksize_x, ky, bounds_y, ksize_y, out_mode, dst, workspace, (hipStream_t)stream);
 }
 
+// a percentile argument the comparisons below may be trusted with: not NaN, not infinite (this unit is compiled with -fno-honor-nans)
+static bool finite_bits(double v) {
+  uint64_t b;
+  memcpy(&b, &v, sizeof b);
+  return (b & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+}
+
+size_t crnerf_scene_bounds_workspace_bytes(int32_t n_images, int32_t n_points) {
+  if (n_images < 1 || n_points < 0) return 0;
+  return scene_bounds_workspace_bytes(n_images, n_points);
+}
+
+int crnerf_scene_bounds_f64(const double* xyz, int32_t n_points, const double* w2c_row2, int32_t n_images, double q_lo, double q_hi, double* nears,
+                            double* fars, int32_t* counts, void* workspace, void* stream) {
+  if (n_images < 1) return set_error(CRNERF_ERR_SHAPE, "scene_bounds: n_images must be positive");
+  if (n_points < 0) return set_error(CRNERF_ERR_SHAPE, "scene_bounds: negative n_points");
+  if (n_points > 0) REQUIRE(xyz, "xyz");
+  REQUIRE(w2c_row2, "w2c_row2"); REQUIRE(nears, "nears"); REQUIRE(fars, "fars"); REQUIRE(counts, "counts");
+  if (!finite_bits(q_lo) || !finite_bits(q_hi) || q_lo < 0.0 || q_lo > 100.0 || q_hi < 0.0 || q_hi > 100.0)
+    return set_error(CRNERF_ERR_CONFIG, "scene_bounds: a percentile outside [0, 100]");
+  if (q_lo > q_hi) return set_error(CRNERF_ERR_CONFIG, "scene_bounds: q_lo above q_hi");
+  if (scene_bounds_workspace_bytes(n_images, n_points) > 0) REQUIRE(workspace, "workspace");
+  return launch_scene_bounds(xyz, n_points, w2c_row2, n_images, q_lo / 100.0, q_hi / 100.0, nears, fars, counts, workspace, (hipStream_t)stream);
+}
+
 static int to_geom(const crnerf_conv_geom* a, ConvGeom& g) {
   if (a->cin <= 0 || a->cout <= 0 || a->H <= 0 || a->W <= 0 || a->k <= 0 || a->stride <= 0 || a->dil <= 0 || a->pad < 0)
     return set_error(CRNERF_ERR_SHAPE, "conv2d: non-positive geometry");

@@ -274,4 +274,10 @@ bool lanczos_fits(int H, int W, int w, int h);            // sizes, grid and the
 int launch_lanczos_resize(const uint8_t* src, int H, int W, int w, int h, const int* kx, const int* bx, int ksize_x, const int* ky, const int* by,
                           int ksize_y, int mode, void* dst, void* workspace, hipStream_t stream);
 
+// ---- scene bounds (scenebounds.hip): per image, two percentiles of the camera-space depth of the sparse model's points in front of it
+// rows: [N,4] = row 2 of every world-to-camera matrix; f_lo / f_hi: the percentiles as fractions in [0, 1]
+size_t scene_bounds_workspace_bytes(int n_images, int n_points);
+int launch_scene_bounds(const double* xyz, int n_points, const double* rows, int n_images, double f_lo, double f_hi, double* nears,
+                        double* fars, int* counts, void* workspace, hipStream_t stream);
+
 }  // namespace crnerf

@@ -1178,6 +1178,48 @@ def lanczos_resize(img_u8, size_wh, out="u8", signed=False, dst=None):
     return dst
 
 
+_scene_ws = {}
+
+
+def scene_bounds(xyz, w2c_row2, q_lo=0.1, q_hi=99.9):
+    """crnerf_scene_bounds_f64: per image, np.percentile(depth[depth > 0], q_lo) and (..., q_hi) of the camera-space depth
+    ((x r20 + y r21) + z r22) + t2 of every point (include/crnerf.h states the arithmetic; read_meta :133-137 in the reference).
+    xyz: float64 [P, 3], w2c_row2: float64 [N, 4] = (r20, r21, r22, t2) per image, both contiguous on the GPU.  Returns (nears float64 [N],
+    fars float64 [N], counts int32 [N]); an image with nothing in front of it has count 0 and NaN bounds."""
+    for t, name, cols in ((xyz, "xyz", 3), (w2c_row2, "w2c_row2", 4)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("crnerf_amd: scene_bounds needs GPU tensors (%s is %s); the HIP path has no CPU fallback"
+                             % (name, t.device if torch.is_tensor(t) else type(t).__name__))
+        if t.dtype != torch.float64:
+            raise TypeError("crnerf_amd: scene_bounds takes float64 (%s is %s): the reference holds the sparse model and the poses in float64"
+                            % (name, t.dtype))
+        if t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError("crnerf_amd: %s must have shape [*, %d], got %s" % (name, cols, tuple(t.shape)))
+    n_points, n_images = int(xyz.shape[0]), int(w2c_row2.shape[0])
+    if n_images < 1:
+        raise ValueError("crnerf_amd: scene_bounds needs at least one image")
+    if n_points >= 2 ** 31:
+        raise ValueError("crnerf_amd: scene_bounds takes fewer than 2^31 points, got %d" % n_points)
+    q_lo, q_hi = float(q_lo), float(q_hi)
+    if not (0.0 <= q_lo <= q_hi <= 100.0):
+        raise ValueError("crnerf_amd: scene_bounds needs 0 <= q_lo <= q_hi <= 100, got (%r, %r)" % (q_lo, q_hi))
+    lib = _lib.load()
+    dev = xyz.device
+    nears = torch.empty(n_images, dtype=torch.float64, device=dev)
+    fars = torch.empty(n_images, dtype=torch.float64, device=dev)
+    counts = torch.empty(n_images, dtype=torch.int32, device=dev)
+    need = lib.crnerf_scene_bounds_workspace_bytes(n_images, n_points)
+    ws = _scene_ws.get(dev)
+    if need and (ws is None or ws.numel() < need):
+        ws = _scene_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)     # stream-ordered reuse, like the metrics workspace
+    _lib.check(lib.crnerf_scene_bounds_f64(_lib.dev_ptr(xyz, "xyz", torch.float64) if n_points else None, n_points,
+                                           _lib.dev_ptr(w2c_row2, "w2c_row2", torch.float64), n_images, q_lo, q_hi,
+                                           _lib.dev_ptr(nears, "nears", torch.float64), _lib.dev_ptr(fars, "fars", torch.float64),
+                                           _lib.dev_ptr(counts, "counts", torch.int32), ctypes.c_void_p(ws.data_ptr()) if need else None,
+                                           _lib.stream_ptr()), "crnerf_scene_bounds_f64")
+    return nears, fars, counts
+
+
 def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset):
     lib = _lib.load()
     all_rays, all_rgbs = _f32c(all_rays, "all_rays"), _f32c(all_rgbs, "all_rgbs")

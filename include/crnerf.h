@@ -642,6 +642,27 @@ int crnerf_lanczos_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t w
                              int32_t ksize_x, const int32_t* ky, const int32_t* bounds_y, int32_t ksize_y, int32_t out_mode, void* dst,
                              void* workspace, void* stream);
 
+/* -------- scene bounds: one near and one far bound per image from the sparse model, what PhototourismDataset.read_meta,
+ * datasets/phototourism_mask_grid_sample.py:130-137, computes per image with (xyz_world_h @ w2c.T)[:, 2], a depth > 0 filter and
+ * np.percentile(depths, 0.1) / np.percentile(depths, 99.9).  Everything is float64, as the reference holds it.
+ * Depth of point (x, y, z) in image i, with (r20, r21, r22, t2) = row 2 of its world-to-camera matrix [[R, t], [0, 0, 0, 1]]:
+ *   depth = ((x r20 + y r21) + z r22) + t2, separate multiplies and adds (the reference's BLAS product fixes no order; this one is ours).
+ * A point is IN FRONT when depth > 0, decided on the bit pattern: with b the 64 bits of depth as an unsigned integer,
+ *   0 < b <= 0x7FF0000000000000 -- positive finite values, denormals included, and +inf; +0, -0, negatives and NaN are not.
+ * With n points in front and s their depths in ascending order, the bound at q percent is np.percentile(s, q), default (linear) method:
+ *   v = (q / 100) (n - 1), lo = floor(v), g = v - lo, a = s[lo], b = s[min(lo + 1, n - 1)], d = b - a,
+ *   result = a + d g when g < 0.5, else b - d (1 - g).
+ * xyz: [n_points, 3]; w2c_row2: [n_images, 4]; nears / fars: [n_images] = the bounds at q_lo / q_hi; counts: [n_images] = n.
+ * An image with n == 0 gets NaN (0x7FF8000000000000) in both bounds and count 0.  The result is a function of the inputs alone:
+ * repeated calls agree bit for bit (integer counting, no floating-point atomics).
+ * workspace: crnerf_scene_bounds_workspace_bytes(n_images, n_points) bytes; this implementation keeps its histograms on chip and
+ * stores no depth, so that is 0 and workspace may then be NULL.  All pointers are device pointers; nothing is allocated; asynchronous
+ * on `stream`.  Returns CRNERF_ERR_SHAPE for n_images < 1 or n_points < 0, CRNERF_ERR_NULL for a missing pointer (xyz may be NULL when
+ * n_points == 0), CRNERF_ERR_CONFIG for a percentile outside [0, 100] (NaN included) or q_lo > q_hi. */
+size_t crnerf_scene_bounds_workspace_bytes(int32_t n_images, int32_t n_points);
+int crnerf_scene_bounds_f64(const double* xyz, int32_t n_points, const double* w2c_row2, int32_t n_images, double q_lo, double q_hi,
+                            double* nears, double* fars, int32_t* counts, void* workspace, void* stream);
+
 /* Operators of the transient-mask network: Context_Guided_Network(classes=1, M=2, N=2, input_channel=3),
  * models/lightweight_seg.py:274-368, applied once per step to the 1/8-scale photo (train_mask_grid_sample.py:170-176).
  * All tensors NCHW fp32, batch 1, contiguous; every backward OVERWRITES its gradient outputs. */
