@@ -13,40 +13,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CRNERF_LIB_PATH: a tuning build of the same library (tools/variants.py) -- never a different backend; a path that does not exist raises at load
 LIB_PATH = os.environ.get("CRNERF_LIB_PATH") or os.path.join(_HERE, "libcrnerf_hip.so")
 
-EXPORTS = [
-    "crnerf_abi_version", "crnerf_last_error", "crnerf_packed_mlp_bytes", "crnerf_pack_mlp_weights",
-    "crnerf_posenc_f32", "crnerf_embed_points_f32", "crnerf_mlp_forward_f32", "crnerf_composite_f32", "crnerf_composite_backward_f32", "crnerf_sample_pdf_merge_f32",
-    "crnerf_render_rays_f32", "crnerf_render_rays_lean_f32", "crnerf_render_rays_train_f32", "crnerf_rng_fill_f32", "crnerf_mlp_backward_ex_f32", "crnerf_packed_mlp_mixed_bytes",
-    "crnerf_pack_mlp_weights_mixed", "crnerf_mlp_train_mixed_acts_bytes", "crnerf_mlp_train_mixed_scratch_bytes", "crnerf_mlp_forward_train_mixed_f32", "crnerf_mlp_backward_mixed_f32", "crnerf_mlp_backward_mixed_ex_f32", "crnerf_render_rays_train_bf16", "crnerf_crossray_workspace_bytes", "crnerf_crossray_chansum_f32",
-    "crnerf_crossray_gram_f32", "crnerf_crossray_matrix_f32", "crnerf_crossray_fold_f32",
-    "crnerf_crossray_apply_f32", "crnerf_crossray_decode_f32",
-    "crnerf_packed_mlp_t_bytes", "crnerf_pack_mlp_weights_t", "crnerf_mlp_train_acts_bytes", "crnerf_mlp_train_scratch_bytes",
-    "crnerf_mlp_forward_train_f32", "crnerf_mlp_backward_f32",
-    "crnerf_ray_directions_f32", "crnerf_rays_from_directions_f32", "crnerf_generate_rays_f32",
-    "crnerf_encoder_workspace_bytes", "crnerf_encoder_forward_f32",
-    "crnerf_crossray_backward_workspace_bytes", "crnerf_crossray_decode_backward_f32", "crnerf_crossray_decode_sharded_f32",
-    "crnerf_crossray_decode_backward_sharded_f32",
-    "crnerf_packed_mlp_h2_bytes", "crnerf_pack_mlp_weights_h2", "crnerf_mlp_forward_f32h2", "crnerf_render_rays_f32h2",
-    "crnerf_render_rays_f32x3_repair", "crnerf_mlp_forward_f32x3_repair",
-    "crnerf_render_rays_train_f32h2", "crnerf_render_rays_train_f32x3_repair", "crnerf_packed_mlp_t_h2_bytes", "crnerf_pack_mlp_weights_t_h2", "crnerf_mlp_backward_h2_f32", "crnerf_pack_mlp_weights_h2_async", "crnerf_pack_h2_status",
-    "crnerf_packed_mlp_x3_bytes", "crnerf_pack_mlp_weights_x3", "crnerf_mlp_forward_f32x3", "crnerf_render_rays_f32x3", "crnerf_render_rays_train_f32x3", "crnerf_packed_mlp_t_x3_bytes", "crnerf_pack_mlp_weights_t_x3", "crnerf_mlp_backward_x3_f32", "crnerf_packed_mlp_bf16_bytes", "crnerf_pack_mlp_weights_bf16", "crnerf_mlp_forward_bf16", "crnerf_render_rays_bf16", "crnerf_render_rays_bf16_fine",
-    "crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16",
-    "crnerf_decoder_content_backward_workspace_bytes", "crnerf_decoder_content_backward_f32",
-    "crnerf_encoder_train_saved_bytes", "crnerf_encoder_train_scratch_bytes", "crnerf_encoder_forward_train_f32", "crnerf_encoder_backward_f32",
-    "crnerf_encoder_train_band_saved_bytes", "crnerf_encoder_train_band_scratch_bytes", "crnerf_encoder_forward_train_band_f32", "crnerf_encoder_backward_band_f32",
-    "crnerf_loss_workspace_bytes", "crnerf_loss_f32", "crnerf_loss_backward_f32", "crnerf_grid_sample_batch_f32", "crnerf_adam_max_tensors", "crnerf_adam_step_f32",
-    "crnerf_conv2d_f32", "crnerf_conv2d_backward_f32", "crnerf_bn_prelu_f32", "crnerf_bn_prelu_train_f32", "crnerf_bn_prelu_backward_f32", "crnerf_avgpool3s2_f32",
-    "crnerf_fglo_f32", "crnerf_fglo_backward_f32", "crnerf_bilinear_gather_f32", "crnerf_bilinear_gather_backward_f32",
-    "crnerf_cgnet_param_count", "crnerf_cgnet_bn_count", "crnerf_cgnet_arena_bytes", "crnerf_cgnet_forward_train_f32", "crnerf_cgnet_backward_f32",
-    "crnerf_peer_window_bytes", "crnerf_peer_window_create", "crnerf_peer_window_open", "crnerf_peer_window_close", "crnerf_peer_window_destroy",
-    "crnerf_peer_window_status", "crnerf_peer_allreduce_f32",
-    "crnerf_cus_per_xcd", "crnerf_stream_create_cu_share", "crnerf_stream_destroy",
-    "crnerf_image_metrics_workspace_bytes", "crnerf_image_metrics_f32",
-    "crnerf_lpips_workspace_bytes", "crnerf_lpips_f32",
-    "crnerf_lanczos_workspace_bytes", "crnerf_lanczos_resize_u8",
-    "crnerf_scene_bounds_workspace_bytes", "crnerf_scene_bounds_f64",
-]
-
 _c_fp = ctypes.c_void_p  # device float*
 
 
@@ -136,6 +102,142 @@ class ConvGeom(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("cin", "cout", "H", "W", "k", "stride", "pad", "dil", "depthwise")]
 
 
+# One row per symbol of include/crnerf.h: name -> (restype, argtypes).  This table IS the export list (EXPORTS below): build() checks the library
+# against it, load() binds it, tests/test_host.py holds it to the header's prototypes.  One spelling per C type, so that equal prototypes read equal.
+i64, i32, u32, u64, f32, f64 = ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_double      # i32: int / int32_t
+usz, cstr, vp = ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p
+pp = ctypes.POINTER(ctypes.c_void_p)                     # a host array of pointers (every `T* const*`)
+hf = ctypes.POINTER(ctypes.c_float)                      # a host float array (`*_host`)
+ra = ctypes.POINTER(RenderArgs)
+SIGNATURES = {
+    "crnerf_abi_version": (i32, []),
+    "crnerf_last_error": (cstr, []),
+    "crnerf_packed_mlp_bytes": (usz, []),
+    "crnerf_crossray_workspace_bytes": (usz, []),
+    "crnerf_pack_mlp_weights": (i32, [pp, vp, vp]),
+    "crnerf_packed_mlp_t_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_t": (i32, [pp, vp, vp]),
+    "crnerf_mlp_train_acts_bytes": (usz, [i64]),
+    "crnerf_mlp_train_scratch_bytes": (usz, [i64]),
+    "crnerf_mlp_forward_train_f32": (i32, [vp, vp, vp, vp, i64, vp]),
+    "crnerf_mlp_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, pp, i64, vp]),
+    "crnerf_mlp_backward_ex_f32": (i32, [vp, vp, vp, vp, vp, vp, pp, i64, i32, vp]),
+    "crnerf_packed_mlp_mixed_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_mixed": (i32, [pp, vp, vp]),
+    "crnerf_mlp_train_mixed_acts_bytes": (usz, [i64]),
+    "crnerf_mlp_train_mixed_scratch_bytes": (usz, [i64]),
+    "crnerf_mlp_forward_train_mixed_f32": (i32, [pp, vp, vp, vp, vp, i64, vp]),
+    "crnerf_mlp_backward_mixed_f32": (i32, [pp, vp, vp, vp, vp, vp, vp, pp, i64, vp]),
+    "crnerf_mlp_backward_mixed_ex_f32": (i32, [pp, vp, vp, vp, vp, vp, pp, i64, i32, vp]),
+    "crnerf_posenc_f32": (i32, [vp, vp, i64, i32, vp]),
+    "crnerf_embed_points_f32": (i32, [vp, vp, vp, vp, i64, i32, vp]),
+    "crnerf_encoder_workspace_bytes": (usz, [i32, i32]),
+    "crnerf_encoder_forward_f32": (i32, [vp, i32, i32, pp, vp, vp, vp]),
+    "crnerf_ray_directions_f32": (i32, [i32, i32, f32, f32, f32, f32, vp, vp]),
+    "crnerf_rays_from_directions_f32": (i32, [vp, hf, i64, vp, vp, vp]),
+    "crnerf_generate_rays_f32": (i32, [hf, hf, i32, i32, f32, f32, vp, vp]),
+    "crnerf_mlp_forward_f32": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_composite_f32": (i32, [vp, vp, vp, f32, vp, vp, vp, i64, i32, vp]),
+    "crnerf_composite_backward_f32": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, vp]),
+    "crnerf_sample_pdf_merge_f32": (i32, [vp, vp, vp, i64, vp, vp, i64, i32, i32, vp]),
+    "crnerf_render_rays_f32": (i32, [ra, vp]),
+    "crnerf_render_rays_lean_f32": (i32, [ra, vp]),
+    "crnerf_rng_fill_f32": (i32, [vp, i64, i32, u64, i32, i64, vp]),
+    "crnerf_render_rays_train_f32": (i32, [ra, vp, vp, vp, vp, vp]),
+    "crnerf_render_rays_train_bf16": (i32, [ra, vp, vp, vp, vp, vp]),
+    "crnerf_render_rays_bf16": (i32, [ra, vp]),
+    "crnerf_render_rays_bf16_fine": (i32, [ra, vp]),
+    "crnerf_packed_mlp_h2_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_h2": (i32, [pp, vp, vp]),
+    "crnerf_mlp_forward_f32h2": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_render_rays_f32h2": (i32, [ra, vp]),
+    "crnerf_render_rays_f32x3_repair": (i32, [ra, vp]),
+    "crnerf_mlp_forward_f32x3_repair": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_render_rays_train_f32h2": (i32, [ra, vp, vp, vp, vp, vp]),
+    "crnerf_render_rays_train_f32x3_repair": (i32, [ra, vp, vp, vp, vp, vp]),
+    "crnerf_packed_mlp_t_h2_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_t_h2": (i32, [pp, vp, vp]),
+    "crnerf_mlp_backward_h2_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, pp, i64, i32, vp]),
+    "crnerf_pack_mlp_weights_h2_async": (i32, [pp, vp, vp]),
+    "crnerf_pack_h2_status": (i32, [vp, vp]),
+    "crnerf_packed_mlp_x3_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_x3": (i32, [pp, vp, vp]),
+    "crnerf_mlp_forward_f32x3": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_render_rays_f32x3": (i32, [ra, vp]),
+    "crnerf_render_rays_train_f32x3": (i32, [ra, vp, vp, vp, vp, vp]),
+    "crnerf_packed_mlp_t_x3_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_t_x3": (i32, [pp, vp, vp]),
+    "crnerf_mlp_backward_x3_f32": (i32, [vp, vp, vp, vp, vp, vp, pp, i64, i32, vp]),
+    "crnerf_packed_mlp_bf16_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_bf16": (i32, [pp, vp, vp]),
+    "crnerf_mlp_forward_bf16": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_packed_mlp_f16_bytes": (usz, []),
+    "crnerf_pack_mlp_weights_f16": (i32, [pp, vp, vp]),
+    "crnerf_mlp_forward_f16": (i32, [vp, vp, vp, i64, i32, vp]),
+    "crnerf_render_rays_f16": (i32, [ra, vp]),
+    "crnerf_crossray_chansum_f32": (i32, [vp, i64, vp, vp, vp]),
+    "crnerf_crossray_gram_f32": (i32, [vp, i64, vp, pp, vp, vp, vp]),
+    "crnerf_crossray_matrix_f32": (i32, [vp, f64, vp, vp, vp, vp]),
+    "crnerf_crossray_fold_f32": (i32, [vp, vp, vp, vp, pp, vp, vp]),
+    "crnerf_crossray_apply_f32": (i32, [vp, i64, vp, vp, i64, vp]),
+    "crnerf_crossray_backward_workspace_bytes": (usz, [i64, i64]),
+    "crnerf_crossray_decode_backward_f32": (i32, [vp, i64, vp, i64, pp, vp, i64, vp, vp, vp, pp, vp]),
+    "crnerf_crossray_decode_sharded_f32": (i32, [vp, i64, vp, i64, pp, i32, vp, f64, vp, vp, i64, vp]),
+    "crnerf_crossray_decode_backward_sharded_f32": (i32, [vp, i64, vp, i64, pp, vp, i64, vp, vp, vp, pp, i32, vp, f64, vp, vp]),
+    "crnerf_crossray_decode_f32": (i32, [vp, i64, vp, i64, pp, vp, vp, i64, vp]),
+    "crnerf_decoder_content_backward_workspace_bytes": (usz, [i64]),
+    "crnerf_decoder_content_backward_f32": (i32, [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "crnerf_encoder_train_saved_bytes": (usz, [i32, i32]),
+    "crnerf_encoder_train_scratch_bytes": (usz, [i32, i32]),
+    "crnerf_encoder_forward_train_f32": (i32, [vp, i32, i32, pp, vp, vp, vp]),
+    "crnerf_encoder_backward_f32": (i32, [i32, i32, pp, vp, vp, vp, vp, pp, vp, vp]),
+    "crnerf_encoder_train_band_saved_bytes": (usz, [i32, i32, i32]),
+    "crnerf_encoder_train_band_scratch_bytes": (usz, [i32, i32, i32]),
+    "crnerf_encoder_forward_train_band_f32": (i32, [vp, i32, i32, i32, i32, i32, i32, pp, vp, vp, vp]),
+    "crnerf_encoder_backward_band_f32": (i32, [i32, i32, i32, i32, i32, i32, pp, vp, vp, vp, vp, pp, vp, vp]),
+    "crnerf_loss_workspace_bytes": (usz, []),
+    "crnerf_loss_f32": (i32, [ctypes.POINTER(LossArgs), vp, vp, vp]),
+    "crnerf_loss_backward_f32": (i32, [ctypes.POINTER(LossArgs), vp, ctypes.POINTER(LossGrads), vp]),
+    "crnerf_grid_sample_batch_f32": (i32, [ctypes.POINTER(BatchArgs), vp]),
+    "crnerf_adam_max_tensors": (i32, []),
+    "crnerf_adam_step_f32": (i32, [vp, vp, vp, vp, i32, pp, i32, f32, f32, f32, f32, f32, f32, vp]),
+    "crnerf_conv2d_f32": (i32, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp]),
+    "crnerf_conv2d_backward_f32": (i32, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp, vp, vp]),
+    "crnerf_bn_prelu_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, f32, i32, vp]),
+    "crnerf_bn_prelu_train_f32": (i32, [vp] * 11 + [f32, i32, i64, f32, vp]),
+    "crnerf_bn_prelu_backward_f32": (i32, [vp] * 11 + [i32, i64, i32, vp]),
+    "crnerf_avgpool3s2_f32": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "crnerf_fglo_f32": (i32, [vp] * 7 + [i32, i32, i64, vp]),
+    "crnerf_fglo_backward_f32": (i32, [vp] * 11 + [i32, i32, i64, vp]),
+    "crnerf_bilinear_gather_f32": (i32, [vp, i32, i32, i32, i32, vp, i64, i32, vp, vp]),
+    "crnerf_bilinear_gather_backward_f32": (i32, [vp, vp, i32, i32, i32, i32, vp, i64, i32, vp, vp]),
+    "crnerf_cgnet_param_count": (i32, []),
+    "crnerf_cgnet_bn_count": (i32, []),
+    "crnerf_cgnet_arena_bytes": (usz, [i32, i32, i32]),
+    "crnerf_cgnet_forward_train_f32": (i32, [vp, i32, i32, i32, pp, pp, pp, pp, f32, f32, vp, vp, vp]),
+    "crnerf_cgnet_backward_f32": (i32, [vp, i32, i32, i32, pp, vp, vp, vp, vp, pp, vp]),
+    "crnerf_peer_window_bytes": (usz, []),
+    "crnerf_peer_window_create": (i32, [pp, ctypes.c_char_p]),
+    "crnerf_peer_window_open": (i32, [ctypes.c_char_p, pp]),
+    "crnerf_peer_window_close": (i32, [vp]),
+    "crnerf_peer_window_destroy": (i32, [vp]),
+    "crnerf_peer_window_status": (i32, [vp, ctypes.POINTER(i32)]),
+    "crnerf_peer_allreduce_f32": (i32, [vp, i32, pp, i32, i32, u32, i64, vp]),
+    "crnerf_cus_per_xcd": (i32, []),
+    "crnerf_stream_create_cu_share": (i32, [pp, i32, i32]),
+    "crnerf_stream_destroy": (i32, [vp]),
+    "crnerf_image_metrics_workspace_bytes": (usz, [i32, i32, i32]),
+    "crnerf_image_metrics_f32": (i32, [ctypes.POINTER(ImageMetricsArgs), vp, vp, vp, vp]),
+    "crnerf_lpips_workspace_bytes": (usz, [i32, i32]),
+    "crnerf_lpips_f32": (i32, [ctypes.POINTER(LpipsArgs), vp, pp, vp, vp]),
+    "crnerf_lanczos_workspace_bytes": (usz, [i32, i32, i32, i32]),
+    "crnerf_lanczos_resize_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
+    "crnerf_scene_bounds_workspace_bytes": (usz, [i32, i32]),
+    "crnerf_scene_bounds_f64": (i32, [vp, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp]),
+}
+EXPORTS = list(SIGNATURES)
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -153,135 +255,7 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        i64, i32, vp, f32, f64 = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
-        pp = ctypes.POINTER(ctypes.c_void_p)
-        sig = {
-            "crnerf_abi_version": (ctypes.c_int, []),
-            "crnerf_last_error": (ctypes.c_char_p, []),
-            "crnerf_packed_mlp_bytes": (ctypes.c_size_t, []),
-            "crnerf_crossray_workspace_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_packed_mlp_t_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_t": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_train_acts_bytes": (ctypes.c_size_t, [i64]),
-            "crnerf_mlp_train_scratch_bytes": (ctypes.c_size_t, [i64]),
-            "crnerf_mlp_forward_train_f32": (ctypes.c_int, [vp, vp, vp, vp, i64, vp]),
-            "crnerf_mlp_backward_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, pp, i64, vp]),
-            "crnerf_mlp_backward_ex_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, pp, i64, i32, vp]),
-            "crnerf_packed_mlp_mixed_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_mixed": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_train_mixed_acts_bytes": (ctypes.c_size_t, [i64]),
-            "crnerf_mlp_train_mixed_scratch_bytes": (ctypes.c_size_t, [i64]),
-            "crnerf_mlp_forward_train_mixed_f32": (ctypes.c_int, [pp, vp, vp, vp, vp, i64, vp]),
-            "crnerf_mlp_backward_mixed_f32": (ctypes.c_int, [pp, vp, vp, vp, vp, vp, vp, pp, i64, vp]),
-            "crnerf_mlp_backward_mixed_ex_f32": (ctypes.c_int, [pp, vp, vp, vp, vp, vp, pp, i64, ctypes.c_int, vp]),
-            "crnerf_posenc_f32": (ctypes.c_int, [vp, vp, i64, i32, vp]),
-            "crnerf_embed_points_f32": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, vp]),
-            "crnerf_encoder_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
-            "crnerf_encoder_forward_f32": (ctypes.c_int, [vp, i32, i32, pp, vp, vp, vp]),
-            "crnerf_ray_directions_f32": (ctypes.c_int, [i32, i32, f32, f32, f32, f32, vp, vp]),
-            "crnerf_rays_from_directions_f32": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float), i64, vp, vp, vp]),
-            "crnerf_generate_rays_f32": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), i32, i32, f32, f32, vp, vp]),
-            "crnerf_mlp_forward_f32": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_composite_f32": (ctypes.c_int, [vp, vp, vp, f32, vp, vp, vp, i64, i32, vp]),
-            "crnerf_composite_backward_f32": (ctypes.c_int, [vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, vp]),
-            "crnerf_sample_pdf_merge_f32": (ctypes.c_int, [vp, vp, vp, i64, vp, vp, i64, i32, i32, vp]),
-            "crnerf_render_rays_f32": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_render_rays_lean_f32": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_rng_fill_f32": (ctypes.c_int, [vp, i64, i32, ctypes.c_uint64, i32, i64, vp]),
-            "crnerf_render_rays_train_f32": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp, vp, vp, vp, vp]),
-            "crnerf_render_rays_train_bf16": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp, vp, vp, vp, vp]),
-            "crnerf_render_rays_bf16": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_render_rays_bf16_fine": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_packed_mlp_h2_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_h2": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_forward_f32h2": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_render_rays_f32h2": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_render_rays_f32x3_repair": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_mlp_forward_f32x3_repair": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_render_rays_train_f32h2": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp, vp, vp, vp, vp]),
-            "crnerf_render_rays_train_f32x3_repair": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp, vp, vp, vp, vp]),
-            "crnerf_packed_mlp_t_h2_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_t_h2": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_backward_h2_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, pp, i64, ctypes.c_int, vp]),
-            "crnerf_pack_mlp_weights_h2_async": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_pack_h2_status": (ctypes.c_int, [vp, vp]),
-            "crnerf_packed_mlp_x3_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_x3": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_forward_f32x3": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_render_rays_f32x3": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_render_rays_train_f32x3": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp, vp, vp, vp, vp]),
-            "crnerf_packed_mlp_t_x3_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_t_x3": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_backward_x3_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, pp, i64, ctypes.c_int, vp]),
-            "crnerf_packed_mlp_bf16_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_bf16": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_forward_bf16": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_packed_mlp_f16_bytes": (ctypes.c_size_t, []),
-            "crnerf_pack_mlp_weights_f16": (ctypes.c_int, [pp, vp, vp]),
-            "crnerf_mlp_forward_f16": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
-            "crnerf_render_rays_f16": (ctypes.c_int, [ctypes.POINTER(RenderArgs), vp]),
-            "crnerf_crossray_chansum_f32": (ctypes.c_int, [vp, i64, vp, vp, vp]),
-            "crnerf_crossray_gram_f32": (ctypes.c_int, [vp, i64, vp, pp, vp, vp, vp]),
-            "crnerf_crossray_matrix_f32": (ctypes.c_int, [vp, f64, vp, vp, vp, vp]),
-            "crnerf_crossray_fold_f32": (ctypes.c_int, [vp, vp, vp, vp, pp, vp, vp]),
-            "crnerf_crossray_apply_f32": (ctypes.c_int, [vp, i64, vp, vp, i64, vp]),
-            "crnerf_crossray_backward_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
-            "crnerf_crossray_decode_backward_f32": (ctypes.c_int, [vp, i64, vp, i64, pp, vp, i64, vp, vp, vp, pp, vp]),
-            "crnerf_crossray_decode_sharded_f32": (ctypes.c_int, [vp, i64, vp, i64, pp, i32, vp, f64, vp, vp, i64, vp]),
-            "crnerf_crossray_decode_backward_sharded_f32": (ctypes.c_int, [vp, i64, vp, i64, pp, vp, i64, vp, vp, vp, pp, i32, vp, f64, vp, vp]),
-            "crnerf_crossray_decode_f32": (ctypes.c_int, [vp, i64, vp, i64, pp, vp, vp, i64, vp]),
-            "crnerf_decoder_content_backward_workspace_bytes": (ctypes.c_size_t, [i64]),
-            "crnerf_decoder_content_backward_f32": (ctypes.c_int, [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
-            "crnerf_encoder_train_saved_bytes": (ctypes.c_size_t, [i32, i32]),
-            "crnerf_encoder_train_scratch_bytes": (ctypes.c_size_t, [i32, i32]),
-            "crnerf_encoder_forward_train_f32": (ctypes.c_int, [vp, i32, i32, pp, vp, vp, vp]),
-            "crnerf_encoder_backward_f32": (ctypes.c_int, [i32, i32, pp, vp, vp, vp, vp, pp, vp, vp]),
-            "crnerf_encoder_train_band_saved_bytes": (ctypes.c_size_t, [i32, i32, i32]),
-            "crnerf_encoder_train_band_scratch_bytes": (ctypes.c_size_t, [i32, i32, i32]),
-            "crnerf_encoder_forward_train_band_f32": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, i32, pp, vp, vp, vp]),
-            "crnerf_encoder_backward_band_f32": (ctypes.c_int, [i32, i32, i32, i32, i32, i32, pp, vp, vp, vp, vp, pp, vp, vp]),
-            "crnerf_loss_workspace_bytes": (ctypes.c_size_t, []),
-            "crnerf_loss_f32": (ctypes.c_int, [ctypes.POINTER(LossArgs), vp, vp, vp]),
-            "crnerf_loss_backward_f32": (ctypes.c_int, [ctypes.POINTER(LossArgs), vp, ctypes.POINTER(LossGrads), vp]),
-            "crnerf_grid_sample_batch_f32": (ctypes.c_int, [ctypes.POINTER(BatchArgs), vp]),
-            "crnerf_adam_max_tensors": (ctypes.c_int, []),
-            "crnerf_adam_step_f32": (ctypes.c_int, [vp, vp, vp, vp, i32, pp, i32, f32, f32, f32, f32, f32, f32, vp]),
-            "crnerf_conv2d_f32": (ctypes.c_int, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp]),
-            "crnerf_conv2d_backward_f32": (ctypes.c_int, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp, vp, vp]),
-            "crnerf_bn_prelu_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, f32, i32, vp]),
-            "crnerf_bn_prelu_train_f32": (ctypes.c_int, [vp] * 11 + [f32, i32, i64, f32, vp]),
-            "crnerf_bn_prelu_backward_f32": (ctypes.c_int, [vp] * 11 + [i32, i64, i32, vp]),
-            "crnerf_avgpool3s2_f32": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, vp]),
-            "crnerf_fglo_f32": (ctypes.c_int, [vp] * 7 + [i32, i32, i64, vp]),
-            "crnerf_fglo_backward_f32": (ctypes.c_int, [vp] * 11 + [i32, i32, i64, vp]),
-            "crnerf_bilinear_gather_f32": (ctypes.c_int, [vp, i32, i32, i32, i32, vp, i64, i32, vp, vp]),
-            "crnerf_bilinear_gather_backward_f32": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, i32, vp, vp]),
-            "crnerf_cgnet_param_count": (ctypes.c_int, []),
-            "crnerf_cgnet_bn_count": (ctypes.c_int, []),
-            "crnerf_cgnet_arena_bytes": (ctypes.c_size_t, [i32, i32, i32]),
-            "crnerf_cgnet_forward_train_f32": (ctypes.c_int, [vp, i32, i32, i32, pp, pp, pp, pp, f32, f32, vp, vp, vp]),
-            "crnerf_cgnet_backward_f32": (ctypes.c_int, [vp, i32, i32, i32, pp, vp, vp, vp, vp, pp, vp]),
-            "crnerf_peer_window_bytes": (ctypes.c_size_t, []),
-            "crnerf_peer_window_create": (ctypes.c_int, [pp, ctypes.c_char_p]),
-            "crnerf_peer_window_open": (ctypes.c_int, [ctypes.c_char_p, pp]),
-            "crnerf_peer_window_close": (ctypes.c_int, [vp]),
-            "crnerf_peer_window_destroy": (ctypes.c_int, [vp]),
-            "crnerf_peer_window_status": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
-            "crnerf_peer_allreduce_f32": (ctypes.c_int, [vp, i32, pp, i32, i32, ctypes.c_uint32, i64, vp]),
-            "crnerf_cus_per_xcd": (ctypes.c_int, []),
-            "crnerf_stream_create_cu_share": (ctypes.c_int, [pp, i32, i32]),
-            "crnerf_stream_destroy": (ctypes.c_int, [vp]),
-            "crnerf_image_metrics_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32]),
-            "crnerf_image_metrics_f32": (ctypes.c_int, [ctypes.POINTER(ImageMetricsArgs), vp, vp, vp, vp]),
-            "crnerf_lpips_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
-            "crnerf_lpips_f32": (ctypes.c_int, [ctypes.POINTER(LpipsArgs), vp, pp, vp, vp]),
-            "crnerf_lanczos_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32, i32]),
-            "crnerf_lanczos_resize_u8": (ctypes.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
-            "crnerf_scene_bounds_workspace_bytes": (ctypes.c_size_t, [i32, i32]),
-            "crnerf_scene_bounds_f64": (ctypes.c_int, [vp, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp]),
-        }
-        for name, (res, args) in sig.items():
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h
             fn.restype = res
             fn.argtypes = args

@@ -102,26 +102,22 @@ using namespace crnerf;
 #define REQUIRE(p, name) \
   if (!(p)) return set_error(CRNERF_ERR_NULL, name " is NULL")
 
-extern "C" {
-
-int crnerf_abi_version(void) { return CRNERF_ABI_VERSION; }
-const char* crnerf_last_error(void) { return g_err; }
-size_t crnerf_packed_mlp_bytes(void) { return PACKED_BYTES; }
-size_t crnerf_crossray_workspace_bytes(void) { return CROSSRAY_WORKSPACE_BYTES; }
-
-int crnerf_pack_mlp_weights(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors");
-  REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights: a tensor pointer is NULL");
-  MlpTensors t;
-  for (int i = 0; i < 8; ++i) { t.w[i] = tensors[2 * i]; t.b[i] = tensors[2 * i + 1]; }
-  t.w_final = tensors[16]; t.b_final = tensors[17];
-  t.w_sigma = tensors[18]; t.b_sigma = tensors[19];
-  t.w_dir = tensors[20]; t.b_dir = tensors[21];
-  t.w_rgb = tensors[22]; t.b_rgb = tensors[23];
-  return launch_pack_mlp(t, packed, (hipStream_t)stream);
+// "<who>: <what>" -- composed here, on the failure path only, for the rules that several entry points share
+static int fail(int code, const char* who, const char* what) {
+  static thread_local char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return set_error(code, msg);
 }
+
+// every entry of a host list of n pointers (of two such lists) is set
+template <class A>
+static bool all_set(A* const* list, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!list[i]) return false;
+  return true;
+}
+template <class A, class B>
+static bool all_set2(A* const* a, B* const* b, int n) { return all_set(a, n) && all_set(b, n); }
 
 static MlpTensors to_tensors(const float* const* tensors) {
   MlpTensors t;
@@ -133,15 +129,133 @@ static MlpTensors to_tensors(const float* const* tensors) {
   return t;
 }
 
+static int null_tensor(const char* who) { return fail(CRNERF_ERR_NULL, who, "a tensor pointer is NULL"); }
+
+// the 24 tensors of a NeRF_sigma are all set
+static int require_tensors(const char* who, const float* const* tensors) { return all_set(tensors, CRNERF_MLP_TENSORS) ? 0 : null_tensor(who); }
+
+// every crnerf_pack_mlp_weights*: launch(MlpTensors, packed, hipStream_t) is the layout's packer
+template <class Launch>
+static int pack_entry(const char* who, const float* const* tensors, void* packed, void* stream, Launch launch) {
+  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
+  if (int rc = require_tensors(who, tensors)) return rc;
+  return launch(to_tensors(tensors), packed, (hipStream_t)stream);
+}
+
+// every crnerf_mlp_forward_*: launch(P) runs the core on the P = n points
+template <class Launch>
+static int forward_entry(const char* who, const void* packed, const float* x, float* out, int64_t n, Launch launch) {
+  if (n == 0) return 0;
+  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
+  if (n < 0) return fail(CRNERF_ERR_SHAPE, who, "negative n");
+  return launch((long)n);
+}
+
+// the 22 decoder tensors in kernel order (CRNERF_DECODER_TENSORS); a backward entry leaves workspace, rgb and plane_stride null
+static DecodeArgs to_decode_args(const float* content, int64_t HW, const float* style, int64_t HWs, const float* const* w, void* workspace = nullptr,
+                                 float* rgb = nullptr, int64_t plane_stride = 0) {
+  DecodeArgs d;
+  d.content = content; d.HW = (long)HW; d.style = style; d.HWs = (long)HWs;
+  d.snet = CnnTensors{w[0], w[1], w[2], w[3], w[4], w[5]}; d.snet_fc_w = w[6]; d.snet_fc_b = w[7];
+  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
+  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
+  d.workspace = workspace; d.rgb = rgb; d.plane_stride = (long)plane_stride;
+  return d;
+}
+
+// The single place that fills a RenderArgs from the ABI's struct; an entry point's own differences are overrides behind it.  The rng fields stay
+// at their defaults (perturb == 0) unless rng_flags asks for in-kernel draws, whatever the caller left in the struct.
+static RenderArgs to_render_args(const crnerf_render_args* a) {
+  RenderArgs r;
+  r.packed_coarse = a->packed_coarse; r.packed_fine = a->packed_fine; r.rays = a->rays; r.view_dir = a->view_dir;
+  r.z_coarse = a->z_coarse; r.z_steps = a->z_steps; r.u = a->u; r.u_stride = (long)a->u_stride; r.noise_coarse = a->noise_coarse; r.noise_fine = a->noise_fine;
+  r.noise_std = a->noise_std; r.use_disp = a->use_disp; r.R = (long)a->n_rays; r.Nc = a->n_samples; r.Ni = a->n_importance;
+  r.weights_coarse = a->weights_coarse; r.feature_coarse = a->feature_coarse; r.depth_coarse = a->depth_coarse;
+  r.weights_fine = a->weights_fine; r.feature_fine = a->feature_fine; r.depth_fine = a->depth_fine; r.z_fine = a->z_fine;
+  if (a->rng_flags) { r.rng_seed = a->rng_seed; r.rng_ray_offset = (long)a->rng_ray_offset; r.rng_flags = a->rng_flags; r.perturb = a->perturb; }
+  r.z_coarse_out = a->z_coarse_out; r.noise_coarse_out = a->noise_coarse_out; r.noise_fine_out = a->noise_fine_out;
+  return r;
+}
+
+// the kernel family behind a crnerf_render_rays_* entry
+enum class Core {
+  F32,         // inference and the fp32 training twin
+  BF16_PAIR,   // the pair core: inference and the mixed-precision training twin
+  F16_PAIR,    // its fp16-operand build; inference only
+  X3,          // three bf16 pieces
+  H2,          // two fp16 pieces
+  X3_REPAIR,   // the x3 core on the ray quads that hold a NaN
+};
+// the pair cores draw nothing in the kernel and write no *_out
+static bool is_pair_core(Core c) { return c == Core::BF16_PAIR || c == Core::F16_PAIR; }
+
+// what a training twin saves per pass; all null: inference
+struct TrainState { void* acts_coarse = nullptr; void* acts_fine = nullptr; float* raw_coarse = nullptr; float* raw_fine = nullptr; };
+
+static int require_train_state(const crnerf_render_args* a, const TrainState& t) {
+  REQUIRE(t.acts_coarse, "acts_coarse"); REQUIRE(t.raw_coarse, "raw_coarse");
+  if (a->n_importance > 0) { REQUIRE(t.acts_fine, "acts_fine"); REQUIRE(t.raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
+  return 0;
+}
+
+static int render_rays_common(const crnerf_render_args* a, void* stream, Core core, const TrainState& train = TrainState()) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays: negative n_rays");
+  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->rays, "rays");
+  REQUIRE(a->weights_coarse, "weights_coarse"); REQUIRE(a->feature_coarse, "feature_coarse"); REQUIRE(a->depth_coarse, "depth_coarse");
+  if (a->n_importance > 0) {
+    REQUIRE(a->packed_fine, "packed_fine");
+    REQUIRE(a->weights_fine, "weights_fine"); REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
+  }
+  if (a->rng_flags) {
+    if (a->rng_flags & ~(CRNERF_RNG_JITTER | CRNERF_RNG_U | CRNERF_RNG_NOISE)) return set_error(CRNERF_ERR_CONFIG, "render_rays: unknown rng_flags bits");
+    if (is_pair_core(core)) return set_error(CRNERF_ERR_CONFIG, "render_rays: in-kernel random draws exist in the fp32, f32x3 and f32h2 kernels only");
+    if ((a->rng_flags & CRNERF_RNG_JITTER) && a->z_coarse) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_JITTER and z_coarse are exclusive");
+    if ((a->rng_flags & CRNERF_RNG_U) && a->u) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_U and u are exclusive");
+    if ((a->rng_flags & CRNERF_RNG_NOISE) && (a->noise_coarse || a->noise_fine)) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_NOISE and noise_* are exclusive");
+  }
+  if ((a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out) && is_pair_core(core))   // (the bf16 kernels do not write them)
+    return set_error(CRNERF_ERR_CONFIG, "render_rays: z_coarse_out / noise_*_out are written by the fp32, f32x3 and f32h2 kernels only");
+  auto r = to_render_args(a);
+  r.train_acts_coarse = train.acts_coarse; r.train_acts_fine = train.acts_fine; r.train_raw_coarse = train.raw_coarse; r.train_raw_fine = train.raw_fine;
+  switch (core) {
+    case Core::H2: return launch_render_rays_h2(r, (hipStream_t)stream);
+    case Core::X3_REPAIR: r.repair = 1; return launch_render_rays_x3(r, (hipStream_t)stream);
+    case Core::X3: return launch_render_rays_x3(r, (hipStream_t)stream);
+    case Core::F16_PAIR: return launch_render_rays_f16p(r, (hipStream_t)stream);
+    case Core::BF16_PAIR: return launch_render_rays_bf16p(r, (hipStream_t)stream);
+    case Core::F32: break;
+  }
+  return launch_render_rays16(r, (hipStream_t)stream);
+}
+
+// the five crnerf_render_rays_train_*: the saved state is checked before anything render_rays_common checks
+static int render_rays_train(const crnerf_render_args* a, const TrainState& train, void* stream, Core core) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (int rc = require_train_state(a, train)) return rc;
+  return render_rays_common(a, stream, core, train);
+}
+
+extern "C" {
+
+int crnerf_abi_version(void) { return CRNERF_ABI_VERSION; }
+const char* crnerf_last_error(void) { return g_err; }
+size_t crnerf_packed_mlp_bytes(void) { return PACKED_BYTES; }
+size_t crnerf_crossray_workspace_bytes(void) { return CROSSRAY_WORKSPACE_BYTES; }
+
+int crnerf_pack_mlp_weights(const float* const* tensors, void* packed, void* stream) {
+  return pack_entry("pack_mlp_weights", tensors, packed, stream, launch_pack_mlp);
+}
+
 size_t crnerf_packed_mlp_t_bytes(void) { return PACKEDT_BYTES; }
 size_t crnerf_mlp_train_acts_bytes(int64_t n) { return mlp_train_acts_bytes((long)n); }
 size_t crnerf_mlp_train_scratch_bytes(int64_t n) { return mlp_train_scratch_bytes((long)n); }
 
 int crnerf_pack_mlp_weights_t(const float* const* tensors, void* packed_t, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed_t, "packed_t");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_t: a tensor pointer is NULL");
-  return launch_pack_mlpT(to_tensors(tensors), packed_t, (hipStream_t)stream);
+  REQUIRE(tensors, "tensors"); REQUIRE(packed_t, "packed_t");     // (this entry's message names the pack "packed_t")
+  return pack_entry("pack_mlp_weights_t", tensors, packed_t, stream, launch_pack_mlpT);
 }
 
 int crnerf_mlp_forward_train_f32(const void* packed, const float* x, float* out, void* acts, int64_t n, void* stream) {
@@ -154,18 +268,19 @@ int crnerf_mlp_forward_train_f32(const void* packed, const float* x, float* out,
 // CRNERF_BWD_PHASE_DGRAD / _WGRAD choose which half runs and with it which pointers are read.
 static int check_backward_args(const char* who, int flags, int modes, const void* packed_t, const float* x, const float* out, const float* d_out,
                                const void* acts, const void* scratch, float* const* grads) {
-  static thread_local char msg[160];
   const int phases = CRNERF_BWD_PHASE_DGRAD | CRNERF_BWD_PHASE_WGRAD;
-  if (flags & ~(modes | phases)) { snprintf(msg, sizeof msg, "%s: unknown flag bits", who); return set_error(CRNERF_ERR_CONFIG, msg); }
+  if (flags & ~(modes | phases)) return fail(CRNERF_ERR_CONFIG, who, "unknown flag bits");
   const int m = flags & modes;
-  if ((m & (m - 1)) != 0) { snprintf(msg, sizeof msg, "%s: the weight-gradient modes are exclusive", who); return set_error(CRNERF_ERR_CONFIG, msg); }
+  if ((m & (m - 1)) != 0) return fail(CRNERF_ERR_CONFIG, who, "the weight-gradient modes are exclusive");
   const bool dgrad = (flags & phases) != CRNERF_BWD_PHASE_WGRAD, wgrad = (flags & phases) != CRNERF_BWD_PHASE_DGRAD;
   const char* missing = !acts ? "acts" : !scratch ? "scratch" : (dgrad && !packed_t) ? "packed_t" : (dgrad && !out) ? "out" : (dgrad && !d_out) ? "d_out" :
                         (wgrad && !x) ? "x" : (wgrad && !grads) ? "grads" : nullptr;
-  if (missing) { snprintf(msg, sizeof msg, "%s: %s is NULL", who, missing); return set_error(CRNERF_ERR_NULL, msg); }
-  if (wgrad)
-    for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-      if (!grads[i]) { snprintf(msg, sizeof msg, "%s: a gradient pointer is NULL", who); return set_error(CRNERF_ERR_NULL, msg); }
+  if (missing) {
+    static thread_local char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s is NULL", who, missing);
+    return set_error(CRNERF_ERR_NULL, msg);
+  }
+  if (wgrad && !all_set(grads, CRNERF_MLP_TENSORS)) return fail(CRNERF_ERR_NULL, who, "a gradient pointer is NULL");
   return 0;
 }
 
@@ -197,12 +312,7 @@ int crnerf_embed_points_f32(const float* rays, const float* z, const float* dir_
 }
 
 int crnerf_mlp_forward_f32(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed");
-  REQUIRE(x, "x");
-  REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward: negative n");
-  return launch_mlp_forward16(packed, x, out, (long)n, sigma_only, (hipStream_t)stream);
+  return forward_entry("mlp_forward", packed, x, out, n, [&](long P) { return launch_mlp_forward16(packed, x, out, P, sigma_only, (hipStream_t)stream); });
 }
 
 int crnerf_composite_f32(const float* raw, const float* z, const float* noise, float noise_std, float* weights, float* feature,
@@ -229,46 +339,7 @@ int crnerf_sample_pdf_merge_f32(const float* z_coarse, const float* weights_coar
   return launch_sample_pdf_merge(z_coarse, weights_coarse, u, (long)u_stride, z_sorted, z_samples, (long)R, Nc, Ni, (hipStream_t)stream);
 }
 
-// x3: 0 = no, 1 = the x3 core (three bf16 pieces), 2 = the h2 core (two fp16 pieces), 3 = the x3 core repairing NaN ray quads
-// bf16: the pair core (no in-kernel draws); f16: its fp16-operand build
-static int render_rays_common(const crnerf_render_args* a, void* stream, bool bf16, void* acts_c = nullptr, void* acts_f = nullptr,
-                              float* raw_c = nullptr, float* raw_f = nullptr, int x3 = 0, bool f16 = false) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays: negative n_rays");
-  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->rays, "rays");
-  REQUIRE(a->weights_coarse, "weights_coarse"); REQUIRE(a->feature_coarse, "feature_coarse"); REQUIRE(a->depth_coarse, "depth_coarse");
-  if (a->n_importance > 0) {
-    REQUIRE(a->packed_fine, "packed_fine");
-    REQUIRE(a->weights_fine, "weights_fine"); REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
-  }
-  RenderArgs r;
-  r.packed_coarse = a->packed_coarse; r.packed_fine = a->packed_fine; r.rays = a->rays; r.view_dir = a->view_dir;
-  r.z_coarse = a->z_coarse; r.z_steps = a->z_steps; r.u = a->u; r.u_stride = (long)a->u_stride; r.noise_coarse = a->noise_coarse; r.noise_fine = a->noise_fine;
-  r.noise_std = a->noise_std; r.use_disp = a->use_disp; r.R = (long)a->n_rays; r.Nc = a->n_samples; r.Ni = a->n_importance;
-  r.weights_coarse = a->weights_coarse; r.feature_coarse = a->feature_coarse; r.depth_coarse = a->depth_coarse;
-  r.weights_fine = a->weights_fine; r.feature_fine = a->feature_fine; r.depth_fine = a->depth_fine; r.z_fine = a->z_fine;
-  r.train_acts_coarse = acts_c; r.train_acts_fine = acts_f; r.train_raw_coarse = raw_c; r.train_raw_fine = raw_f;
-  if (a->rng_flags) {
-    if (a->rng_flags & ~(CRNERF_RNG_JITTER | CRNERF_RNG_U | CRNERF_RNG_NOISE)) return set_error(CRNERF_ERR_CONFIG, "render_rays: unknown rng_flags bits");
-    if (bf16) return set_error(CRNERF_ERR_CONFIG, "render_rays: in-kernel random draws exist in the fp32, f32x3 and f32h2 kernels only");
-    if ((a->rng_flags & CRNERF_RNG_JITTER) && a->z_coarse) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_JITTER and z_coarse are exclusive");
-    if ((a->rng_flags & CRNERF_RNG_U) && a->u) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_U and u are exclusive");
-    if ((a->rng_flags & CRNERF_RNG_NOISE) && (a->noise_coarse || a->noise_fine)) return set_error(CRNERF_ERR_CONFIG, "render_rays: CRNERF_RNG_NOISE and noise_* are exclusive");
-    r.rng_seed = a->rng_seed; r.rng_ray_offset = (long)a->rng_ray_offset; r.rng_flags = a->rng_flags; r.perturb = a->perturb;
-  }
-  if ((a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out) && bf16)   // (the bf16 kernels do not write them)
-    return set_error(CRNERF_ERR_CONFIG, "render_rays: z_coarse_out / noise_*_out are written by the fp32, f32x3 and f32h2 kernels only");
-  r.z_coarse_out = a->z_coarse_out; r.noise_coarse_out = a->noise_coarse_out; r.noise_fine_out = a->noise_fine_out;
-  if (x3 == 2) return launch_render_rays_h2(r, (hipStream_t)stream);
-  if (x3 == 3) r.repair = 1;
-  if (x3) return launch_render_rays_x3(r, (hipStream_t)stream);
-  if (f16) return launch_render_rays_f16p(r, (hipStream_t)stream);     // inference only
-  if (bf16) return launch_render_rays_bf16p(r, (hipStream_t)stream);   // inference and (acts_c) the mixed-precision training twin
-  return launch_render_rays16(r, (hipStream_t)stream);                 // inference and (acts_c) the fp32 training twin
-}
-
-int crnerf_render_rays_f32(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, false); }
+int crnerf_render_rays_f32(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::F32); }
 int crnerf_rng_fill_f32(float* out, int64_t n_rays, int n, uint64_t seed, int stream_id, int64_t ray_offset, void* stream) {
   if (n_rays == 0 || n == 0) return 0;
   REQUIRE(out, "out");
@@ -277,7 +348,7 @@ int crnerf_rng_fill_f32(float* out, int64_t n_rays, int n, uint64_t seed, int st
   return launch_rng_fill(out, (long)n_rays, n, seed, stream_id, (long)ray_offset, (hipStream_t)stream);
 }
 
-int crnerf_render_rays_bf16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, true); }
+int crnerf_render_rays_bf16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::BF16_PAIR); }
 
 int crnerf_render_rays_bf16_fine(const crnerf_render_args* a, void* stream) {
   REQUIRE(a, "args");
@@ -288,12 +359,9 @@ int crnerf_render_rays_bf16_fine(const crnerf_render_args* a, void* stream) {
   REQUIRE(a->weights_fine, "weights_fine"); REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
   if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
     return set_error(CRNERF_ERR_CONFIG, "render_rays_bf16_fine: no in-kernel random draws in the bf16 kernels");
-  RenderArgs r;
-  r.packed_coarse = a->packed_fine; r.packed_fine = a->packed_fine; r.rays = a->rays; r.view_dir = a->view_dir;
-  r.z_coarse = a->z_coarse; r.z_steps = a->z_steps; r.u = a->u; r.u_stride = (long)a->u_stride; r.noise_coarse = nullptr; r.noise_fine = a->noise_fine;
-  r.noise_std = a->noise_std; r.use_disp = a->use_disp; r.R = (long)a->n_rays; r.Nc = a->n_samples; r.Ni = a->n_importance;
-  r.weights_coarse = a->weights_coarse; r.feature_coarse = nullptr; r.depth_coarse = nullptr;
-  r.weights_fine = a->weights_fine; r.feature_fine = a->feature_fine; r.depth_fine = a->depth_fine; r.z_fine = a->z_fine;
+  auto r = to_render_args(a);
+  r.packed_coarse = a->packed_fine;                                                   // one pack: the fine model's
+  r.noise_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr;     // no coarse pass; weights_coarse is the INPUT
   r.fine_only = 1;
   return launch_render_rays_bf16p(r, (hipStream_t)stream);
 }
@@ -308,12 +376,8 @@ int crnerf_render_rays_lean_f32(const crnerf_render_args* a, void* stream) {
   REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
   if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
     return set_error(CRNERF_ERR_CONFIG, "render_rays_lean: no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)");
-  RenderArgs r;
-  r.packed_coarse = a->packed_coarse; r.packed_fine = a->packed_fine; r.rays = a->rays; r.view_dir = a->view_dir;
-  r.z_coarse = a->z_coarse; r.z_steps = a->z_steps; r.u = a->u; r.u_stride = (long)a->u_stride; r.noise_coarse = a->noise_coarse; r.noise_fine = a->noise_fine;
-  r.noise_std = a->noise_std; r.use_disp = a->use_disp; r.R = (long)a->n_rays; r.Nc = a->n_samples; r.Ni = a->n_importance;
+  auto r = to_render_args(a);
   r.weights_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr;   // ignored, whatever the caller passed
-  r.feature_fine = a->feature_fine; r.depth_fine = a->depth_fine; r.z_fine = a->z_fine;
   r.lean = 1;
   return launch_render_rays16(r, (hipStream_t)stream);
 }
@@ -323,10 +387,7 @@ size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_act
 size_t crnerf_mlp_train_mixed_scratch_bytes(int64_t n) { return mlp_train_mixed_scratch_bytes((long)n); }
 
 int crnerf_pack_mlp_weights_mixed(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_mixed: a tensor pointer is NULL");
-  return launch_pack_mlp_gemm(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_mixed", tensors, packed, stream, launch_pack_mlp_gemm);
 }
 
 int crnerf_mlp_forward_train_mixed_f32(const float* const* tensors, const void* packed, const float* x, float* out, void* acts, int64_t n,
@@ -334,8 +395,7 @@ int crnerf_mlp_forward_train_mixed_f32(const float* const* tensors, const void* 
   if (n == 0) return 0;
   REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out"); REQUIRE(acts, "acts");
   if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_train_mixed: negative n");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "mlp_forward_train_mixed: a tensor pointer is NULL");
+  if (int rc = require_tensors("mlp_forward_train_mixed", tensors)) return rc;
   return launch_mlp_forward_train_mixed(to_tensors(tensors), packed, x, out, acts, (long)n, (hipStream_t)stream);
 }
 
@@ -344,8 +404,7 @@ int crnerf_mlp_backward_mixed_f32(const float* const* tensors, const void* packe
   if (n == 0) return 0;
   REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out"); REQUIRE(d_out, "d_out"); REQUIRE(acts, "acts");
   REQUIRE(scratch, "scratch"); REQUIRE(grads, "grads");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "mlp_backward_mixed: a tensor / gradient pointer is NULL");
+  if (!all_set2(tensors, grads, CRNERF_MLP_TENSORS)) return set_error(CRNERF_ERR_NULL, "mlp_backward_mixed: a tensor / gradient pointer is NULL");
   return launch_mlp_backward_mixed(to_tensors(tensors), packed, x, out, d_out, acts, scratch, grads, (long)n, (hipStream_t)stream);
 }
 
@@ -355,36 +414,24 @@ int crnerf_mlp_backward_mixed_ex_f32(const float* const* tensors, const void* pa
   REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed"); REQUIRE(out, "out"); REQUIRE(d_out, "d_out"); REQUIRE(acts, "acts");
   REQUIRE(scratch, "scratch"); REQUIRE(grads, "grads");
   if (acts_layout != CRNERF_MIXED_ACTS_GEMM && acts_layout != CRNERF_MIXED_ACTS_FUSED) return set_error(CRNERF_ERR_CONFIG, "mlp_backward_mixed_ex: unknown acts_layout");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "mlp_backward_mixed_ex: a tensor / gradient pointer is NULL");
+  if (!all_set2(tensors, grads, CRNERF_MLP_TENSORS)) return set_error(CRNERF_ERR_NULL, "mlp_backward_mixed_ex: a tensor / gradient pointer is NULL");
   return launch_mlp_backward_mixed(to_tensors(tensors), packed, nullptr, out, d_out, acts, scratch, grads, (long)n, (hipStream_t)stream, acts_layout);
 }
 
 int crnerf_render_rays_train_bf16(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine,
                                   void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  REQUIRE(acts_coarse, "acts_coarse"); REQUIRE(raw_coarse, "raw_coarse");
-  if (a->n_importance > 0) { REQUIRE(acts_fine, "acts_fine"); REQUIRE(raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
-  return render_rays_common(a, stream, true, acts_coarse, acts_fine, raw_coarse, raw_fine);
+  return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::BF16_PAIR);
 }
 
 int crnerf_render_rays_train_f32(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine,
                                  void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  REQUIRE(acts_coarse, "acts_coarse"); REQUIRE(raw_coarse, "raw_coarse");
-  if (a->n_importance > 0) { REQUIRE(acts_fine, "acts_fine"); REQUIRE(raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
-  return render_rays_common(a, stream, false, acts_coarse, acts_fine, raw_coarse, raw_fine);
+  return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::F32);
 }
 
 size_t crnerf_packed_mlp_t_x3_bytes(void) { return PACKEDXT_BYTES; }
 
 int crnerf_pack_mlp_weights_t_x3(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_t_x3: a tensor pointer is NULL");
-  return launch_pack_mlp_x3t(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_t_x3", tensors, packed, stream, launch_pack_mlp_x3t);
 }
 
 int crnerf_mlp_backward_x3_f32(const void* packed_t_x3, const float* x, const float* out, const float* d_out, const void* acts, void* scratch,
@@ -397,10 +444,7 @@ int crnerf_mlp_backward_x3_f32(const void* packed_t_x3, const float* x, const fl
 size_t crnerf_packed_mlp_t_h2_bytes(void) { return PACKEDHT_BYTES; }
 
 int crnerf_pack_mlp_weights_t_h2(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_t_h2: a tensor pointer is NULL");
-  return launch_pack_mlp_h2t(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_t_h2", tensors, packed, stream, launch_pack_mlp_h2t);
 }
 
 int crnerf_mlp_backward_h2_f32(const void* packed_t_h2, const void* packed_t_x3, const float* x, const float* out, const float* d_out, const void* acts,
@@ -416,35 +460,24 @@ int crnerf_mlp_backward_h2_f32(const void* packed_t_h2, const void* packed_t_x3,
 size_t crnerf_packed_mlp_x3_bytes(void) { return PACKEDX_BYTES; }
 
 int crnerf_pack_mlp_weights_x3(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_x3: a tensor pointer is NULL");
-  return launch_pack_mlp_x3(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_x3", tensors, packed, stream, launch_pack_mlp_x3);
 }
 
 int crnerf_mlp_forward_f32x3(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_f32x3: negative n");
-  return launch_mlp_forward_x3(packed, x, out, (long)n, sigma_only, (hipStream_t)stream, 0);
+  return forward_entry("mlp_forward_f32x3", packed, x, out, n, [&](long P) { return launch_mlp_forward_x3(packed, x, out, P, sigma_only, (hipStream_t)stream, 0); });
 }
 
-int crnerf_render_rays_f32x3(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, false, nullptr, nullptr, nullptr, nullptr, 1); }
+int crnerf_render_rays_f32x3(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::X3); }
 
 size_t crnerf_packed_mlp_h2_bytes(void) { return PACKEDH_BYTES; }
 
 int crnerf_pack_mlp_weights_h2(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_h2: a tensor pointer is NULL");
-  return launch_pack_mlp_h2(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_h2", tensors, packed, stream, [](const MlpTensors& t, void* p, hipStream_t st) { return launch_pack_mlp_h2(t, p, st); });
 }
 
 int crnerf_pack_mlp_weights_h2_async(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_h2_async: a tensor pointer is NULL");
-  return launch_pack_mlp_h2(to_tensors(tensors), packed, (hipStream_t)stream, false);
+  return pack_entry("pack_mlp_weights_h2_async", tensors, packed, stream,
+                    [](const MlpTensors& t, void* p, hipStream_t st) { return launch_pack_mlp_h2(t, p, st, /*check=*/false); });
 }
 
 int crnerf_pack_h2_status(const void* packed_h2, void* stream) {
@@ -453,85 +486,54 @@ int crnerf_pack_h2_status(const void* packed_h2, void* stream) {
 }
 
 int crnerf_mlp_forward_f32h2(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_f32h2: negative n");
-  return launch_mlp_forward_h2(packed, x, out, (long)n, sigma_only, (hipStream_t)stream, 0);
+  return forward_entry("mlp_forward_f32h2", packed, x, out, n, [&](long P) { return launch_mlp_forward_h2(packed, x, out, P, sigma_only, (hipStream_t)stream, 0); });
 }
 
-int crnerf_render_rays_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, false, nullptr, nullptr, nullptr, nullptr, 3); }
+int crnerf_render_rays_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::X3_REPAIR); }
 int crnerf_mlp_forward_f32x3_repair(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_f32x3_repair: negative n");
-  return launch_mlp_forward_x3(packed, x, out, (long)n, sigma_only, (hipStream_t)stream, 1);
+  return forward_entry("mlp_forward_f32x3_repair", packed, x, out, n, [&](long P) { return launch_mlp_forward_x3(packed, x, out, P, sigma_only, (hipStream_t)stream, 1); });
 }
-int crnerf_render_rays_f32h2(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, false, nullptr, nullptr, nullptr, nullptr, 2); }
+int crnerf_render_rays_f32h2(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::H2); }
 
 int crnerf_render_rays_train_f32x3(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  REQUIRE(acts_coarse, "acts_coarse"); REQUIRE(raw_coarse, "raw_coarse");
-  if (a->n_importance > 0) { REQUIRE(acts_fine, "acts_fine"); REQUIRE(raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
-  return render_rays_common(a, stream, false, acts_coarse, acts_fine, raw_coarse, raw_fine, true);
+  return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::X3);
 }
 
 int crnerf_render_rays_train_f32h2(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  REQUIRE(acts_coarse, "acts_coarse"); REQUIRE(raw_coarse, "raw_coarse");
-  if (a->n_importance > 0) { REQUIRE(acts_fine, "acts_fine"); REQUIRE(raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
-  return render_rays_common(a, stream, false, acts_coarse, acts_fine, raw_coarse, raw_fine, 2);
+  return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::H2);
 }
 
 int crnerf_render_rays_train_f32x3_repair(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  REQUIRE(acts_coarse, "acts_coarse"); REQUIRE(raw_coarse, "raw_coarse");
-  if (a->n_importance > 0) { REQUIRE(acts_fine, "acts_fine"); REQUIRE(raw_fine, "raw_fine"); REQUIRE(a->z_fine, "z_fine"); }
-  return render_rays_common(a, stream, false, acts_coarse, acts_fine, raw_coarse, raw_fine, 3);
+  return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::X3_REPAIR);
 }
 
 size_t crnerf_packed_mlp_bf16_bytes(void) { return PACKEDB_BYTES; }
 
 int crnerf_pack_mlp_weights_bf16(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_bf16: a tensor pointer is NULL");
-  return launch_pack_mlp_bf16(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_bf16", tensors, packed, stream, launch_pack_mlp_bf16);
 }
 
 int crnerf_mlp_forward_bf16(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_bf16: negative n");
-  return launch_mlp_forward_bf16p(packed, x, out, (long)n, sigma_only, (hipStream_t)stream);
+  return forward_entry("mlp_forward_bf16", packed, x, out, n, [&](long P) { return launch_mlp_forward_bf16p(packed, x, out, P, sigma_only, (hipStream_t)stream); });
 }
 
 size_t crnerf_packed_mlp_f16_bytes(void) { return PACKEDB_BYTES; }
 
 int crnerf_pack_mlp_weights_f16(const float* const* tensors, void* packed, void* stream) {
-  REQUIRE(tensors, "tensors"); REQUIRE(packed, "packed");
-  for (int i = 0; i < CRNERF_MLP_TENSORS; ++i)
-    if (!tensors[i]) return set_error(CRNERF_ERR_NULL, "pack_mlp_weights_f16: a tensor pointer is NULL");
-  return launch_pack_mlp_f16(to_tensors(tensors), packed, (hipStream_t)stream);
+  return pack_entry("pack_mlp_weights_f16", tensors, packed, stream, launch_pack_mlp_f16);
 }
 
 int crnerf_mlp_forward_f16(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
-  if (n == 0) return 0;
-  REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
-  if (n < 0) return set_error(CRNERF_ERR_SHAPE, "mlp_forward_f16: negative n");
-  return launch_mlp_forward_f16p(packed, x, out, (long)n, sigma_only, (hipStream_t)stream);
+  return forward_entry("mlp_forward_f16", packed, x, out, n, [&](long P) { return launch_mlp_forward_f16p(packed, x, out, P, sigma_only, (hipStream_t)stream); });
 }
 
-int crnerf_render_rays_f16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, true, nullptr, nullptr, nullptr, nullptr, 0, true); }
+int crnerf_render_rays_f16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::F16_PAIR); }
 
 size_t crnerf_encoder_workspace_bytes(int H, int W) { return encoder_workspace_bytes(H, W); }
 
 int crnerf_encoder_forward_f32(const float* image, int H, int W, const float* const* weights, void* workspace, float* out, void* stream) {
   REQUIRE(image, "image"); REQUIRE(weights, "weights"); REQUIRE(workspace, "workspace"); REQUIRE(out, "out");
-  for (int i = 0; i < CRNERF_ENCODER_TENSORS; ++i)
-    if (!weights[i]) return set_error(CRNERF_ERR_NULL, "encoder_forward: a weight pointer is NULL");
+  if (!all_set(weights, CRNERF_ENCODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "encoder_forward: a weight pointer is NULL");
   return launch_encoder_forward(image, H, W, weights, workspace, out, (hipStream_t)stream);
 }
 
@@ -560,8 +562,7 @@ int crnerf_crossray_chansum_f32(const float* x, int64_t HW, float* sum64, void* 
 int crnerf_crossray_gram_f32(const float* x, int64_t HW, const float* mean64, const float* const* cnn, float* gram_sum,
                              void* workspace, void* stream) {
   REQUIRE(x, "x"); REQUIRE(mean64, "mean64"); REQUIRE(cnn, "cnn"); REQUIRE(gram_sum, "gram_sum"); REQUIRE(workspace, "workspace");
-  for (int i = 0; i < 6; ++i)
-    if (!cnn[i]) return set_error(CRNERF_ERR_NULL, "crossray_gram: a cnn tensor pointer is NULL");
+  if (!all_set(cnn, 6)) return set_error(CRNERF_ERR_NULL, "crossray_gram: a cnn tensor pointer is NULL");
   CnnTensors w{cnn[0], cnn[1], cnn[2], cnn[3], cnn[4], cnn[5]};
   return launch_crossray_gram(x, (long)HW, mean64, w, gram_sum, (float*)workspace, (hipStream_t)stream);
 }
@@ -574,8 +575,7 @@ int crnerf_crossray_matrix_f32(const float* gram_sum, double count, const float*
 int crnerf_crossray_fold_f32(const float* s_matrix, const float* c_matrix, const float* c_mean64, const float* s_mean64,
                              const float* const* lin, float* affine, void* stream) {
   REQUIRE(lin, "lin"); REQUIRE(affine, "affine");
-  for (int i = 0; i < 6; ++i)
-    if (!lin[i]) return set_error(CRNERF_ERR_NULL, "crossray_fold: a tensor pointer is NULL");
+  if (!all_set(lin, 6)) return null_tensor("crossray_fold");
   if (s_matrix) { REQUIRE(c_matrix, "c_matrix"); REQUIRE(c_mean64, "c_mean64"); REQUIRE(s_mean64, "s_mean64"); }
   FoldTensors w{lin[0], lin[1], lin[2], lin[3], lin[4], lin[5]};
   return launch_crossray_fold(s_matrix, c_matrix, c_mean64, s_mean64, w, affine, (hipStream_t)stream);
@@ -586,14 +586,8 @@ int crnerf_crossray_decode_f32(const float* content, int64_t HW, const float* st
   if (HW == 0) return 0;
   REQUIRE(content, "content"); REQUIRE(w, "weights"); REQUIRE(workspace, "workspace"); REQUIRE(rgb, "rgb");
   if (HW < 0 || HWs < 0) return set_error(CRNERF_ERR_SHAPE, "crossray_decode: negative size");
-  for (int i = 0; i < CRNERF_DECODER_TENSORS; ++i)
-    if (!w[i]) return set_error(CRNERF_ERR_NULL, "crossray_decode: a weight pointer is NULL");
-  DecodeArgs d;
-  d.content = content; d.HW = (long)HW; d.style = style; d.HWs = (long)HWs;
-  d.snet = CnnTensors{w[0], w[1], w[2], w[3], w[4], w[5]}; d.snet_fc_w = w[6]; d.snet_fc_b = w[7];
-  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
-  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
-  d.workspace = workspace; d.rgb = rgb; d.plane_stride = (long)plane_stride;
+  if (!all_set(w, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_decode: a weight pointer is NULL");
+  const auto d = to_decode_args(content, HW, style, HWs, w, workspace, rgb, plane_stride);
   return launch_crossray_decode(d, (hipStream_t)stream);
 }
 
@@ -604,14 +598,8 @@ int crnerf_crossray_decode_sharded_f32(const float* content, int64_t HW_local, c
   if (HW_local < 0 || phase < 0 || phase > 2) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_sharded: bad size or phase");
   if (HW_local > 0) REQUIRE(content, "content");
   if (phase == 2 && HW_local > 0) REQUIRE(rgb, "rgb");
-  for (int i = 0; i < CRNERF_DECODER_TENSORS; ++i)
-    if (!w[i]) return set_error(CRNERF_ERR_NULL, "crossray_decode_sharded: a weight pointer is NULL");
-  DecodeArgs d;
-  d.content = content; d.HW = (long)HW_local; d.style = style; d.HWs = (long)HWs;
-  d.snet = CnnTensors{w[0], w[1], w[2], w[3], w[4], w[5]}; d.snet_fc_w = w[6]; d.snet_fc_b = w[7];
-  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
-  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
-  d.workspace = workspace; d.rgb = rgb; d.plane_stride = (long)plane_stride;
+  if (!all_set(w, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_decode_sharded: a weight pointer is NULL");
+  const auto d = to_decode_args(content, HW_local, style, HWs, w, workspace, rgb, plane_stride);
   return launch_crossray_decode_sharded(d, phase, xchg, count_global, (hipStream_t)stream);
 }
 
@@ -623,14 +611,8 @@ int crnerf_crossray_decode_backward_f32(const float* content, int64_t HW, const 
   REQUIRE(content, "content"); REQUIRE(style, "style"); REQUIRE(w, "weights"); REQUIRE(d_rgb, "d_rgb"); REQUIRE(workspace, "workspace");
   REQUIRE(d_content, "d_content"); REQUIRE(d_style, "d_style"); REQUIRE(grads, "grads");
   if (HW <= 0 || HWs <= 0) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_backward: empty grid");
-  for (int i = 0; i < CRNERF_DECODER_TENSORS; ++i)
-    if (!w[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "crossray_decode_backward: a weight or gradient pointer is NULL");
-  DecodeArgs d;
-  d.content = content; d.HW = (long)HW; d.style = style; d.HWs = (long)HWs;
-  d.snet = CnnTensors{w[0], w[1], w[2], w[3], w[4], w[5]}; d.snet_fc_w = w[6]; d.snet_fc_b = w[7];
-  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
-  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
-  d.workspace = nullptr; d.rgb = nullptr; d.plane_stride = 0;
+  if (!all_set2(w, grads, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_decode_backward: a weight or gradient pointer is NULL");
+  const auto d = to_decode_args(content, HW, style, HWs, w);     // no workspace, rgb or plane_stride: the backward has its own
   return launch_crossray_decode_backward(d, d_rgb, (long)d_plane_stride, (float*)workspace, d_content, d_style, grads, (hipStream_t)stream);
 }
 
@@ -641,14 +623,8 @@ int crnerf_crossray_decode_backward_sharded_f32(const float* content, int64_t HW
   REQUIRE(d_content, "d_content"); REQUIRE(d_style, "d_style"); REQUIRE(grads, "grads"); REQUIRE(fwd_xchg, "fwd_xchg"); REQUIRE(xb, "xb");
   if (HW <= 0 || HWs <= 0) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_backward_sharded: empty grid (every rank must hold pixels)");
   if (phase < 0 || phase > 2) return set_error(CRNERF_ERR_CONFIG, "crossray_decode_backward_sharded: phase must be 0, 1 or 2");
-  for (int i = 0; i < CRNERF_DECODER_TENSORS; ++i)
-    if (!w[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "crossray_decode_backward_sharded: a weight or gradient pointer is NULL");
-  DecodeArgs d;
-  d.content = content; d.HW = (long)HW; d.style = style; d.HWs = (long)HWs;
-  d.snet = CnnTensors{w[0], w[1], w[2], w[3], w[4], w[5]}; d.snet_fc_w = w[6]; d.snet_fc_b = w[7];
-  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
-  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
-  d.workspace = nullptr; d.rgb = nullptr; d.plane_stride = 0;
+  if (!all_set2(w, grads, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_decode_backward_sharded: a weight or gradient pointer is NULL");
+  const auto d = to_decode_args(content, HW, style, HWs, w);     // no workspace, rgb or plane_stride: the backward has its own
   return launch_crossray_decode_backward_sharded(d, d_rgb, (long)d_plane_stride, (float*)workspace, d_content, d_style, grads, phase, fwd_xchg, count_global, xb,
                                                  (hipStream_t)stream);
 }
@@ -678,8 +654,7 @@ size_t crnerf_encoder_train_scratch_bytes(int H, int W) { return encoder_train_s
 
 int crnerf_encoder_forward_train_f32(const float* image, int H, int W, const float* const* weights, void* saved, float* out, void* stream) {
   REQUIRE(image, "image"); REQUIRE(weights, "weights"); REQUIRE(saved, "saved"); REQUIRE(out, "out");
-  for (int i = 0; i < CRNERF_ENCODER_TENSORS; ++i)
-    if (!weights[i]) return set_error(CRNERF_ERR_NULL, "encoder_forward_train: a weight pointer is NULL");
+  if (!all_set(weights, CRNERF_ENCODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "encoder_forward_train: a weight pointer is NULL");
   return launch_encoder_forward_train(image, H, W, weights, saved, out, (hipStream_t)stream);
 }
 
@@ -689,8 +664,7 @@ size_t crnerf_encoder_train_band_scratch_bytes(int H, int W, int n_out_rows) { r
 int crnerf_encoder_forward_train_band_f32(const float* image_rows, int H, int W, int H_image, int row0, int o0, int o1, const float* const* weights, void* saved,
                                           float* out, void* stream) {
   REQUIRE(image_rows, "image_rows"); REQUIRE(weights, "weights"); REQUIRE(saved, "saved"); REQUIRE(out, "out");
-  for (int i = 0; i < CRNERF_ENCODER_TENSORS; ++i)
-    if (!weights[i]) return set_error(CRNERF_ERR_NULL, "encoder_forward_train_band: a weight pointer is NULL");
+  if (!all_set(weights, CRNERF_ENCODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "encoder_forward_train_band: a weight pointer is NULL");
   return launch_encoder_forward_train_band(image_rows, H, W, H_image, row0, o0, o1, weights, saved, out, (hipStream_t)stream);
 }
 
@@ -698,8 +672,7 @@ int crnerf_encoder_backward_band_f32(int H, int W, int H_image, int row0, int o0
                                      const float* d_out, void* scratch, float* const* grads, float* d_image_rows, void* stream) {
   REQUIRE(weights, "weights"); REQUIRE(saved, "saved"); REQUIRE(out, "out"); REQUIRE(d_out, "d_out"); REQUIRE(scratch, "scratch"); REQUIRE(grads, "grads");
   if (H < 8 || W < 8) return set_error(CRNERF_ERR_SHAPE, "encoder_backward_band: band must be at least 8x8");
-  for (int i = 0; i < CRNERF_ENCODER_TENSORS; ++i)
-    if (!weights[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "encoder_backward_band: a weight or gradient pointer is NULL");
+  if (!all_set2(weights, grads, CRNERF_ENCODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "encoder_backward_band: a weight or gradient pointer is NULL");
   return launch_encoder_backward_band(H, W, H_image, row0, o0, o1, weights, saved, out, d_out, scratch, grads, d_image_rows, (hipStream_t)stream);
 }
 
@@ -707,8 +680,7 @@ int crnerf_encoder_backward_f32(int H, int W, const float* const* weights, const
                                 float* const* grads, float* d_image, void* stream) {
   REQUIRE(weights, "weights"); REQUIRE(saved, "saved"); REQUIRE(out, "out"); REQUIRE(d_out, "d_out"); REQUIRE(scratch, "scratch"); REQUIRE(grads, "grads");
   if (H < 8 || W < 8) return set_error(CRNERF_ERR_SHAPE, "encoder_backward: image must be at least 8x8");
-  for (int i = 0; i < CRNERF_ENCODER_TENSORS; ++i)
-    if (!weights[i] || !grads[i]) return set_error(CRNERF_ERR_NULL, "encoder_backward: a weight or gradient pointer is NULL");
+  if (!all_set2(weights, grads, CRNERF_ENCODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "encoder_backward: a weight or gradient pointer is NULL");
   return launch_encoder_backward(H, W, weights, saved, out, d_out, scratch, grads, d_image, (hipStream_t)stream);
 }
 
@@ -984,8 +956,7 @@ size_t crnerf_cgnet_arena_bytes(int32_t cin, int32_t H, int32_t W) {
 static int cgnet_args(const char* who, int32_t cin, int32_t H, int32_t W, const float* const* params) {
   if (cin <= 0 || H < 1 || W < 1 || (long)H * W > (1L << 24)) return set_error(CRNERF_ERR_SHAPE, "cgnet: image must be cin >= 1 channels of 1 ... 2^24 pixels");
   REQUIRE(params, "params");
-  for (int i = 0; i < CGNET_PARAMS; ++i)
-    if (!params[i]) return set_error(CRNERF_ERR_NULL, who);
+  if (!all_set(params, CGNET_PARAMS)) return set_error(CRNERF_ERR_NULL, who);
   return 0;
 }
 
@@ -994,8 +965,7 @@ int crnerf_cgnet_forward_train_f32(const float* image, int32_t cin, int32_t H, i
                                    float* mask, void* stream) {
   REQUIRE(image, "image"); REQUIRE(saved, "saved"); REQUIRE(mask, "mask"); REQUIRE(running_mean, "running_mean"); REQUIRE(running_var, "running_var");
   if (int rc = cgnet_args("cgnet_forward_train: a params[] entry is NULL", cin, H, W, params)) return rc;
-  for (int i = 0; i < CGNET_BNS; ++i)
-    if (!running_mean[i] || !running_var[i]) return set_error(CRNERF_ERR_NULL, "cgnet_forward_train: a running_mean / running_var entry is NULL");
+  if (!all_set2(running_mean, running_var, CGNET_BNS)) return set_error(CRNERF_ERR_NULL, "cgnet_forward_train: a running_mean / running_var entry is NULL");
   if (!(eps > 0.0f) || !(momentum >= 0.0f && momentum <= 1.0f)) return set_error(CRNERF_ERR_CONFIG, "cgnet_forward_train: eps must be positive and momentum in [0, 1]");
   const CgNetArgs a{cin, H, W, params, running_mean, running_var, (long long* const*)num_batches_tracked, momentum, eps};
   return launch_cgnet_forward_train(a, image, (float*)saved, mask, (hipStream_t)stream);
@@ -1005,8 +975,7 @@ int crnerf_cgnet_backward_f32(const float* image, int32_t cin, int32_t H, int32_
                               const float* d_mask, void* scratch, float* const* grads, void* stream) {
   REQUIRE(image, "image"); REQUIRE(saved, "saved"); REQUIRE(mask, "mask"); REQUIRE(d_mask, "d_mask"); REQUIRE(scratch, "scratch"); REQUIRE(grads, "grads");
   if (int rc = cgnet_args("cgnet_backward: a params[] entry is NULL", cin, H, W, params)) return rc;
-  for (int i = 0; i < CGNET_PARAMS; ++i)
-    if (!grads[i]) return set_error(CRNERF_ERR_NULL, "cgnet_backward: a grads[] entry is NULL");
+  if (!all_set(grads, CGNET_PARAMS)) return set_error(CRNERF_ERR_NULL, "cgnet_backward: a grads[] entry is NULL");
   const CgNetArgs a{cin, H, W, params, nullptr, nullptr, nullptr, 0.0f, 1e-3f};
   return launch_cgnet_backward(a, image, (const float*)saved, mask, d_mask, (float*)scratch, grads, (hipStream_t)stream);
 }

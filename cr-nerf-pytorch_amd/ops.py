@@ -458,6 +458,26 @@ def sample_pdf_merge(z_coarse, weights_coarse, n_importance, u=None, return_samp
     return (zs, smp) if return_samples else zs
 
 
+def _render_args(rays, inputs, noise_std, use_disp, Nc, Ni, out):
+    """The crnerf_render_args fields every render entry fills alike: rays, the optional input tensors `inputs` ({field: tensor or None}, made fp32 and
+    contiguous), u_stride, noise_std, use_disp, the three counts and the pointer of every output present in `out`.  Returns the struct and the list of
+    converted inputs: the struct holds raw pointers, so whoever keeps it keeps that list (and rays, the packs and `out`) alive."""
+    keep = [t if t is None else _f32c(t, n) for n, t in inputs.items()]
+    a = _lib.RenderArgs()
+    a.rays = rays.data_ptr()
+    for field, t in zip(inputs, keep):
+        setattr(a, field, t.data_ptr() if t is not None else None)
+    u = inputs["u"]
+    a.u_stride = 0 if (u is None or u.dim() == 1) else Ni
+    a.noise_std = float(noise_std)
+    a.use_disp = int(bool(use_disp))
+    a.n_rays, a.n_samples, a.n_importance = rays.shape[0], Nc, Ni
+    for k in ("weights_coarse", "feature_coarse", "depth_coarse", "weights_fine", "feature_fine", "depth_fine", "z_fine"):
+        if k in out:
+            setattr(a, k, out[k].data_ptr())
+    return a, keep
+
+
 def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
                 noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, precision="f32", train=False, launcher=False, rng=None,
                 repair_x3=None, lean=False):
@@ -528,20 +548,10 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
         out["z_fine"] = new(R, Nc + Ni)
     if R == 0:
         return out
-    keep = [t if t is None else _f32c(t, n) for t, n in ((view_dir, "view_dir"), (z_coarse, "z_coarse"), (z_steps, "z_steps"), (u, "u"),
-                                                         (noise_coarse, "noise_coarse"), (noise_fine, "noise_fine"))]
-    a = _lib.RenderArgs()
+    a, keep = _render_args(rays, {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_coarse": noise_coarse,
+                                  "noise_fine": noise_fine}, noise_std, use_disp, Nc, Ni, out)
     a.packed_coarse = packed_coarse.data_ptr()
     a.packed_fine = packed_fine.data_ptr() if packed_fine is not None else None
-    a.rays = rays.data_ptr()
-    a.u_stride = 0 if (u is None or u.dim() == 1) else Ni
-    for field, t in zip(("view_dir", "z_coarse", "z_steps", "u", "noise_coarse", "noise_fine"), keep):
-        setattr(a, field, t.data_ptr() if t is not None else None)
-    a.noise_std = float(noise_std)
-    a.use_disp = int(bool(use_disp))
-    a.n_rays, a.n_samples, a.n_importance = R, Nc, Ni
-    for k in ("weights_coarse", "feature_coarse", "depth_coarse", "weights_fine", "feature_fine", "depth_fine", "z_fine"):
-        setattr(a, k, out[k].data_ptr() if k in out else None)
     if rng is not None:
         if name == "bf16":
             raise ValueError("crnerf_amd: in-kernel random draws exist in the fp32 kernels only")
@@ -604,19 +614,10 @@ def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_i
         out["z_fine"] = new(R, Nc + Ni)
     if R == 0:
         return out
-    keep = [t if t is None else _f32c(t, n) for t, n in ((view_dir, "view_dir"), (z_coarse, "z_coarse"), (z_steps, "z_steps"), (u, "u"), (noise_fine, "noise_fine"))]
-    a = _lib.RenderArgs()
+    a, keep = _render_args(rays, {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_fine": noise_fine}, noise_std, use_disp,
+                           Nc, Ni, out)
     a.packed_fine = packed_fine_bf16.data_ptr()
-    a.rays = rays.data_ptr()
-    a.u_stride = 0 if (u is None or u.dim() == 1) else Ni
-    for field, t in zip(("view_dir", "z_coarse", "z_steps", "u", "noise_fine"), keep):
-        setattr(a, field, t.data_ptr() if t is not None else None)
-    a.noise_std = float(noise_std)
-    a.use_disp = int(bool(use_disp))
-    a.n_rays, a.n_samples, a.n_importance = R, Nc, Ni
     a.weights_coarse = weights_coarse.data_ptr()                    # INPUT of this entry point
-    for k in ("weights_fine", "feature_fine", "depth_fine", "z_fine"):
-        setattr(a, k, out[k].data_ptr() if k in out else None)
     _lib.check(lib.crnerf_render_rays_bf16_fine(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_bf16_fine")
     return out
 

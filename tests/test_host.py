@@ -26,8 +26,24 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(crnerf_[a-z0-9_]+)\s*\(", text)))
 
 
+def header_prototypes():
+    """{symbol: (return type, number of parameters)} of every prototype of include/crnerf.h."""
+    text = open(os.path.join(ROOT, "include", "crnerf.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(crnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
+    return {name: ("".join(ret.split()), 0 if params.strip() == "void" else params.count(",") + 1) for ret, name, params in protos}
+
+
 def test_header_declares_what_the_binding_expects():
     assert header_symbols() == sorted(_lib.EXPORTS)
+    # the signature table row by row: as many argtypes as the prototype has parameters, and its return type
+    protos = header_prototypes()
+    assert sorted(protos) == sorted(_lib.SIGNATURES) and len(protos) == 124
+    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "constchar*": ctypes.c_char_p}
+    for name, (ret, n_params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert len(argtypes) == n_params, "%s: %d argtypes for %d parameters" % (name, len(argtypes), n_params)
+        assert restype is restypes[ret], "%s returns %s, the table says %s" % (name, ret, restype)
 
 
 def test_library_exports_every_declared_symbol():
