@@ -97,6 +97,23 @@ LANCZOS_TILE_H, LANCZOS_TILE_W, LANCZOS_VBLOCK = 8, 32, 256     # CRNERF_LANCZOS
 LANCZOS_OUT = {"u8": 0, "rows": 1, "chw": 2, "chw_signed": 3}   # CRNERF_LANCZOS_OUT_*
 
 
+RGBA_TILE_H, RGBA_TILE_W, RGBA_VBLOCK = 8, 32, 256     # CRNERF_RGBA_TILE_H / _W / _VBLOCK (include/crnerf_blender.h)
+RGBA_MAX_RECTS = 16                                     # CRNERF_RGBA_MAX_RECTS
+RGBA_OUT = {"u8": 0, "rows": 1, "chw": 2, "chw_signed": 3}      # CRNERF_RGBA_OUT_*
+
+
+class RgbaPrepareArgs(ctypes.Structure):
+    """struct crnerf_rgba_prepare_args (include/crnerf_blender.h)."""
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+        ("kx", ctypes.c_void_p), ("bounds_x", ctypes.c_void_p), ("ky", ctypes.c_void_p), ("bounds_y", ctypes.c_void_p),
+        ("ksize_x", ctypes.c_int32), ("ksize_y", ctypes.c_int32), ("n_rects", ctypes.c_int32), ("out_mode", ctypes.c_int32),
+        ("rects", ctypes.c_void_p), ("colors", ctypes.c_void_p),          # HOST arrays
+        ("lut", ctypes.c_void_p),
+        ("dst", ctypes.c_void_p), ("valid_mask", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+    ]
+
+
 class ConvGeom(ctypes.Structure):
     """struct crnerf_conv_geom."""
     _fields_ = [(n, ctypes.c_int32) for n in ("cin", "cout", "H", "W", "k", "stride", "pad", "dil", "depthwise")]
@@ -236,6 +253,14 @@ SIGNATURES = {
     "crnerf_scene_bounds_f64": (i32, [vp, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp]),
 }
 EXPORTS = list(SIGNATURES)
+# One row per symbol of the companion header include/crnerf_blender.h (the Blender dataset path), in the same spelling and bound by the
+# same loader; tests/test_blender_host.py holds it to that header's prototypes.  Folding the headers moves these rows to the end of SIGNATURES.
+BLENDER_SIGNATURES = {
+    "crnerf_rgba_prepare_workspace_bytes": (usz, [i32, i32, i32, i32]),
+    "crnerf_rgba_prepare_u8": (i32, [ctypes.POINTER(RgbaPrepareArgs), vp]),
+    "crnerf_grid_sample_batch_round_f32": (i32, [ctypes.POINTER(BatchArgs), vp]),
+    "crnerf_generate_rays_fmanorm_f32": (i32, [hf, hf, i32, i32, f32, f32, vp, vp]),
+}
 
 
 _lib = None
@@ -255,8 +280,8 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h
+        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()):
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/crnerf.h"
+#include "../../include/crnerf_blender.h"
 #include "crossray.h"
 #include "kernels.h"
 #include "layout.h"
@@ -554,6 +555,12 @@ int crnerf_generate_rays_f32(const float* intrinsics_host, const float* c2w_host
   return launch_generate_rays(intrinsics_host, c2w_host, H, W, near, far, rays, (hipStream_t)stream);
 }
 
+int crnerf_generate_rays_fmanorm_f32(const float* intrinsics_host, const float* c2w_host, int32_t H, int32_t W, float near, float far, float* rays,
+                                     void* stream) {
+  REQUIRE(intrinsics_host, "intrinsics"); REQUIRE(c2w_host, "c2w"); REQUIRE(rays, "rays");
+  return launch_generate_rays_fmanorm(intrinsics_host, c2w_host, H, W, near, far, rays, (hipStream_t)stream);
+}
+
 int crnerf_crossray_chansum_f32(const float* x, int64_t HW, float* sum64, void* workspace, void* stream) {
   REQUIRE(x, "x"); REQUIRE(sum64, "sum64"); REQUIRE(workspace, "workspace");
   return launch_crossray_chansum(x, (long)HW, sum64, (float*)workspace, (hipStream_t)stream);
@@ -728,7 +735,8 @@ int crnerf_loss_backward_f32(const crnerf_loss_args* a, const float* upstream, c
   return launch_loss_backward(k, sc, upstream, kg, (hipStream_t)stream);
 }
 
-int crnerf_grid_sample_batch_f32(const crnerf_batch_args* a, void* stream) {
+// both gathers: the checks, then launch(BatchArgs, hipStream_t)
+static int grid_batch_entry(const crnerf_batch_args* a, void* stream, int (*launch)(const BatchArgs&, hipStream_t)) {
   REQUIRE(a, "args");
   if (a->side <= 0) return 0;
   REQUIRE(a->all_rays, "all_rays"); REQUIRE(a->all_rgbs, "all_rgbs"); REQUIRE(a->w_lin, "w_lin"); REQUIRE(a->h_lin, "h_lin");
@@ -736,8 +744,11 @@ int crnerf_grid_sample_batch_f32(const crnerf_batch_args* a, void* stream) {
   if (a->img_w <= 0 || a->img_h <= 0 || a->ray_stride < 9) return set_error(CRNERF_ERR_SHAPE, "grid_sample_batch: bad image size or ray_stride < 9");
   BatchArgs k{a->all_rays, (long)a->ray_stride, a->all_rgbs, (long)a->row_offset, a->img_w, a->img_h, a->side, a->w_lin, a->h_lin,
               a->scale, a->h_offset, a->w_offset, a->rays, (long*)a->ts, a->rgbs, (long*)a->rgb_idx, a->uv_sample};
-  return launch_grid_batch(k, (hipStream_t)stream);
+  return launch(k, (hipStream_t)stream);
 }
+
+int crnerf_grid_sample_batch_f32(const crnerf_batch_args* a, void* stream) { return grid_batch_entry(a, stream, launch_grid_batch); }
+int crnerf_grid_sample_batch_round_f32(const crnerf_batch_args* a, void* stream) { return grid_batch_entry(a, stream, launch_grid_batch_round); }
 
 int crnerf_adam_max_tensors(void) { return ADAM_MAX_TENSORS; }
 
@@ -829,6 +840,50 @@ int crnerf_lanczos_resize_u8(const uint8_t* src, int32_t H, int32_t W, int32_t w
   if (!lanczos_fits(H, W, w, h))
     return set_error(CRNERF_ERR_SHAPE, "lanczos_resize: image over 2^31 bytes or 65,535 output rows, or a horizontal downscale whose tile does not fit the LDS (above ~32x)");
   return launch_lanczos_resize(src, H, W, w, h, kx, bounds_x, ksize_x, ky, bounds_y, ksize_y, out_mode, dst, workspace, (hipStream_t)stream);
+}
+
+static_assert(RGBA_TILE_H == CRNERF_RGBA_TILE_H && RGBA_TILE_W == CRNERF_RGBA_TILE_W && RGBA_VBLOCK == CRNERF_RGBA_VBLOCK && RGBA_MAX_RECTS == CRNERF_RGBA_MAX_RECTS,
+              "rgba tiles: kernels.h vs crnerf_blender.h");
+static_assert(RGBA_U8 == CRNERF_RGBA_OUT_U8 && RGBA_ROWS == CRNERF_RGBA_OUT_ROWS && RGBA_CHW == CRNERF_RGBA_OUT_CHW && RGBA_CHW_SIGNED == CRNERF_RGBA_OUT_CHW_SIGNED,
+              "rgba output modes: kernels.h vs crnerf_blender.h");
+
+size_t crnerf_rgba_prepare_workspace_bytes(int32_t H, int32_t W, int32_t w, int32_t h) {
+  if (H < 1 || W < 1 || w < 1 || h < 1) return 0;
+  return rgba_workspace_bytes(H, W, w, h);
+}
+
+int crnerf_rgba_prepare_u8(const crnerf_rgba_prepare_args* a, void* stream) {
+  static const char who[] = "rgba_prepare";
+  REQUIRE(a, "args"); REQUIRE(a->src, "src"); REQUIRE(a->dst, "dst");
+  if (a->H < 1 || a->W < 1 || a->w < 1 || a->h < 1) return fail(CRNERF_ERR_SHAPE, who, "H, W, w and h must be positive");
+  if (a->out_mode < CRNERF_RGBA_OUT_U8 || a->out_mode > CRNERF_RGBA_OUT_CHW_SIGNED) return fail(CRNERF_ERR_CONFIG, who, "unknown output mode");
+  if (a->w != a->W) {
+    REQUIRE(a->kx, "kx"); REQUIRE(a->bounds_x, "bounds_x");
+    if (a->ksize_x != lanczos_ksize(a->W, a->w)) return fail(CRNERF_ERR_CONFIG, who, "ksize_x is not the kernel size of W -> w");
+    if ((uintptr_t)a->kx & 15) return fail(CRNERF_ERR_SHAPE, who, "kx must be 16-byte aligned");
+  }
+  if (a->h != a->H) {
+    REQUIRE(a->ky, "ky"); REQUIRE(a->bounds_y, "bounds_y");
+    if (a->ksize_y != lanczos_ksize(a->H, a->h)) return fail(CRNERF_ERR_CONFIG, who, "ksize_y is not the kernel size of H -> h");
+  }
+  if (a->n_rects < 0 || a->n_rects > CRNERF_RGBA_MAX_RECTS) return fail(CRNERF_ERR_SHAPE, who, "n_rects outside 0 ... CRNERF_RGBA_MAX_RECTS");
+  if (a->n_rects > 0) {
+    REQUIRE(a->rects, "rects"); REQUIRE(a->colors, "colors");
+    for (int i = 0; i < a->n_rects; ++i)
+      if (a->rects[4 * i + 2] < a->rects[4 * i] || a->rects[4 * i + 3] < a->rects[4 * i + 1])
+        return fail(CRNERF_ERR_SHAPE, who, "a rectangle with x1 < x0 or y1 < y0");
+  }
+  if ((uintptr_t)a->src & 3) return fail(CRNERF_ERR_SHAPE, who, "src must be 4-byte aligned");
+  if (a->out_mode == CRNERF_RGBA_OUT_U8 && ((uintptr_t)a->dst & 3)) return fail(CRNERF_ERR_SHAPE, who, "a uint8 dst must be 4-byte aligned");
+  if (a->w != a->W && a->h != a->H) {
+    REQUIRE(a->workspace, "workspace");
+    if ((uintptr_t)a->workspace & 3) return fail(CRNERF_ERR_SHAPE, who, "workspace must be 4-byte aligned");
+  }
+  if (!rgba_fits(a->H, a->W, a->w, a->h))
+    return fail(CRNERF_ERR_SHAPE, who, "image over 2^31 bytes or 65,535 output rows, or a horizontal downscale whose tile does not fit the LDS (above ~33x)");
+  const RgbaPrepare k{a->src, a->H, a->W, a->w, a->h, a->kx, a->bounds_x, a->ksize_x, a->ky, a->bounds_y, a->ksize_y, a->n_rects, a->rects, a->colors,
+                      a->lut, a->out_mode, a->dst, a->valid_mask, a->workspace};
+  return launch_rgba_prepare(k, (hipStream_t)stream);
 }
 
 // a percentile argument the comparisons below may be trusted with: not NaN, not infinite (this unit is compiled with -fno-honor-nans)

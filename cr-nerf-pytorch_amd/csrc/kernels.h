@@ -64,6 +64,8 @@ int launch_wgrad_reduce(const float* partial, int nchunk, int M, int N, float* d
 int launch_ray_directions(float fx, float fy, float cx, float cy, int H, int W, float* dirs, hipStream_t stream);
 int launch_rays_from_directions(const float* dirs, const float* c2w_host, long n, float* rays_o, float* rays_d, hipStream_t stream);
 int launch_generate_rays(const float* intr4_host, const float* c2w_host, int H, int W, float near, float far, float* rays, hipStream_t stream);
+// the same rays with the direction's squared norm accumulated by fma (the Blender dataset's, pinned to the reference bit for bit)
+int launch_generate_rays_fmanorm(const float* intr4_host, const float* c2w_host, int H, int W, float near, float far, float* rays, hipStream_t stream);
 size_t encoder_workspace_bytes(int H, int W);
 int launch_encoder_forward(const float* img, int H, int W, const float* const* w, void* workspace, float* out, hipStream_t st);
 // dst[m*ldc + n] = sum_p D[p][m] * A[p][n] (and db[m] = sum_p D[p][m] when db != null); ws: wgrad_workspace_floats()
@@ -233,6 +235,7 @@ struct BatchArgs {
   float* rays; long* ts; float* rgbs; long* rgb_idx; float* uv;
 };
 int launch_grid_batch(const BatchArgs& a, hipStream_t stream);
+int launch_grid_batch_round(const BatchArgs& a, hipStream_t stream);   // the same gather with rintf for floorf (the Blender batcher's .round())
 constexpr int ADAM_MAX_TENSORS = 448;             // gradient pointers ride in the kernel arguments (3.5 KB of the 4 KB)
 constexpr int ADAM_BLOCK_ELEMS = 4096;            // elements one workgroup updates
 struct AdamHyper { float step_size, beta1, beta2, eps, weight_decay, bias_correction2_sqrt; };
@@ -273,6 +276,23 @@ size_t lanczos_workspace_bytes(int H, int W, int w, int h);
 bool lanczos_fits(int H, int W, int w, int h);            // sizes, grid and the horizontal pass's LDS within one launch's limits
 int launch_lanczos_resize(const uint8_t* src, int H, int W, int w, int h, const int* kx, const int* bx, int ksize_x, const int* ky, const int* by,
                           int ksize_y, int mode, void* dst, void* workspace, hipStream_t stream);
+
+// ---- RGBA preparation (rgbaprep.hip): occluders + colour table, Pillow's RGBA (premultiplied) LANCZOS resize, white blend in the store
+constexpr int RGBA_TILE_H = 8, RGBA_TILE_W = 32;          // rows x output columns of one workgroup of the horizontal pass (CRNERF_RGBA_TILE_H / _W)
+constexpr int RGBA_VBLOCK = 256;                          // pixels (dwords) of one output row one workgroup of the vertical pass writes (CRNERF_RGBA_VBLOCK)
+constexpr int RGBA_MAX_RECTS = 16;                        // CRNERF_RGBA_MAX_RECTS
+enum { RGBA_U8 = 0, RGBA_ROWS = 1, RGBA_CHW = 2, RGBA_CHW_SIGNED = 3 };   // CRNERF_RGBA_OUT_*
+struct RgbaPrepare {
+  const uint8_t* src; int H, W, w, h;
+  const int* kx; const int* bx; int ksize_x;
+  const int* ky; const int* by; int ksize_y;
+  int n_rects; const int* rects; const uint8_t* colors;   // HOST arrays [n, 4] inclusive (x0, y0, x1, y1) and [n, 3]
+  const uint8_t* lut;                                     // device [3, 256] or null
+  int mode; void* dst; uint8_t* valid; void* workspace;
+};
+size_t rgba_workspace_bytes(int H, int W, int w, int h);
+bool rgba_fits(int H, int W, int w, int h);               // sizes, grid and the horizontal pass's LDS within one launch's limits
+int launch_rgba_prepare(const RgbaPrepare& a, hipStream_t stream);
 
 // ---- scene bounds (scenebounds.hip): per image, two percentiles of the camera-space depth of the sparse model's points in front of it
 // rows: [N,4] = row 2 of every world-to-camera matrix; f_lo / f_hi: the percentiles as fractions in [0, 1]

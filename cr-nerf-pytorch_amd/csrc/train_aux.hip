@@ -136,6 +136,8 @@ int launch_loss_backward(const LossArgs& a, const LossScales& sc, const float* u
 
 // ---------------------------------------------------------------- grid-sample batcher
 // sample n = j * side + i  <->  lattice node (i, j): w from w_lin[i], h from h_lin[j]  (meshgrid 'ij' + permute(1, 0), :249-262)
+// ROUND: the Blender dataset's (h_sb * H).round() (datasets/blender_mask_grid_sample.py:151-152), torch's half-to-even = rintf, for floorf
+template <bool ROUND>
 __global__ __launch_bounds__(256) void grid_batch_kernel(BatchArgs a) {
   const long n = (long)blockIdx.x * 256 + threadIdx.x;
   const long total = (long)a.side * a.side;
@@ -143,7 +145,8 @@ __global__ __launch_bounds__(256) void grid_batch_kernel(BatchArgs a) {
   const int i = (int)(n % a.side), j = (int)(n / a.side);
   const float w_sb = a.w_lin[i] * a.scale + a.w_offset;       // separate mul / add, as the reference's tensor ops (:257-258)
   const float h_sb = a.h_lin[j] * a.scale + a.h_offset;
-  const float w = floorf(w_sb * (float)a.img_w), h = floorf(h_sb * (float)a.img_h);
+  const float wf = w_sb * (float)a.img_w, hf = h_sb * (float)a.img_h;
+  const float w = ROUND ? rintf(wf) : floorf(wf), h = ROUND ? rintf(hf) : floorf(hf);
   const long pt = (long)(w + h * (float)a.img_w);             // fp32 like (w + h * img_w) before .long() (:262); exact below 2^24 pixels
   const long row = pt + a.row_offset;
   const float* src = a.all_rays + row * a.ray_stride;
@@ -160,8 +163,15 @@ __global__ __launch_bounds__(256) void grid_batch_kernel(BatchArgs a) {
 int launch_grid_batch(const BatchArgs& a, hipStream_t stream) {
   const long total = (long)a.side * a.side;
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(grid_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(grid_batch_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
   return check_launch("grid_batch_kernel");
+}
+
+int launch_grid_batch_round(const BatchArgs& a, hipStream_t stream) {
+  const long total = (long)a.side * a.side;
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(grid_batch_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
+  return check_launch("grid_batch_round_kernel");
 }
 
 // ---------------------------------------------------------------- Adam over one flat parameter buffer

@@ -38,13 +38,16 @@ def get_rays(directions, c2w):
     return o, r
 
 
-def generate_rays(H, W, K, c2w, near=0.0, far=5.0, device="cuda"):
-    """rays[H*W,8] = cat[rays_o, rays_d, near, far] for one camera (video path: near=0, far=5)."""
+def generate_rays(H, W, K, c2w, near=0.0, far=5.0, device="cuda", fma_norm=False):
+    """rays[H*W,8] = cat[rays_o, rays_d, near, far] for one camera (video path: near=0, far=5).  fma_norm=True: the direction's squared norm
+    accumulated by fma, as torch.norm evaluates it on an FMA host (crnerf_generate_rays_fmanorm_f32: the Blender dataset's rays, equal to the
+    reference's bit for bit); the default sums the three squares in order and is within 2 ulp of that."""
     lib = _lib.load()
     K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
     k1, kp = _host_floats([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], 4)
     k2, cp = _host_floats(c2w, 12)
     rays = torch.empty(int(H) * int(W), 8, dtype=torch.float32, device=device)
-    _lib.check(lib.crnerf_generate_rays_f32(kp, cp, int(H), int(W), float(near), float(far), _lib.dev_ptr(rays), _lib.stream_ptr()),
-               "crnerf_generate_rays_f32")
+    fn, name = ((lib.crnerf_generate_rays_fmanorm_f32, "crnerf_generate_rays_fmanorm_f32") if fma_norm
+                else (lib.crnerf_generate_rays_f32, "crnerf_generate_rays_f32"))
+    _lib.check(fn(kp, cp, int(H), int(W), float(near), float(far), _lib.dev_ptr(rays), _lib.stream_ptr()), name)
     return rays

@@ -4,6 +4,7 @@ import collections
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1179,6 +1180,81 @@ def lanczos_resize(img_u8, size_wh, out="u8", signed=False, dst=None):
     return dst
 
 
+RGBA_TILE = (_lib.RGBA_TILE_H, _lib.RGBA_TILE_W)            # rows, output columns of one workgroup of the horizontal pass (csrc/rgbaprep.hip)
+RGBA_VBLOCK = _lib.RGBA_VBLOCK                               # pixels of an output row of one workgroup of the vertical pass
+RGBA_MAX_RECTS = _lib.RGBA_MAX_RECTS
+_rgba_ws = {}
+
+
+def rgba_prepare(img_u8, size_wh, out="u8", signed=False, rects=None, colors=None, lut=None, dst=None, valid_mask=False):
+    """crnerf_rgba_prepare_u8 (include/crnerf_blender.h): the Blender dataset's preparation of a decoded RGBA frame, bit for bit -- the
+    occluders and the colour table of add_perturbation, PIL.Image.resize(size_wh, Image.LANCZOS) of an RGBA image (premultiplied inside, as
+    Pillow does), and the white blend fused into the store.  img_u8: contiguous uint8 [H, W, 4] on the GPU; size_wh = (w, h).
+    out="u8": uint8 [h, w, 4]; "rows": float32 [h*w, 3] = rgb * a + (1 - a) of ToTensor(img), pixel-major (the rgbs / all_rgbs layout);
+    "chw": float32 [3, h, w] of the same blend, with signed=True Normalize(0.5, 0.5) of it ([-1, 1], the all_imgs / whole_img layout).
+    rects / colors: up to RGBA_MAX_RECTS occluders, host int [n, 4] = inclusive (x0, y0, x1, y1) in source pixels and host uint8 [n, 3]; the
+    last rectangle that holds a pixel wins and sets alpha 255.  lut: uint8 [3, 256] (host or device), applied to R, G, B after the occluders.
+    dst: write there instead of a fresh tensor -- contiguous, of the output's dtype and shape (a slice of a larger buffer is).
+    valid_mask=True: returns (out, mask) with mask bool [h*w] = alpha > 0 of the resized frame.
+    A size that equals the source's skips that pass; with both skipped nothing is premultiplied: the frame's bytes pass as they are."""
+    if not torch.is_tensor(img_u8) or not img_u8.is_cuda:
+        raise ValueError("crnerf_amd: rgba_prepare needs a GPU tensor (got %s); the HIP path has no CPU fallback"
+                         % (img_u8.device if torch.is_tensor(img_u8) else type(img_u8).__name__))
+    if img_u8.dtype != torch.uint8:
+        raise ValueError("crnerf_amd: rgba_prepare takes a uint8 image, got %s" % img_u8.dtype)
+    if img_u8.dim() != 3 or img_u8.shape[2] != 4 or img_u8.shape[0] < 1 or img_u8.shape[1] < 1:
+        raise ValueError("crnerf_amd: rgba_prepare takes an image of shape [H, W, 4], got %s" % (tuple(img_u8.shape),))
+    if not img_u8.is_contiguous():
+        raise ValueError("crnerf_amd: rgba_prepare takes a contiguous image")
+    if img_u8.device.index != _lib._current_device():
+        raise _lib._bad_tensor(img_u8, "img_u8", torch.uint8)
+    if out not in ("u8", "rows", "chw") or (signed and out != "chw"):
+        raise ValueError("crnerf_amd: out must be 'u8', 'rows' or 'chw' (signed=True with 'chw' only), got %r" % (out,))
+    H, W = int(img_u8.shape[0]), int(img_u8.shape[1])
+    w, h = (int(v) for v in size_wh)
+    if w < 1 or h < 1:
+        raise ValueError("crnerf_amd: rgba_prepare to a size below 1x1: %s" % ((w, h),))
+    dev = img_u8.device
+    n_rects, rects_np, colors_np = 0, None, None
+    if rects is not None and len(rects) > 0:
+        rects_np = np.ascontiguousarray(np.asarray(rects, dtype=np.int32).reshape(-1, 4))
+        if colors is None:
+            raise ValueError("crnerf_amd: rgba_prepare: rects come with colors")
+        colors_np = np.ascontiguousarray(np.asarray(colors, dtype=np.uint8).reshape(-1, 3))
+        n_rects = int(rects_np.shape[0])
+        if colors_np.shape[0] != n_rects or n_rects > RGBA_MAX_RECTS:
+            raise ValueError("crnerf_amd: rgba_prepare takes up to %d rectangles with one colour each, got %d and %d"
+                             % (RGBA_MAX_RECTS, n_rects, colors_np.shape[0]))
+    if lut is not None:
+        lut = torch.as_tensor(lut)
+        if lut.dtype != torch.uint8 or tuple(lut.shape) != (3, 256):
+            raise ValueError("crnerf_amd: lut must be uint8 [3, 256], got %s %s" % (lut.dtype, tuple(lut.shape)))
+        lut = lut.to(dev).contiguous()
+    shape, dtype = {"u8": ((h, w, 4), torch.uint8), "rows": ((h * w, 3), torch.float32), "chw": ((3, h, w), torch.float32)}[out]
+    if dst is None:
+        dst = torch.empty(shape, dtype=dtype, device=dev)
+    elif (not torch.is_tensor(dst) or dst.device != dev or dst.dtype != dtype or tuple(dst.shape) != shape or not dst.is_contiguous()):
+        raise ValueError("crnerf_amd: dst must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
+    mask = torch.empty(h * w, dtype=torch.bool, device=dev) if valid_mask else None
+    lib = _lib.load()
+    kx, bx, ksx = _lanczos_axis(dev, W, w)
+    ky, by, ksy = _lanczos_axis(dev, H, h)
+    need = lib.crnerf_rgba_prepare_workspace_bytes(H, W, w, h)
+    ws = _rgba_ws.get(dev)
+    if need and (ws is None or ws.numel() < need):
+        ws = _rgba_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)     # stream-ordered reuse, like the metrics workspace
+    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    a = _lib.RgbaPrepareArgs()
+    a.src, a.H, a.W, a.w, a.h = p(img_u8), H, W, w, h
+    a.kx, a.bounds_x, a.ky, a.bounds_y, a.ksize_x, a.ksize_y = p(kx), p(bx), p(ky), p(by), ksx, ksy
+    a.n_rects, a.out_mode = n_rects, _lib.RGBA_OUT["chw_signed" if signed else out]
+    a.rects = rects_np.ctypes.data if n_rects else None
+    a.colors = colors_np.ctypes.data if n_rects else None
+    a.lut, a.dst, a.valid_mask, a.workspace = p(lut), p(dst), p(mask), p(ws) if need else None
+    _lib.check(lib.crnerf_rgba_prepare_u8(ctypes.byref(a), _lib.stream_ptr()), "crnerf_rgba_prepare_u8")
+    return (dst, mask) if valid_mask else dst
+
+
 _scene_ws = {}
 
 
@@ -1221,7 +1297,10 @@ def scene_bounds(xyz, w2c_row2, q_lo=0.1, q_hi=99.9):
     return nears, fars, counts
 
 
-def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset):
+def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin, h_lin, scale, h_offset, w_offset, rounding="floor"):
+    """rounding: how a lattice node becomes a pixel -- "floor" (the Phototourism batcher) or "round" (the Blender batcher's .round(), half to even)."""
+    if rounding not in ("floor", "round"):
+        raise ValueError("crnerf_amd: rounding must be 'floor' or 'round', got %r" % (rounding,))
     lib = _lib.load()
     all_rays, all_rgbs = _f32c(all_rays, "all_rays"), _f32c(all_rgbs, "all_rgbs")
     if all_rays.dim() != 2 or all_rays.shape[1] < 9 or all_rgbs.dim() != 2 or all_rgbs.shape[1] != 3:
@@ -1236,7 +1315,10 @@ def grid_sample_batch(all_rays, all_rgbs, row_offset, img_w, img_h, side, w_lin,
     a.w_lin, a.h_lin = w_lin.data_ptr(), h_lin.data_ptr()
     a.scale, a.h_offset, a.w_offset = float(scale), float(h_offset), float(w_offset)
     a.rays, a.ts, a.rgbs, a.rgb_idx, a.uv_sample = (out[k].data_ptr() for k in ("rays", "ts", "rgbs", "rgb_idx", "uv_sample"))
-    _lib.check(lib.crnerf_grid_sample_batch_f32(ctypes.byref(a), _lib.stream_ptr()), "crnerf_grid_sample_batch_f32")
+    if rounding == "round":
+        _lib.check(lib.crnerf_grid_sample_batch_round_f32(ctypes.byref(a), _lib.stream_ptr()), "crnerf_grid_sample_batch_round_f32")
+    else:
+        _lib.check(lib.crnerf_grid_sample_batch_f32(ctypes.byref(a), _lib.stream_ptr()), "crnerf_grid_sample_batch_f32")
     return out
 
 
