@@ -715,13 +715,23 @@ def crossray_fold(s_matrix, c_matrix, c_mean, s_mean, lin):
     return out
 
 
+def _planar_out(out, HW, like):
+    """The planar rgb destination [3,HW] of a decode: a fresh tensor, or the caller's -- which may be a view with a plane stride of its own
+    (the ABI's plane_stride), each plane dense."""
+    if out is None:
+        return torch.empty(3, HW, dtype=torch.float32, device=like.device)
+    if tuple(out.shape) != (3, HW) or out.dtype != torch.float32 or out.device != like.device or (HW > 1 and out.stride(1) != 1) or out.stride(0) < HW:
+        raise ValueError("crnerf_amd: out must be a float32 [3,%d] tensor on %s with dense planes, got %s %s strides %s on %s"
+                         % (HW, like.device, out.dtype, tuple(out.shape), out.stride(), out.device))
+    return out
+
+
 def crossray_apply(x, affine, out=None):
     lib = _lib.load()
     x = _f32c(x, "x")
     HW = x.shape[0]
-    if out is None:
-        out = torch.empty(3, HW, dtype=torch.float32, device=x.device)
-    _lib.check(lib.crnerf_crossray_apply_f32(_lib.dev_ptr(x), HW, _lib.dev_ptr(affine), _lib.dev_ptr(out), out.stride(0), _lib.stream_ptr()),
+    out = _planar_out(out, HW, x)
+    _lib.check(lib.crnerf_crossray_apply_f32(_lib.dev_ptr(x), HW, _lib.dev_ptr(affine), ctypes.c_void_p(out.data_ptr()), out.stride(0), _lib.stream_ptr()),
                "crnerf_crossray_apply_f32")
     return out
 
@@ -734,11 +744,10 @@ def crossray_decode(content_pm, style_pm, weights, out=None):
     s = _f32c(style_pm, "style") if style_pm is not None else None
     ws = crossray_workspace(x.device)
     HW = x.shape[0]
-    if out is None:
-        out = torch.empty(3, HW, dtype=torch.float32, device=x.device)
+    out = _planar_out(out, HW, x)
     arr = _lib.ptr_array(_wlist(weights, "decoder weight"), "decoder weight")
     _lib.check(lib.crnerf_crossray_decode_f32(_lib.dev_ptr(x), HW, _lib.dev_ptr(s), s.shape[0] if s is not None else 0, arr,
-                                              ctypes.c_void_p(ws.data_ptr()), _lib.dev_ptr(out), out.stride(0), _lib.stream_ptr()),
+                                              ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.stride(0), _lib.stream_ptr()),
                "crnerf_crossray_decode_f32")
     return out
 
