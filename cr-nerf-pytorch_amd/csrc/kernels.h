@@ -153,11 +153,11 @@ int launch_mlp_dgrad_h2(const void* packedT_h2, const float* out, const float* d
 int launch_mlp_dgrad_x3(const void* packedT_x3, const float* out, const float* d_out, const float* acts, float* deltas, float* d_rgb, float* d_sig, long P,
                         hipStream_t stream, const int* only_if = nullptr);
 int launch_mlp_forward_bf16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);   // pair core: the module entry
-int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream);
+int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream);   // one ray per wave PAIR, 32-point tiles, two waves per SIMD (render_fused_bf16p.hip)
 // the pair core with one-piece fp16 operands and a range guard (mlp_forward_bf16p_f16.hip, render_fused_bf16p_f16.hip; inference only)
 int launch_mlp_forward_f16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);
 int launch_render_rays_f16p(const RenderArgs& a, hipStream_t stream);
-int launch_rng_fill(float* out, long R, int n, unsigned long long seed, int stream_id, long ray_offset, hipStream_t stream);   // one ray per wave PAIR, 32-point tiles, two waves per SIMD (render_fused_bf16p.hip)
+int launch_rng_fill(float* out, long R, int n, unsigned long long seed, int stream_id, long ray_offset, hipStream_t stream);
 
 
 size_t content_backward_workspace_floats(long HW);

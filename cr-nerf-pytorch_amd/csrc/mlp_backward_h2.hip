@@ -7,6 +7,7 @@
 // "operand scale"): gradients of any magnitude go through, and an overflow cannot happen (|w| < 255 from the pack check, 256 terms).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core_h2t.h"
 #include "mlp_train16.h"
 
@@ -194,12 +195,9 @@ int launch_mlp_dgrad_h2(const void* packedT_h2, const float* out, const float* d
   if (P <= 0) return 0;
   if ((unsigned long long)P * 1024ull >= (unsigned long long)SAVEX_OOB)
     return set_error(-2, "mlp_backward_h2: more than 3.9 M points per call (the delta rows are addressed with 32-bit offsets)");
-  const long groups = (P + 127) / 128;
-  const int cus = num_cus();
-  const int grid = (int)(groups < cus ? groups : cus), iters = (int)((groups + grid - 1) / grid);
-  if (int rc = ensure_dynamic_lds((const void*)mlp_backward_h2_kernel, LDS_SCRATCH_X, "mlp_backward_h2_kernel")) return rc;
-  hipLaunchKernelGGL(mlp_backward_h2_kernel, dim3(grid), dim3(256), LDS_SCRATCH_X, stream, (const char*)packedT_h2, out, d_out, acts, deltas, d_rgb, d_sig, P, iters, dmax);
-  return check_launch("mlp_backward_h2_kernel");
+  const GridPlan plan = plan_grid((P + 127) / 128);
+  return launch_kernel(mlp_backward_h2_kernel, "mlp_backward_h2_kernel", plan.grid, 256, LDS_SCRATCH_X, stream, (const char*)packedT_h2, out, d_out, acts, deltas, d_rgb,
+                       d_sig, P, plan.iters, dmax);
 }
 
 }  // namespace crnerf

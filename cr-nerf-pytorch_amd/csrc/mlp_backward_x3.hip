@@ -6,6 +6,7 @@
 // A delta row leaves for HBM while the NEXT (transposed) layer walks it as its B operand (the x3 core's row hook).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core_x3.h"
 #include "mlp_train16.h"
 
@@ -141,12 +142,9 @@ int launch_mlp_dgrad_x3(const void* packedT_x3, const float* out, const float* d
   if (P <= 0) return 0;
   if ((unsigned long long)P * 1024ull >= (unsigned long long)SAVEX_OOB)
     return set_error(-2, "mlp_backward_x3: more than 3.9 M points per call (the delta rows are addressed with 32-bit offsets)");
-  const long groups = (P + 127) / 128;
-  const int cus = num_cus();
-  const int grid = (int)(groups < cus ? groups : cus), iters = (int)((groups + grid - 1) / grid);
-  if (int rc = ensure_dynamic_lds((const void*)mlp_backward_x3_kernel, LDS_SCRATCH_X, "mlp_backward_x3_kernel")) return rc;
-  hipLaunchKernelGGL(mlp_backward_x3_kernel, dim3(grid), dim3(256), LDS_SCRATCH_X, stream, (const char*)packedT_x3, out, d_out, acts, deltas, d_rgb, d_sig, P, iters, only_if);
-  return check_launch("mlp_backward_x3_kernel");
+  const GridPlan plan = plan_grid((P + 127) / 128);
+  return launch_kernel(mlp_backward_x3_kernel, "mlp_backward_x3_kernel", plan.grid, 256, LDS_SCRATCH_X, stream, (const char*)packedT_x3, out, d_out, acts, deltas, d_rgb,
+                       d_sig, P, plan.iters, only_if);
 }
 
 }  // namespace crnerf

@@ -1,6 +1,7 @@
 // Stand-alone NeRF_sigma forward on the v16 core: x[P,120] -> out[P,65] (module entry / unit under test).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core16.h"
 
 namespace crnerf {
@@ -65,14 +66,8 @@ __global__ __launch_bounds__(512, 2) void mlp_forward16_kernel(const char* __res
 
 int launch_mlp_forward16(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream) {
   if (P <= 0) return 0;
-  const long groups = (P + 127) / 128;  // 128 points per workgroup-iteration (8 waves x 16)
-  const int cus = num_cus();
-  const int grid = (int)(groups < cus ? groups : cus);
-  const int iters = (int)((groups + grid - 1) / grid);
-  const size_t shmem = LDS_SCRATCH;
-  if (int rc = ensure_dynamic_lds((const void*)mlp_forward16_kernel, shmem, "mlp_forward16_kernel")) return rc;
-  hipLaunchKernelGGL(mlp_forward16_kernel, dim3(grid), dim3(512), shmem, stream, (const char*)packed, x, out, sigma_only, P, iters);
-  return check_launch("mlp_forward16_kernel");
+  const GridPlan plan = plan_grid((P + 127) / 128);  // 128 points per workgroup-iteration (8 waves x 16)
+  return launch_kernel(mlp_forward16_kernel, "mlp_forward16_kernel", plan.grid, 512, LDS_SCRATCH, stream, (const char*)packed, x, out, sigma_only, P, plan.iters);
 }
 
 }  // namespace crnerf

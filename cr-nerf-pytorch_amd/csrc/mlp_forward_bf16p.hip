@@ -4,6 +4,7 @@
 // the two cores' outputs are bit-identical (tests/test_gpu_bf16.py).  The production path is the fused renderer, render_fused_bf16p.hip.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core_bf16p.h"
 
 // mlp_forward_bf16p_f16.hip builds this unit a second time with CRNERF_P_F16 = 1 (fp16 operands + range guard, see mlp_core_bf16.h) under its own names
@@ -116,13 +117,8 @@ __global__ __launch_bounds__(512, 2) void CRNERF_P_MLP_KERNEL(const char* __rest
 
 int CRNERF_P_MLP_LAUNCH(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream) {
   if (P <= 0) return 0;
-  const long groups = (P + 255) / 256;  // 256 points per workgroup-iteration (eight 32-point tiles)
-  const int cus = num_cus();
-  const int grid = (int)(groups < cus ? groups : cus);
-  const int iters = (int)((groups + grid - 1) / grid);
-  if (int rc = ensure_dynamic_lds((const void*)CRNERF_P_MLP_KERNEL, LDS_TOTAL_M, CRNERF_P_MLP_NAME)) return rc;
-  hipLaunchKernelGGL(CRNERF_P_MLP_KERNEL, dim3(grid), dim3(512), LDS_TOTAL_M, stream, (const char*)packed, x, out, sigma_only, P, iters);
-  return check_launch(CRNERF_P_MLP_NAME);
+  const GridPlan plan = plan_grid((P + 255) / 256);  // 256 points per workgroup-iteration (eight 32-point tiles)
+  return launch_kernel(CRNERF_P_MLP_KERNEL, CRNERF_P_MLP_NAME, plan.grid, 512, LDS_TOTAL_M, stream, (const char*)packed, x, out, sigma_only, P, plan.iters);
 }
 
 }  // namespace crnerf

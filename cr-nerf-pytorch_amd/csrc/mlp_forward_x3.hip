@@ -2,6 +2,7 @@
 // on the bf16 matrix cores.  Module-level entry (NeRF_sigma.__call__, models/nerf.py:157-182) and the unit under test for that core.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #if defined(CRNERF_X_NP) && CRNERF_X_NP == 2
 #include "mlp_core_h2t.h"
 #else
@@ -82,14 +83,10 @@ __global__ __launch_bounds__(256, 1) void mlp_forward_x3_kernel(const char* __re
 int launch_mlp_forward_x3(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream, int repair) {
   if (P <= 0) return 0;
   const long groups = (P + 127) / 128;   // 128 points per workgroup-iteration
-  const int cus = num_cus();
   if (repair && groups > 0x7fffffffL) return set_error(-2, "mlp_forward_f32x3_repair: too many points");
-  const int grid = repair ? (int)groups : (int)(groups < cus ? groups : cus);
-  const int iters = (int)((groups + grid - 1) / grid);
-  const size_t shmem = LDS_SCRATCH_X;
-  if (int rc = ensure_dynamic_lds((const void*)mlp_forward_x3_kernel, shmem, "mlp_forward_x3_kernel")) return rc;
-  hipLaunchKernelGGL(mlp_forward_x3_kernel, dim3(grid), dim3(256), shmem, stream, (const char*)packed, x, out, sigma_only, P, iters, repair);
-  return check_launch("mlp_forward_x3_kernel");
+  const GridPlan plan = plan_grid(groups, repair);   // repair: one workgroup per group
+  return launch_kernel(mlp_forward_x3_kernel, "mlp_forward_x3_kernel", plan.grid, 256, LDS_SCRATCH_X, stream, (const char*)packed, x, out, sigma_only, P, plan.iters,
+                       repair);
 }
 
 }  // namespace crnerf

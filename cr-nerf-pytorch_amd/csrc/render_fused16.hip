@@ -10,6 +10,7 @@
 // barriers order the exchanges.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core16.h"
 #include "mlp_train16.h"
 #include "pair_ops.h"
@@ -259,53 +260,27 @@ __global__ __launch_bounds__(512, 2) void render_rays_train16_rng_kernel(RenderP
 
 int launch_render_rays16(const RenderArgs& a, hipStream_t stream) {
   if (a.R <= 0) return 0;
-  if (a.Nc < 2 || a.Nc > MAX_NC) return set_error(-2, "render_rays: N_samples must be in [2, 256] for the fused kernel");
-  if (a.Ni < 0 || a.Ni > MAX_NI) return set_error(-2, "render_rays: N_importance must be in [0, 256] for the fused kernel");
-  if (a.Ni > 0 && a.Nc < 3) return set_error(-2, "render_rays: hierarchical sampling needs N_samples >= 3");
-  if (a.Ni > 0 && !a.packed_fine) return set_error(-3, "render_rays: N_importance > 0 but no fine model");
+  if (int rc = check_sample_counts("render_rays", a, MAX_NC, MAX_NI)) return rc;
   RenderParams16 k;
-  k.packed0 = (const char*)a.packed_coarse;
-  k.packed1 = (const char*)(a.packed_fine ? a.packed_fine : a.packed_coarse);
-  k.rays = a.rays; k.view_dir = a.view_dir; k.z_coarse = a.z_coarse; k.z_steps = a.z_steps; k.u = a.u; k.u_stride = a.u_stride;
-  k.noise_c = a.noise_coarse; k.noise_f = a.noise_fine; k.noise_std = a.noise_std; k.use_disp = a.use_disp;
-  k.R = a.R; k.Nc = a.Nc; k.Ni = a.Ni;
-  k.weights_c = a.weights_coarse; k.feature_c = a.feature_coarse; k.depth_c = a.depth_coarse;
-  k.weights_f = a.weights_fine; k.feature_f = a.feature_fine; k.depth_f = a.depth_fine; k.z_fine = a.z_fine;
-  k.rng_seed = a.rng_seed; k.rng_ray_offset = a.rng_ray_offset; k.rng_flags = a.rng_flags; k.perturb = a.perturb;
-  k.z_coarse_out = a.z_coarse_out; k.noise_c_out = a.noise_coarse_out; k.noise_f_out = a.noise_fine_out;
-  const long quads = (a.R + 3) / 4;
-  const int cus = num_cus();
-  const int grid = (int)(quads < cus ? quads : cus);
-  k.iters = (int)((quads + grid - 1) / grid);
+  fill_render_params(k, a);
+  fill_rng_params(k, a);
+  const GridPlan plan = plan_grid((a.R + 3) / 4);
+  k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)crnerf_sched16) : nullptr;
   const size_t shmem = LDS_SCRATCH + 4 * PAIR_BYTES + V16_WAVES * 32 * sizeof(float) + 16;
   if (a.lean) {   // crnerf_render_rays_lean_f32: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
     if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
     if (a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
-    if (int rc = ensure_dynamic_lds((const void*)render_rays16_lean_kernel, shmem, "render_rays16_lean_kernel")) return rc;
-    hipLaunchKernelGGL(render_rays16_lean_kernel, dim3(grid), dim3(512), shmem, stream, k);
-    return check_launch("render_rays16_lean_kernel");
+    return launch_kernel(render_rays16_lean_kernel, "render_rays16_lean_kernel", plan.grid, 512, shmem, stream, k);
   }
+  const bool rngk = wants_rng_kernel(a);
   if (a.train_acts_coarse) {
-    if (a.Ni > 0 && (!a.train_acts_fine || !a.train_raw_fine)) return set_error(-1, "render_rays_train: fine buffers are NULL");
-    if (!a.train_raw_coarse) return set_error(-1, "render_rays_train: raw_coarse is NULL");
-    TrainHook h{{(float*)a.train_acts_coarse, (float*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
-    if (int rc = zero_acts_range(a.train_acts_coarse, a.R * a.Nc, stream)) return rc;     // the fp32 twin tracks no operand range (kernels.h)
-    if (a.Ni > 0)
-      if (int rc = zero_acts_range(a.train_acts_fine, a.R * (a.Nc + a.Ni), stream)) return rc;
-    const bool rngk = a.rng_flags != 0 || a.z_coarse_out;
-    const void* fn = rngk ? (const void*)render_rays_train16_rng_kernel : (const void*)render_rays_train16_kernel;
-    if (int rc = ensure_dynamic_lds(fn, shmem, "render_rays_train16_kernel")) return rc;
-    if (rngk) hipLaunchKernelGGL(render_rays_train16_rng_kernel, dim3(grid), dim3(512), shmem, stream, k, h);
-    else hipLaunchKernelGGL(render_rays_train16_kernel, dim3(grid), dim3(512), shmem, stream, k, h);
-    return check_launch("render_rays_train16_kernel");
+    if (int rc = check_train_state("render_rays_train", a)) return rc;
+    const TrainHook h{{(float*)a.train_acts_coarse, (float*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
+    if (int rc = zero_train_ranges(a, stream)) return rc;     // the fp32 twin tracks no operand range (kernels.h)
+    return launch_kernel(rngk ? render_rays_train16_rng_kernel : render_rays_train16_kernel, "render_rays_train16_kernel", plan.grid, 512, shmem, stream, k, h);
   }
-  const bool rngk = a.rng_flags != 0 || a.z_coarse_out;
-  const void* fn = rngk ? (const void*)render_rays16_rng_kernel : (const void*)render_rays16_kernel;
-  if (int rc = ensure_dynamic_lds(fn, shmem, "render_rays16_kernel")) return rc;
-  if (rngk) hipLaunchKernelGGL(render_rays16_rng_kernel, dim3(grid), dim3(512), shmem, stream, k);
-  else hipLaunchKernelGGL(render_rays16_kernel, dim3(grid), dim3(512), shmem, stream, k);
-  return check_launch("render_rays16_kernel");
+  return launch_kernel(rngk ? render_rays16_rng_kernel : render_rays16_kernel, "render_rays16_kernel", plan.grid, 512, shmem, stream, k);
 }
 
 #ifdef CRNERF_TIMING

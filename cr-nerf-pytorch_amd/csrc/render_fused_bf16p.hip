@@ -12,6 +12,7 @@
 // accumulator is live across the MLP (the kernel must fit 256 registers for two waves per SIMD).
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mlp_core_bf16p.h"
 #include "pair_ops.h"
 #include "ray_ops.h"
@@ -323,18 +324,9 @@ __global__ __launch_bounds__(512, 2) void render_rays_bf16p_fine_kernel(RenderPa
 
 int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   if (a.R <= 0) return 0;
-  if (a.Nc < 2 || a.Nc > MAX_NC) return set_error(-2, CRNERF_P_RENDER_WHAT ": N_samples must be in [2, 256] for the fused kernel");
-  if (a.Ni < 0 || a.Ni > MAX_NI) return set_error(-2, CRNERF_P_RENDER_WHAT ": N_importance must be in [0, 256] for the fused kernel");
-  if (a.Ni > 0 && a.Nc < 3) return set_error(-2, CRNERF_P_RENDER_WHAT ": hierarchical sampling needs N_samples >= 3");
-  if (a.Ni > 0 && !a.packed_fine) return set_error(-3, CRNERF_P_RENDER_WHAT ": N_importance > 0 but no fine model");
+  if (int rc = check_sample_counts(CRNERF_P_RENDER_WHAT, a, MAX_NC, MAX_NI)) return rc;
   RenderParamsP k;
-  k.packed0 = (const char*)a.packed_coarse;
-  k.packed1 = (const char*)(a.packed_fine ? a.packed_fine : a.packed_coarse);
-  k.rays = a.rays; k.view_dir = a.view_dir; k.z_coarse = a.z_coarse; k.z_steps = a.z_steps; k.u = a.u; k.u_stride = a.u_stride;
-  k.noise_c = a.noise_coarse; k.noise_f = a.noise_fine; k.noise_std = a.noise_std; k.use_disp = a.use_disp;
-  k.R = a.R; k.Nc = a.Nc; k.Ni = a.Ni;
-  k.weights_c = a.weights_coarse; k.feature_c = a.feature_coarse; k.depth_c = a.depth_coarse;
-  k.weights_f = a.weights_fine; k.feature_f = a.feature_fine; k.depth_f = a.depth_fine; k.z_fine = a.z_fine;
+  fill_render_params(k, a);
   k.wc_in = nullptr;
 #if CRNERF_P_F16
   if (a.fine_only || a.train_acts_coarse) return set_error(-3, CRNERF_P_RENDER_WHAT ": the fp16 build has the inference kernel only");
@@ -347,31 +339,20 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
     k.weights_c = k.feature_c = k.depth_c = nullptr;
   }
 #endif
-  const long quads = (a.R + 3) / 4;
-  const int cus = num_cus();
-  const int grid = (int)(quads < cus ? quads : cus);   // one workgroup per CU, persistent over ray quads
-  k.iters = (int)((quads + grid - 1) / grid);
+  const GridPlan plan = plan_grid((a.R + 3) / 4);   // one workgroup per CU, persistent over ray quads
+  k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)CRNERF_P_RENDER_SCHED) : nullptr;
 #if !CRNERF_P_F16
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_bf16)
-    if (a.Ni > 0 && (!a.train_acts_fine || !a.train_raw_fine)) return set_error(-1, "render_rays_train_bf16: fine buffers are NULL");
-    if (!a.train_raw_coarse) return set_error(-1, "render_rays_train_bf16: raw_coarse is NULL");
+    if (int rc = check_train_state("render_rays_train_bf16", a)) return rc;
     if ((unsigned long long)a.R * (unsigned)(a.Nc + a.Ni) * 512ull >= (unsigned long long)SAVE_OOB)
       return set_error(-2, "render_rays_train_bf16: more than 7.8 M sample points per pass and call (the saved rows are addressed with 32-bit offsets)");
-    TrainHookP h{{(char*)a.train_acts_coarse, (char*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
-    if (int rc = ensure_dynamic_lds((const void*)render_rays_train_bf16p_kernel, LDS_TOTAL_TRAIN_P, "render_rays_train_bf16p_kernel")) return rc;
-    hipLaunchKernelGGL(render_rays_train_bf16p_kernel, dim3(grid), dim3(512), LDS_TOTAL_TRAIN_P, stream, k, h);
-    return check_launch("render_rays_train_bf16p_kernel");
+    const TrainHookP h{{(char*)a.train_acts_coarse, (char*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
+    return launch_kernel(render_rays_train_bf16p_kernel, "render_rays_train_bf16p_kernel", plan.grid, 512, LDS_TOTAL_TRAIN_P, stream, k, h);
   }
-  if (a.fine_only) {
-    if (int rc = ensure_dynamic_lds((const void*)render_rays_bf16p_fine_kernel, LDS_TOTAL_P, "render_rays_bf16p_fine_kernel")) return rc;
-    hipLaunchKernelGGL(render_rays_bf16p_fine_kernel, dim3(grid), dim3(512), LDS_TOTAL_P, stream, k);
-    return check_launch("render_rays_bf16p_fine_kernel");
-  }
+  if (a.fine_only) return launch_kernel(render_rays_bf16p_fine_kernel, "render_rays_bf16p_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
 #endif
-  if (int rc = ensure_dynamic_lds((const void*)CRNERF_P_RENDER_KERNEL, LDS_TOTAL_P, CRNERF_P_RENDER_NAME)) return rc;
-  hipLaunchKernelGGL(CRNERF_P_RENDER_KERNEL, dim3(grid), dim3(512), LDS_TOTAL_P, stream, k);
-  return check_launch(CRNERF_P_RENDER_NAME);
+  return launch_kernel(CRNERF_P_RENDER_KERNEL, CRNERF_P_RENDER_NAME, plan.grid, 512, LDS_TOTAL_P, stream, k);
 }
 
 #if defined(CRNERF_TIMING) && !CRNERF_P_F16

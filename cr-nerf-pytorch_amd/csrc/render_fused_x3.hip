@@ -11,6 +11,7 @@
 // transmittance, so compositing needs no cross-wave traffic.  Grid-stride over ray quads.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "launch.h"
 #if defined(CRNERF_X_NP) && CRNERF_X_NP == 2
 #include "mlp_core_h2t.h"
 #else
@@ -252,51 +253,29 @@ __global__ __launch_bounds__(256, 1) void render_rays_train_x3_rng_kernel(Render
 
 int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
   if (a.R <= 0) return 0;
-  if (a.Nc < 2 || a.Nc > MAX_NC) return set_error(-2, "render_rays_f32x3: N_samples must be in [2, 256] for the fused kernel");
-  if (a.Ni < 0 || a.Ni > MAX_NI) return set_error(-2, "render_rays_f32x3: N_importance must be in [0, 256] for the fused kernel");
-  if (a.Ni > 0 && a.Nc < 3) return set_error(-2, "render_rays_f32x3: hierarchical sampling needs N_samples >= 3");
-  if (a.Ni > 0 && !a.packed_fine) return set_error(-3, "render_rays_f32x3: N_importance > 0 but no fine model");
+  if (int rc = check_sample_counts("render_rays_f32x3", a, MAX_NC, MAX_NI)) return rc;
   RenderParamsX k;
-  k.packed0 = (const char*)a.packed_coarse;
-  k.packed1 = (const char*)(a.packed_fine ? a.packed_fine : a.packed_coarse);
-  k.rays = a.rays; k.view_dir = a.view_dir; k.z_coarse = a.z_coarse; k.z_steps = a.z_steps; k.u = a.u; k.u_stride = a.u_stride;
-  k.noise_c = a.noise_coarse; k.noise_f = a.noise_fine; k.noise_std = a.noise_std; k.use_disp = a.use_disp;
-  k.R = a.R; k.Nc = a.Nc; k.Ni = a.Ni;
-  k.rng_seed = a.rng_seed; k.rng_ray_offset = a.rng_ray_offset; k.rng_flags = a.rng_flags; k.perturb = a.perturb;
-  k.z_coarse_out = a.z_coarse_out; k.noise_c_out = a.noise_coarse_out; k.noise_f_out = a.noise_fine_out;
-  const bool rngk = a.rng_flags != 0 || a.z_coarse_out;
-  k.weights_c = a.weights_coarse; k.feature_c = a.feature_coarse; k.depth_c = a.depth_coarse;
-  k.weights_f = a.weights_fine; k.feature_f = a.feature_fine; k.depth_f = a.depth_fine; k.z_fine = a.z_fine;
+  fill_render_params(k, a);
+  fill_rng_params(k, a);
+  const bool rngk = wants_rng_kernel(a);
   const long quads = (a.R + 3) / 4;
-  const int cus = num_cus();
   if (a.repair && quads > 0x7fffffffL) return set_error(-3, "render_rays_f32x3_repair: renders of < 2^33 rays only");
   k.repair = a.repair;
-  const int grid = a.repair ? (int)quads : (int)(quads < cus ? quads : cus);   // one workgroup per CU, persistent over ray quads (repair: one per quad)
-  k.iters = (int)((quads + grid - 1) / grid);
+  const GridPlan plan = plan_grid(quads, a.repair);   // one workgroup per CU, persistent over ray quads (repair: one per quad)
+  k.iters = plan.iters;
   const size_t shmem = LDS_SCRATCH_X + 4 * SCRATCH_BYTES;
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_f32x3 / _f32h2; repair: the rays the h2 twin poisoned, saved rows included)
-    if (a.Ni > 0 && (!a.train_acts_fine || !a.train_raw_fine)) return set_error(-1, "render_rays_train_f32x3: fine buffers are NULL");
-    if (!a.train_raw_coarse) return set_error(-1, "render_rays_train_f32x3: raw_coarse is NULL");
+    if (int rc = check_train_state("render_rays_train_f32x3", a)) return rc;
     if ((unsigned long long)a.R * (unsigned)(a.Nc + a.Ni) * 1024ull >= (unsigned long long)SAVEX_OOB)
       return set_error(-2, "render_rays_train_f32x3: more than 3.9 M sample points per pass and call (the saved rows are addressed with 32-bit offsets)");
-    TrainHookX h{{(float*)a.train_acts_coarse, (float*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
-    if (!a.repair) {   // the range words of both passes start at zero (the repair launch leaves what the h2 twin raised: kernels.h acts_range_word)
-      if (int rc = zero_acts_range(a.train_acts_coarse, a.R * a.Nc, stream)) return rc;
-      if (a.Ni > 0)
-        if (int rc = zero_acts_range(a.train_acts_fine, a.R * (a.Nc + a.Ni), stream)) return rc;
-    }
-    const void* fn = rngk ? (const void*)render_rays_train_x3_rng_kernel : (const void*)render_rays_train_x3_kernel;
-    const size_t shmem_t = shmem + LDS_RANGE_BYTES;      // + the h2 twin's per-lane range words (x3: unused)
-    if (int rc = ensure_dynamic_lds(fn, shmem_t, "render_rays_train_x3_kernel")) return rc;
-    if (rngk) hipLaunchKernelGGL(render_rays_train_x3_rng_kernel, dim3(grid), dim3(256), shmem_t, stream, k, h);
-    else hipLaunchKernelGGL(render_rays_train_x3_kernel, dim3(grid), dim3(256), shmem_t, stream, k, h);
-    return check_launch("render_rays_train_x3_kernel");
+    const TrainHookX h{{(float*)a.train_acts_coarse, (float*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
+    if (!a.repair)   // (the repair launch leaves what the h2 twin raised: kernels.h acts_range_word)
+      if (int rc = zero_train_ranges(a, stream)) return rc;
+    // + the h2 twin's per-lane range words (x3: unused)
+    return launch_kernel(rngk ? render_rays_train_x3_rng_kernel : render_rays_train_x3_kernel, "render_rays_train_x3_kernel", plan.grid, 256,
+                         shmem + LDS_RANGE_BYTES, stream, k, h);
   }
-  const void* fn = rngk ? (const void*)render_rays_x3_rng_kernel : (const void*)render_rays_x3_kernel;
-  if (int rc = ensure_dynamic_lds(fn, shmem, "render_rays_x3_kernel")) return rc;
-  if (rngk) hipLaunchKernelGGL(render_rays_x3_rng_kernel, dim3(grid), dim3(256), shmem, stream, k);
-  else hipLaunchKernelGGL(render_rays_x3_kernel, dim3(grid), dim3(256), shmem, stream, k);
-  return check_launch("render_rays_x3_kernel");
+  return launch_kernel(rngk ? render_rays_x3_rng_kernel : render_rays_x3_kernel, "render_rays_x3_kernel", plan.grid, 256, shmem, stream, k);
 }
 
 #ifdef CRNERF_TIMING

@@ -1,6 +1,8 @@
-"""Records tests/golden/abi_errors.json: the return code and the crnerf_last_error() text of every argument check of csrc/abi.hip.  Run it on a
-machine WITHOUT a GPU, with the library whose messages are the contract (the fixture in the tree was recorded from the build before the boundary
-helpers -- fail / all_set / pack_entry / forward_entry / to_render_args ... -- replaced the hand-copied checks):
+"""Records tests/golden/abi_errors.json: the return code and the crnerf_last_error() text of every argument check of csrc/abi.hip and of the
+launch layer behind it (csrc/launch.h and the render / MLP launchers: sample counts, saved-row offset limits, the repair grids).  Run it on a
+machine WITHOUT a GPU, with the library whose messages are the contract (the abi.hip cases in the tree were recorded from the build before the
+boundary helpers -- fail / all_set / pack_entry / forward_entry / to_render_args ... -- replaced the hand-copied checks, the launch-layer cases
+from the build before launch.h replaced the launchers' own copies):
 
     CRNERF_LIB_PATH=path/to/libcrnerf_parent.so python tools/make_abi_error_golden.py [--out FILE]
 
@@ -13,8 +15,14 @@ GPU machine that call would launch on the dummy pointers.  The test module impor
 
 Before every case the error text is set by one fixed refused call (PRIME), so a no-op's recorded text is that one: a success leaves it alone.
 
-Checks of abi.hip that no case reaches:
-  * check_launch, ensure_dynamic_lds, crnerf_stream_destroy's failure and hipExtStreamCreateWithCUMask's: they need the HIP runtime to fail;
+Checks that no case reaches:
+  * check_launch, ensure_dynamic_lds, zero_acts_range, crnerf_stream_destroy's failure and hipExtStreamCreateWithCUMask's: they need the HIP runtime
+    to fail;
+  * of the launchers: "no fine model" (abi.hip refuses a missing packed_fine first), the training twins' NULL saved state (abi.hip's own REQUIREs
+    come first), the lean and fine-only refusals of render_fused16.hip / render_fused_bf16p.hip (abi.hip checks the same conditions under its own
+    texts) and the fp16 build's "inference kernel only" (no entry point routes there); the 3.9 M point limit of the two data-gradient launchers
+    is not recorded either (launch_mlp_backward may touch the scratch buffer before it gets there);
+  * the saved-row limit of crnerf_render_rays_train_f32: that launcher has none, the call would go on to a launch;
   * crnerf_stream_create_cu_share's range check and crnerf_cus_per_xcd: they query the device before validating (only the NULL `stream` case is here);
   * crnerf_scene_bounds_f64 "workspace is NULL": scene_bounds_workspace_bytes() is 0 for every size;
   * the phase-dependent pointers of the three backward entries are covered from the refusing side only (a phase that does not read a pointer
@@ -251,6 +259,28 @@ bad(e, "args.rng_flags", 1, 8)
 for k in ("z_coarse_out", "noise_coarse_out", "noise_fine_out"):
     case(e, k, **{"args." + k: P})
 noop(e, "n_rays=0", **{"args.n_rays": 0})
+
+
+# ---- the launch layer behind abi.hip (csrc/launch.h and the launchers' own refusals): every one fires before anything is launched
+def sample_count_checks(e, skip=()):
+    """What launch.h's check_sample_counts refuses, in the order it checks."""
+    for ns, ni in ((1, None), (257, None), (64, 257), (64, -1), (2, 1)):
+        label = "n_samples=%d" % ns + ("" if ni is None else ", n_importance=%d" % ni)
+        if label not in skip:
+            case(e, label, **{"args.n_samples": ns}, **({} if ni is None else {"args.n_importance": ni}))
+
+
+for e in ("crnerf_render_rays_f32", "crnerf_render_rays_bf16", "crnerf_render_rays_f32x3", "crnerf_render_rays_f32h2", "crnerf_render_rays_f32x3_repair",
+          "crnerf_render_rays_f16", "crnerf_render_rays_train_f32", "crnerf_render_rays_train_bf16", "crnerf_render_rays_train_f32x3",
+          "crnerf_render_rays_train_f32h2", "crnerf_render_rays_train_f32x3_repair"):
+    sample_count_checks(e)
+sample_count_checks("crnerf_render_rays_bf16_fine", skip=("n_samples=64, n_importance=-1",))      # abi.hip refuses that one itself (above)
+# the saved rows' 32-bit offsets (not crnerf_render_rays_train_f32: its launcher has no such limit, the call would go on to a launch)
+for e in ("crnerf_render_rays_train_bf16", "crnerf_render_rays_train_f32x3", "crnerf_render_rays_train_f32h2", "crnerf_render_rays_train_f32x3_repair"):
+    case(e, "more sample points than 32-bit row offsets reach", **{"args.n_rays": 2 ** 20, "args.n_samples": 8, "args.n_importance": 8})
+# the repair launches: one workgroup per ray quad / per 128 points
+case("crnerf_render_rays_f32x3_repair", "more ray quads than a launch", **{"args.n_rays": 2 ** 34, "args.n_samples": 4, "args.n_importance": 0})
+case("crnerf_mlp_forward_f32x3_repair", "more point groups than a launch", n=2 ** 39)
 
 # ---- rays, encoder
 e = entry("crnerf_ray_directions_f32", H=1, W=1, fx=1.0, fy=1.0, cx=0.0, cy=0.0, directions=P, stream=None)
