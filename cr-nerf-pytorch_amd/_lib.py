@@ -261,6 +261,12 @@ BLENDER_SIGNATURES = {
     "crnerf_grid_sample_batch_round_f32": (i32, [ctypes.POINTER(BatchArgs), vp]),
     "crnerf_generate_rays_fmanorm_f32": (i32, [hf, hf, i32, i32, f32, f32, vp, vp]),
 }
+# One row per symbol of the companion header include/crnerf_lean.h (the lean render on the pair core's two builds), bound by the same loader;
+# tests/test_lean_pair_host.py holds it to that header's prototypes.
+LEAN_SIGNATURES = {
+    "crnerf_render_rays_lean_bf16": (i32, [ra, vp]),
+    "crnerf_render_rays_lean_f16": (i32, [ra, vp]),
+}
 
 
 _lib = None
@@ -280,8 +286,8 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()):
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h
+        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()):
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

@@ -6,6 +6,7 @@
 #include <string.h>
 #include "../../include/crnerf.h"
 #include "../../include/crnerf_blender.h"
+#include "../../include/crnerf_lean.h"
 #include "crossray.h"
 #include "kernels.h"
 #include "layout.h"
@@ -382,6 +383,25 @@ int crnerf_render_rays_lean_f32(const crnerf_render_args* a, void* stream) {
   r.lean = 1;
   return launch_render_rays16(r, (hipStream_t)stream);
 }
+
+// include/crnerf_lean.h: the same checks, codes and texts on the pair core's two builds
+static int render_rays_lean_pair(const crnerf_render_args* a, void* stream, Core core) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: negative n_rays");
+  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_importance must be in [1, 256]");
+  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_samples must be in [3, 256]");
+  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays");
+  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
+  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
+    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean: no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)");
+  auto r = to_render_args(a);
+  r.weights_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr;   // ignored, whatever the caller passed
+  r.lean = 1;
+  return core == Core::F16_PAIR ? launch_render_rays_f16p(r, (hipStream_t)stream) : launch_render_rays_bf16p(r, (hipStream_t)stream);
+}
+int crnerf_render_rays_lean_bf16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::BF16_PAIR); }
+int crnerf_render_rays_lean_f16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::F16_PAIR); }
 
 size_t crnerf_packed_mlp_mixed_bytes(void) { return gemm_packed_bytes(); }
 size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_acts_bytes((long)n); }

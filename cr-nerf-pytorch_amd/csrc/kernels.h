@@ -123,7 +123,8 @@ struct RenderArgs {
   int repair = 0;
   // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT (rendered by another core); sample_pdf + merge + the fine pass only
   int fine_only = 0;
-  // crnerf_render_rays_lean_f32 (render_fused16.hip): trunk-only coarse pass; writes feature_fine, depth_fine and (optional) z_fine only
+  // crnerf_render_rays_lean_f32 (render_fused16.hip), crnerf_render_rays_lean_bf16 / _f16 (render_fused_bf16p.hip; include/crnerf_lean.h): trunk-only
+  // coarse pass; writes feature_fine, depth_fine and (optional) z_fine only.  The other launchers do not look at it.
   int lean = 0;
   // training twin (crnerf_render_rays_train_f32; all null for inference): saved activations + raw MLP outputs per pass
   void* train_acts_coarse = nullptr;   // crnerf_mlp_train_acts_bytes(R*Nc)

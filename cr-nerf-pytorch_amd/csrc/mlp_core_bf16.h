@@ -43,9 +43,16 @@ constexpr int B_AHEAD = CRNERF_B_AHEAD;   // fragments read ahead of the one bei
 constexpr int B_TAIL = STREAMB_USED - (STAGESB_PER_PASS - 1) * STAGE_FRAGS;  // fragments in the (short) last stage: 8
 static_assert(B_TAIL == 8 && STREAMB_USED % B_AHEAD == 0, "tail stage must fit the piece schedule");
 
-// ---- compile-time schedule over the pass-relative fragment index i (0 <= i < STREAMB_USED) -------------
-// position in the padded stream (the look-ahead past the last fragment lands in the next pass)
-constexpr int b_pos(int i) { return i < STREAMB_USED ? i : i + (STREAMB_FRAGS - STREAMB_USED); }
+// ---- compile-time schedule over the walk-relative fragment index i (0 <= i < used) ---------------------
+// A WALK is what one tile multiplies: `used` fragments of a packed stream from its start.  The full walk is the whole pass (used = STREAMB_USED =
+// 1208: 75 stages + the 8-fragment tail stage); the trunk walk of the lean renderer (mlp_core_bf16p.h "Trunk walk") ends behind xyz_encoding_8
+// (used = OFFB_FIN = 992: 62 whole stages, no tail).  Every function below takes the walk as its last argument and defaults to the full walk.
+constexpr int TRUNKB_USED = OFFB_FIN;
+constexpr int b_walk_stages(int used = STREAMB_USED) { return (used + STAGE_FRAGS - 1) / STAGE_FRAGS; }
+constexpr bool b_walk_ok(int used) { return used % STAGE_FRAGS == 0 || used % STAGE_FRAGS == B_TAIL; }   // the tail's piece / barrier slots are written for 8 fragments
+static_assert(b_walk_stages() == STAGESB_PER_PASS && b_walk_ok(STREAMB_USED) && b_walk_ok(TRUNKB_USED) && TRUNKB_USED % STAGE_FRAGS == 0, "walks");
+// position in the padded stream (the look-ahead past the last fragment lands in the next tile's walk)
+constexpr int b_pos(int i, int used = STREAMB_USED) { return i < used ? i : i + (b_walk_stages(used) * STAGE_FRAGS - used); }
 // The barrier that opens stage c + 1 sits in the LAST k-step of stage c whose look-ahead read still targets stage c (slot
 // 15 - B_AHEAD = 11; in the 8-fragment tail stage slot 3): every read of stage c + 1 is issued behind it.  (Rounds 1-2 had it in
 // slot 14, i.e. BEHIND the first three look-ahead reads of stage c + 1, which were therefore covered by nothing but the ~1 us that
@@ -55,41 +62,45 @@ constexpr int b_pos(int i) { return i < STREAMB_USED ? i : i + (STREAMB_FRAGS - 
 constexpr int B_ADV_SLOT = STAGE_FRAGS - 1 - B_AHEAD;
 constexpr int B_ADV_SLOT_TAIL = B_TAIL - 1 - B_AHEAD;
 static_assert(B_ADV_SLOT >= 10 && B_ADV_SLOT_TAIL >= 3, "the barrier must come after the stage's third LDS-DMA piece (slots 9 / 3)");
-constexpr bool b_tail(int i) { return i / STAGE_FRAGS == STAGESB_PER_PASS - 1; }
-constexpr bool b_advance_at(int i) { return i % STAGE_FRAGS == (b_tail(i) ? B_ADV_SLOT_TAIL : B_ADV_SLOT); }
+constexpr bool b_tail(int i, int used = STREAMB_USED) { return used % STAGE_FRAGS != 0 && i / STAGE_FRAGS == b_walk_stages(used) - 1; }
+constexpr bool b_advance_at(int i, int used = STREAMB_USED) { return i % STAGE_FRAGS == (b_tail(i, used) ? B_ADV_SLOT_TAIL : B_ADV_SLOT); }
 // stage advances executed before iteration i's read is issued (= the newest stage that read may touch)
-constexpr int b_cur_stage(int i) { return i / STAGE_FRAGS + (i % STAGE_FRAGS > (b_tail(i) ? B_ADV_SLOT_TAIL : B_ADV_SLOT) ? 1 : 0); }
+constexpr int b_cur_stage(int i, int used = STREAMB_USED) {
+  return i / STAGE_FRAGS + (i % STAGE_FRAGS > (b_tail(i, used) ? B_ADV_SLOT_TAIL : B_ADV_SLOT) ? 1 : 0);
+}
 // LDS-DMA piece (0..3) issued at iteration i, or -1: slots 1, 5, 9, 13 of a stage (k-steps that carry one epilogue
 // quarter in the 16-k-step layers, so piece + quarter + fragment read stay within 4 fillers per MFMA gap)
-constexpr int b_piece_at(int i) {
+constexpr int b_piece_at(int i, int used = STREAMB_USED) {
   const int sl = i % STAGE_FRAGS;
-  if (!b_tail(i)) return sl % 4 == 1 ? sl / 4 : -1;
+  if (!b_tail(i, used)) return sl % 4 == 1 ? sl / 4 : -1;
   return sl == 0 ? 0 : (sl == 1 ? 1 : (sl == 3 ? 2 : (sl == 5 ? 3 : -1)));   // tail stage (B_TAIL = 8 fragments)
 }
 // prefetch-cursor bookkeeping (SALU only) sits in the stage's last k-step, which carries no epilogue work
-constexpr bool b_cursor_at(int i) { return b_tail(i) ? i == STREAMB_USED - 1 : i % STAGE_FRAGS == STAGE_FRAGS - 1; }
-constexpr bool b_schedule_ok() {
+constexpr bool b_cursor_at(int i, int used = STREAMB_USED) { return b_tail(i, used) ? i == used - 1 : i % STAGE_FRAGS == STAGE_FRAGS - 1; }
+constexpr bool b_schedule_ok(int used = STREAMB_USED) {
+  if (!b_walk_ok(used)) return false;
   int pieces = 0, advances = 0, cursors = 0;
-  for (int i = 0; i < STREAMB_USED; ++i) {
-    if (b_cur_stage(i) != advances) return false;
-    const int rs = b_pos(i + B_AHEAD) / STAGE_FRAGS;
+  for (int i = 0; i < used; ++i) {
+    if (b_cur_stage(i, used) != advances) return false;
+    const int rs = b_pos(i + B_AHEAD, used) / STAGE_FRAGS;
     if (rs > advances || rs < i / STAGE_FRAGS) return false;   // EVERY read targets a stage whose barrier has been passed
-    if (b_piece_at(i) >= 0) {
-      if (b_piece_at(i) != pieces % 4 || cursors != pieces / 4) return false;   // in order, cursor moved before piece 0
+    if (b_piece_at(i, used) >= 0) {
+      if (b_piece_at(i, used) != pieces % 4 || cursors != pieces / 4) return false;   // in order, cursor moved before piece 0
       ++pieces;
     }
-    if (b_cursor_at(i)) {
+    if (b_cursor_at(i, used)) {
       ++cursors;
       if (pieces != 4 * cursors) return false;
     }
-    if (b_advance_at(i)) {
+    if (b_advance_at(i, used)) {
       ++advances;
       if (pieces != 4 * advances - 1) return false;   // the barrier follows the stage's third piece: vmcnt(7), see WeightPipeB
     }
   }
-  return advances == STAGESB_PER_PASS && cursors == STAGESB_PER_PASS && b_cur_stage(STREAMB_USED - 1) == STAGESB_PER_PASS;
+  return advances == b_walk_stages(used) && cursors == b_walk_stages(used) && b_cur_stage(used - 1, used) == b_walk_stages(used);
 }
 static_assert(b_schedule_ok(), "bf16 fragment schedule violates the ring protocol");
+static_assert(b_schedule_ok(TRUNKB_USED), "bf16 fragment schedule of the trunk walk violates the ring protocol");
 
 // Weight ring of the bf16 core: B_RING = 4 slots x 16 KiB, and because a pass is 76 = 19 x 4 stages the ring is in the SAME
 // phase at the start of every tile -- so, with the tile code fully unrolled, every ring quantity is a compile-time

@@ -42,37 +42,110 @@ static_assert(P_PIECES == 2, "issue_piece hard-codes two pieces");
 #endif
 constexpr int P_STAGGER = CRNERF_P_STAGGER;   // compile-time: a per-wave (runtime) choice would put a branch in every k-step and keep hipcc
                                               // from unrolling the tile loop, on which every ring constant depends
-constexpr int p_piece_at(int i, int stagger) {
+constexpr int p_piece_at(int i, int stagger, int used = STREAMB_USED) {
   const int sl = i % STAGE_FRAGS;
-  if (!b_tail(i)) return sl == 1 + 2 * stagger ? 0 : (sl == 5 + 2 * stagger ? 1 : -1);
+  if (!b_tail(i, used)) return sl == 1 + 2 * stagger ? 0 : (sl == 5 + 2 * stagger ? 1 : -1);
   return sl == stagger ? 0 : (sl == 2 + stagger ? 1 : -1);
 }
-constexpr bool p_schedule_ok() {
+constexpr bool p_schedule_ok(int used = STREAMB_USED) {
+  if (!b_walk_ok(used) || used % B_AHEAD != 0) return false;      // (q[i % B_AHEAD] must be in the same turn at every tile start)
   for (int st = 0; st < 2; ++st) {
     int pieces = 0, advances = 0, cursors = 0;
-    for (int i = 0; i < STREAMB_USED; ++i) {
-      if (b_cur_stage(i) != advances) return false;
-      const int rs = b_pos(i + B_AHEAD) / STAGE_FRAGS;
+    for (int i = 0; i < used; ++i) {
+      if (b_cur_stage(i, used) != advances) return false;
+      const int rs = b_pos(i + B_AHEAD, used) / STAGE_FRAGS;
       if (rs > advances || rs < i / STAGE_FRAGS) return false;   // EVERY read targets a stage whose barrier has been passed
-      if (p_piece_at(i, st) >= 0) {
-        if (p_piece_at(i, st) != pieces % P_PIECES || cursors != pieces / P_PIECES) return false;
-        if (b_cur_stage(i) != i / STAGE_FRAGS) return false;      // pieces of stage c + 3 are issued before stage c's barrier
+      if (p_piece_at(i, st, used) >= 0) {
+        if (p_piece_at(i, st, used) != pieces % P_PIECES || cursors != pieces / P_PIECES) return false;
+        if (b_cur_stage(i, used) != i / STAGE_FRAGS) return false;      // pieces of stage c + 3 are issued before stage c's barrier
         ++pieces;
       }
-      if (b_advance_at(i)) {
+      if (b_advance_at(i, used)) {
         ++advances;
         if (pieces != P_PIECES * advances) return false;          // vmcnt(4) at the barrier counts on both pieces being out
       }
-      if (b_cursor_at(i)) {
+      if (b_cursor_at(i, used)) {
         ++cursors;
         if (pieces != P_PIECES * cursors) return false;
       }
     }
-    if (advances != STAGESB_PER_PASS || cursors != STAGESB_PER_PASS) return false;
+    if (advances != b_walk_stages(used) || cursors != b_walk_stages(used)) return false;
   }
   return true;
 }
 static_assert(p_schedule_ok(), "pair-core fragment schedule violates the ring protocol");
+
+// ---- Trunk walk (the lean renderer's coarse tiles, render_fused_bf16p.hip LEAN) and the ring PHASE ---------------------------------------
+// A coarse tile of the lean renderer needs sigma only: it walks layers 1..8 (+ static_sigma in layer 8's epilogue) and leaves, TRUNKB_USED = 992
+// fragments = 62 WHOLE stages.  The walk has no tail stage and nothing special at its end: its stages 59, 60, 61 fetch "stages 62, 63, 64" = the
+// next tile's stages 0, 1, 2 from `nxt` (as stages 73, 74, 75 of a full walk fetch 76, 77, 78), its barriers sit in slot 11 of every stage, the one in
+// stage 61 opens the next tile's stage 0, and k-steps 988..991 read the next tile's first four fragments into q[0..3] behind that barrier.
+//
+// 62 mod 4 = 2: a trunk walk leaves the ring HALF A TURN on.  So the walk carries a compile-time phase PH (0 or 2; PWalk below): walk-relative stage
+// c lives in slot (c + PH) % 4 -- the ds_read offset and the index into m0s[] shift by PH slots, still constants --, and the tile after a walk of S
+// stages runs in phase (PH + S) % 4.  The renderer keeps the phase in a scalar (it toggles per trunk tile and survives across ray quads) and
+// branches between the two instantiations of a tile, once per tile.  Chosen over two idle stages that would round the trunk walk up to 64: an idle
+// stage has no MFMAs to put between the LDS-DMA of the next tile's stage 0 (whose slot is free only behind the barrier in stage 61) and the barrier
+// that waits for it, i.e. every coarse tile would end on an exposed memory round trip of all eight waves (by construction; not measured), and the
+// full, training and fine-only kernels would have had to learn about idle stages.  The price here is code size: the
+// lean kernel holds four unrolled tiles (trunk / full x phase 0 / 2) where the full kernel holds one; straight-line code that all eight waves stream
+// through together.
+//
+// Refill hazard (why a slot is rewritten only after every wave has read it), for any walk and phase; p_ring_ok() below replays it slot by slot.
+//   * The only writer of a slot is the LDS-DMA of stage F = c + 3, issued in k-steps 1 and 5 of stage c (P_STAGGER: 3 and 7) into slot (F + PH) % 4,
+//     whose tenant is stage F - 4 = c - 1 (at c = 0: the previous tile's last stage, by the phase rule above).
+//   * A wave issues its last read of stage c - 1 in k-step 11 of stage c - 1 (look-ahead B_AHEAD = 4: fragment 15), in program order IN FRONT of
+//     the barrier of that k-step, the barrier that opens stage c; every later read targets stage c or newer (p_schedule_ok: rs >= i / STAGE_FRAGS).
+//   * A wave that issues a piece of stage c + 3 is in stage c, i.e. it has left that barrier, so all eight waves have arrived at it and have issued
+//     every read of stage c - 1 they will ever issue.  LDS returns a wave's reads in order and the DMA data arrives a memory round trip after its
+//     issue, which itself is >= 6 k-steps behind the barrier: the ring has always relied on exactly this distance in mid-walk (mlp_core_bf16.h).
+//   * At the END of a trunk walk nothing else happens: stages 59..61 are ordinary stages, the slots they refill are those of stages 58..60, each
+//     left behind its own barrier as above; the next tile's stage 0 refills the slot of trunk stage 61 from its k-step 1, behind the barrier of
+//     stage 61 (k-step 987), in front of which every wave issued its last read of stage 61 (the look-ahead of k-step 987 reads fragment 991).
+//     The compositing between two tiles adds workgroup barriers and touches no ring slot.
+//   * A slot is read only when it holds the stage the reader means, and that stage has landed: the barrier in stage c waits vmcnt(4) = everything
+//     but the four pieces of stages c + 2 and c + 3, so stage c + 1 of every wave is in LDS when any wave leaves it (p_schedule_ok: rs <= advances).
+template <int USED_, int PH_>
+struct PWalk {
+  static constexpr int used = USED_, ph = PH_, stages = b_walk_stages(USED_);
+  static constexpr bool trunk = USED_ == TRUNKB_USED;
+  static_assert(USED_ == STREAMB_USED || USED_ == TRUNKB_USED, "a tile walks the whole pass or its trunk");
+  static_assert(PH_ >= 0 && PH_ < B_RING, "ring phase");
+};
+typedef PWalk<STREAMB_USED, 0> PFullWalk;
+// One wave's k-steps in program order (piece, read, barrier: the order of mma_layer_p) against the four slots.  holds[k]: the walk-relative stage
+// slot k holds or is being filled with.
+constexpr bool p_ring_ok(int used, int ph) {
+  const int S = b_walk_stages(used);
+  for (int st = 0; st < 2; ++st) {
+    int holds[B_RING] = {0, 0, 0, 0};
+    for (int c = 0; c < B_RING - 1; ++c) holds[(c + ph) % B_RING] = c;   // entry state: start(), or what the previous walk leaves (checked at the end)
+    holds[(B_RING - 1 + ph) % B_RING] = -1;                               // the previous tile's last stage; the barrier that opened stage 0 closed it
+    int advances = 0;
+    for (int i = 0; i < used; ++i) {
+      const int pc = p_piece_at(i, st, used);
+      if (pc >= 0) {
+        const int F = i / STAGE_FRAGS + B_RING - 1, slot = (F + ph) % B_RING;
+        // the tenant is stage F - 4, and this wave has left the barrier that opened stage F - 3: every wave has issued its last read of stage F - 4
+        if (pc == 0 && (holds[slot] != F - B_RING || advances < F - (B_RING - 1))) return false;
+        if (pc != 0 && holds[slot] != F) return false;
+        holds[slot] = F;
+      }
+      const int rs = b_pos(i + B_AHEAD, used) / STAGE_FRAGS;
+      if (holds[(rs + ph) % B_RING] != rs) return false;                  // the read finds the stage it means, not a refilled slot
+      if (rs < i / STAGE_FRAGS) return false;                             // and no read goes back behind a barrier that released its slot
+      if (b_advance_at(i, used)) ++advances;
+    }
+    for (int c = 0; c < B_RING - 1; ++c)                                  // exit state = the next tile's entry state in phase (ph + S) % 4
+      if (holds[(S + c + ph) % B_RING] != S + c) return false;
+    if (holds[(S + B_RING - 1 + ph) % B_RING] != S - 1 || advances != S) return false;
+  }
+  return true;
+}
+static_assert(p_schedule_ok(TRUNKB_USED), "pair-core fragment schedule of the trunk walk violates the ring protocol");
+static_assert(p_ring_ok(STREAMB_USED, 0) && p_ring_ok(STREAMB_USED, 2) && p_ring_ok(TRUNKB_USED, 0) && p_ring_ok(TRUNKB_USED, 2),
+              "a ring slot is refilled before it is read, or read before it is refilled");
+static_assert((2 * b_walk_stages(TRUNKB_USED)) % B_RING == 0 && b_walk_stages(TRUNKB_USED) % B_RING == 2, "two phases: 0 and 2");
 
 struct WeightPipeP {
   const char* base[2];   // packed streams + this wave's 2 KiB column (scalar)
@@ -84,13 +157,16 @@ struct WeightPipeP {
   uint32_t lane16;
   lds_char* lds;
 
+  // W: the walk of the tile being multiplied and its ring phase (PWalk above); F: walk-relative stage, F >= W::stages: the next tile's first stages
+  template <class W = PFullWalk>
   __device__ __forceinline__ void issue_piece(int i, int F) {   // both constant after unrolling
-    const char* src = F < STAGESB_PER_PASS ? cur : nxt;
-    if (i == 0) glds16(m0s[F % B_RING], src, voff, 0);            // writes M0; piece 1 reuses it with its instruction offset
+    const char* src = F < W::stages ? cur : nxt;
+    if (i == 0) glds16(m0s[(F + W::ph) % B_RING], src, voff, 0);  // writes M0; piece 1 reuses it with its instruction offset
     else glds16_more(src, voff, FRAG_BYTES);
   }
+  template <class W = PFullWalk>
   __device__ __forceinline__ void cursor_update(int F) {
-    voff = (F + 1 == STAGESB_PER_PASS) ? rd_base - LDS_RING : voff + STAGE_BYTES;   // = lane16, from the register that is live in every k-step
+    voff = (F + 1 == W::stages) ? rd_base - LDS_RING : voff + STAGE_BYTES;   // = lane16, from the register that is live in every k-step
     asm volatile("" : "+v"(voff));                                                  // (lane16 itself is spilled in the training twin and came back behind a vmcnt(0))
   }
   // all_landed (training twin): the first tile's barriers use store windows that assume a previous tile; with its first three stages
@@ -130,8 +206,9 @@ struct WeightPipeP {
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
+  template <int PH = 0>
   __device__ __forceinline__ u32x4 read(int pos) const {
-    return *(const __attribute__((address_space(3))) u32x4*)(lds + rd_base + ((pos / STAGE_FRAGS) % B_RING) * STAGE_BYTES +
+    return *(const __attribute__((address_space(3))) u32x4*)(lds + rd_base + ((pos / STAGE_FRAGS + PH) % B_RING) * STAGE_BYTES +
                                                               (pos % STAGE_FRAGS) * FRAG_BYTES);
   }
   __device__ __forceinline__ void prime(u32x4 (&q)[B_AHEAD]) const {
@@ -455,7 +532,7 @@ __device__ __forceinline__ void load_bias_into(f32x16& acc, const lds_float* bia
 // in accs[G & 1] --, PT: the previous layer's last tile, whose epilogue `prev` runs behind this layer's first tile).  On entry
 // accs[G0 & 1] holds the bias of tile 0; the bias of each following tile (and of the NEXT layer's tile 0, from next_bias) is
 // read into the other accumulator in the tile's last two k-steps, after the epilogue quarters have drained it.
-template <int NT, int NSA, int NSB, int FBASE, int G0, int PT, int NA, int NB, class PREV, class EPI, class SV>
+template <int NT, int NSA, int NSB, int FBASE, int G0, int PT, class W, int NA, int NB, class PREV, class EPI, class SV>
 __device__ __forceinline__ void mma_layer_p(WeightPipeP& p, const u32x4 (&srcA)[NA], const u32x4 (&srcB)[NB], u32x4 (&q)[B_AHEAD],
                                             f32x16 (&accs)[2], const lds_float* bias, const lds_float* next_bias, int h, PREV& prev,
                                             EPI& epi, SV& sv) {
@@ -480,8 +557,8 @@ __device__ __forceinline__ void mma_layer_p(WeightPipeP& p, const u32x4 (&srcA)[
       const u32x4 b = s < NSA ? srcA[s < NSA ? s : 0] : srcB[s < NSA ? 0 : s - NSA];
       accs[cur] = CRNERF_MFMA_P(af, b, accs[cur]);
       __builtin_amdgcn_sched_barrier(0);   // MFMA first, its fillers behind it
-      if (p_piece_at(i, P_STAGGER) >= 0) p.issue_piece(p_piece_at(i, P_STAGGER), i / STAGE_FRAGS + B_RING - 1);
-      q[i % B_AHEAD] = p.read(b_pos(i + B_AHEAD));
+      if (p_piece_at(i, P_STAGGER, W::used) >= 0) p.template issue_piece<W>(p_piece_at(i, P_STAGGER, W::used), i / STAGE_FRAGS + B_RING - 1);
+      q[i % B_AHEAD] = p.template read<W::ph>(b_pos(i + B_AHEAD, W::used));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < count; ++u) {
@@ -511,8 +588,8 @@ __device__ __forceinline__ void mma_layer_p(WeightPipeP& p, const u32x4 (&srcA)[
         const lds_float* nb = (T + 1 < NT) ? bias : next_bias;
         load_bias_into(accs[cur ^ 1], nb, (T + 1 < NT) ? T + 1 : 0, h, s - (NS - 2));
       }
-      if (b_advance_at(i)) p.advance();
-      if (b_cursor_at(i)) p.cursor_update(i / STAGE_FRAGS + B_RING - 1);
+      if (b_advance_at(i, W::used)) p.advance();
+      if (b_cursor_at(i, W::used)) p.template cursor_update<W>(i / STAGE_FRAGS + B_RING - 1);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -521,7 +598,10 @@ __device__ __forceinline__ void mma_layer_p(WeightPipeP& p, const u32x4 (&srcA)[
 // One 32-point tile through one model.  pe[s]: the xyz embedding as B operands (posenc_b); dirsrc: this lane half's 2 x 16 bytes
 // of the ray's direction embedding, parked in LDS.  Returns feat[t][r] = rgb feature 32t + 8(r>>2) + 4h + (r&3) of point p, and
 // sigma (valid in both lane halves).
-template <class SV = NoSaveP>
+// W (PWalk): the walk and the ring phase.  W::trunk (the lean renderer's coarse tiles): layers 1..8 and static_sigma only -- feat and dirsrc are not
+// touched, sigma is bit-identical to the full tile's (the same fmaf chain in the same order, the same half-lane exchange, the same softplus), and in
+// the fp16 build sv.g returns the point's range guard over the xyz embedding and the outputs of layers 1..8, merged over both lane halves.
+template <class W = PFullWalk, class SV = NoSaveP>
 __device__ __forceinline__ void mlp_tile_p(WeightPipeP& p, int model, int next_model, const u32x4 (&pe)[KS_XYZ], const lds_char* dirsrc,
                                            f32x16 (&feat)[2], float& sigma, int h, u32x4 (&q)[B_AHEAD], PhaseTimer& tm, SV& sv) {
   p.begin_tile(next_model);
@@ -544,23 +624,56 @@ __device__ __forceinline__ void mlp_tile_p(WeightPipeP& p, int model, int next_m
   SigmaEpiP<SV> e8(actB, sg, C + C_WSIG, h, sv);
   RgbEpiP ergb(feat);
   eA.slot(0);
-  mma_layer_p<8, KS_XYZ, 0, OFFB_L1, 0, 0>(p, pe, pe, q, accs, B1, B1 + 1 * W_HIDDEN, h, none, eA, sv);                                // xyz_encoding_1
+  mma_layer_p<8, KS_XYZ, 0, OFFB_L1, 0, 0, W>(p, pe, pe, q, accs, B1, B1 + 1 * W_HIDDEN, h, none, eA, sv);                                // xyz_encoding_1
   eB.slot(1);
-  mma_layer_p<8, KS_HID, 0, OFFB_L2, 8, 7>(p, actA, actA, q, accs, B1 + 1 * W_HIDDEN, B1 + 2 * W_HIDDEN, h, eA, eB, sv);               // 2
+  mma_layer_p<8, KS_HID, 0, OFFB_L2, 8, 7, W>(p, actA, actA, q, accs, B1 + 1 * W_HIDDEN, B1 + 2 * W_HIDDEN, h, eA, eB, sv);               // 2
   eA.slot(2);
-  mma_layer_p<8, KS_HID, 0, OFFB_L2 + FB_HID, 16, 7>(p, actB, actB, q, accs, B1 + 2 * W_HIDDEN, B1 + 3 * W_HIDDEN, h, eB, eA, sv);     // 3
+  mma_layer_p<8, KS_HID, 0, OFFB_L2 + FB_HID, 16, 7, W>(p, actB, actB, q, accs, B1 + 2 * W_HIDDEN, B1 + 3 * W_HIDDEN, h, eB, eA, sv);     // 3
   eB.slot(3);
-  mma_layer_p<8, KS_HID, 0, OFFB_L2 + 2 * FB_HID, 24, 7>(p, actA, actA, q, accs, B1 + 3 * W_HIDDEN, B1 + 4 * W_HIDDEN, h, eA, eB, sv); // 4
+  mma_layer_p<8, KS_HID, 0, OFFB_L2 + 2 * FB_HID, 24, 7, W>(p, actA, actA, q, accs, B1 + 3 * W_HIDDEN, B1 + 4 * W_HIDDEN, h, eA, eB, sv); // 4
   eA.slot(4);
-  mma_layer_p<8, KS_XYZ, KS_HID, OFFB_L5, 32, 7>(p, pe, actB, q, accs, B1 + 4 * W_HIDDEN, B1 + 5 * W_HIDDEN, h, eB, eA, sv);           // 5 = Linear(cat[xyz, h])
+  mma_layer_p<8, KS_XYZ, KS_HID, OFFB_L5, 32, 7, W>(p, pe, actB, q, accs, B1 + 4 * W_HIDDEN, B1 + 5 * W_HIDDEN, h, eB, eA, sv);           // 5 = Linear(cat[xyz, h])
   eB.slot(5);
-  mma_layer_p<8, KS_HID, 0, OFFB_L6, 40, 7>(p, actA, actA, q, accs, B1 + 5 * W_HIDDEN, B1 + 6 * W_HIDDEN, h, eA, eB, sv);              // 6
+  mma_layer_p<8, KS_HID, 0, OFFB_L6, 40, 7, W>(p, actA, actA, q, accs, B1 + 5 * W_HIDDEN, B1 + 6 * W_HIDDEN, h, eA, eB, sv);              // 6
   eA.slot(6);
-  mma_layer_p<8, KS_HID, 0, OFFB_L6 + FB_HID, 48, 7>(p, actB, actB, q, accs, B1 + 6 * W_HIDDEN, B1 + 7 * W_HIDDEN, h, eB, eA, sv);     // 7
+  mma_layer_p<8, KS_HID, 0, OFFB_L6 + FB_HID, 48, 7, W>(p, actB, actB, q, accs, B1 + 6 * W_HIDDEN, B1 + 7 * W_HIDDEN, h, eB, eA, sv);     // 7
   e8.slot(7);
-  mma_layer_p<8, KS_HID, 0, OFFB_L6 + 2 * FB_HID, 56, 7>(p, actA, actA, q, accs, B1 + 7 * W_HIDDEN, C + C_BFIN, h, eA, e8, sv);        // 8 (+ static_sigma)
+  mma_layer_p<8, KS_HID, 0, OFFB_L6 + 2 * FB_HID, 56, 7, W>(p, actA, actA, q, accs, B1 + 7 * W_HIDDEN, C + C_BFIN, h, eA, e8, sv);        // 8 (+ static_sigma)
+  if constexpr (W::trunk) {
+    static_assert(!SV::on, "the trunk walk is an inference walk");
+    tm.tick(T_MMA);
+    // layer 8's last tile: its epilogue (which carries the sigma dot product) has no next tile to hide behind; drained in place, quarters in the
+    // order the full tile retires them behind xyz_encoding_final's first tile
+    e8.prefetch(7);
+    // the quarters read the accumulator of layer 8's LAST MFMA, in the fp16 build from inside an asm statement (v_cvt_pk_f16_f32), which hipcc does not
+    // pad: 12 wait states behind a 32x32x16 MFMA (tools/isa_audit.py "mfma->any"; the full tile has 16 k-steps in between)
+    asm volatile("s_nop 15" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int qc = 0; qc < 8; ++qc) e8.finish(7, qc, accs[(56 + 7) & 1]);
+    sg += __shfl_xor(sg, 32);
+    sigma = softplus_fast(sg + C[C_BSIG]);
+#if CRNERF_P_F16
+    if constexpr (SV::guard) {
+#pragma unroll
+      for (int s = 0; s < KS_XYZ; ++s)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) sv.g = guard_max_signed(sv.g, pe[s][d]);
+      sv.g = guard_max(sv.g, (uint32_t)__shfl_xor((int)sv.g, 32));
+      if (guard_tripped(sv.g)) sigma = __uint_as_float(0x7fc00000u);   // as the full tile: the sample composites as transparent
+    }
+#endif
+    // feat is not this walk's to return, but it must not be left undefined: where the renderer's control flow joins the full tile's, an undefined
+    // feat is 32 registers hipcc carries THROUGH the trunk walk in scratch (measured: ~3.7 k cycles per tile in front of the tile, 32 reloads behind it)
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) feat[t][r] = 0.0f;
+    tm.tick(T_SIGMA);
+    return;
+  }
   efin.slot(8);
-  mma_layer_p<8, KS_HID, 0, OFFB_FIN, 64, 7>(p, actB, actB, q, accs, C + C_BFIN, C + C_BDIR, h, e8, efin, sv);                         // xyz_encoding_final
+  mma_layer_p<8, KS_HID, 0, OFFB_FIN, 64, 7, W>(p, actB, actB, q, accs, C + C_BFIN, C + C_BDIR, h, e8, efin, sv);                         // xyz_encoding_final
   tm.tick(T_MMA);
   sg += __shfl_xor(sg, 32);
   sigma = softplus_fast(sg + C[C_BSIG]);
@@ -581,8 +694,8 @@ __device__ __forceinline__ void mlp_tile_p(WeightPipeP& p, int model, int next_m
 #endif
   tm.tick(T_SIGMA);
   eB.slot(9);
-  mma_layer_p<4, KS_HID, KS_DIR, OFFB_DIR, 72, 7>(p, actA, dv, q, accs, C + C_BDIR, C + C_BRGB, h, efin, eB, sv);                      // dir_encoding
-  mma_layer_p<2, KS_HALF, 0, OFFB_RGB, 76, 3>(p, actB, actB, q, accs, C + C_BRGB, C + C_BRGB, h, eB, ergb, sv);                         // static_rgb
+  mma_layer_p<4, KS_HID, KS_DIR, OFFB_DIR, 72, 7, W>(p, actA, dv, q, accs, C + C_BDIR, C + C_BRGB, h, efin, eB, sv);                      // dir_encoding
+  mma_layer_p<2, KS_HALF, 0, OFFB_RGB, 76, 3, W>(p, actB, actB, q, accs, C + C_BRGB, C + C_BRGB, h, eB, ergb, sv);                         // static_rgb
   tm.tick(T_MMA);
 #pragma unroll
   for (int qc = 0; qc < 8; ++qc) {   // rgb's last tile: nothing left to hide it behind

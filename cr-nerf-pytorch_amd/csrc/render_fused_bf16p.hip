@@ -21,6 +21,8 @@
 // the inference kernel only -- the training twin and the fine-only kernel stay bf16
 #ifndef CRNERF_P_RENDER_KERNEL
 #define CRNERF_P_RENDER_KERNEL render_rays_bf16p_kernel
+#define CRNERF_P_RENDER_LEAN_KERNEL render_rays_bf16p_lean_kernel
+#define CRNERF_P_RENDER_LEAN_NAME "render_rays_bf16p_lean_kernel"
 #define CRNERF_P_RENDER_LAUNCH launch_render_rays_bf16p
 #define CRNERF_P_RENDER_SCHED crnerf_sched_bf16p
 #define CRNERF_P_RENDER_NAME "render_rays_bf16p_kernel"
@@ -42,6 +44,9 @@ struct RenderParamsP {
   const float* wc_in;    // render_rays_bf16p_fine_kernel: the coarse pass's weights [R, Nc], computed elsewhere (crnerf_render_rays_bf16_fine)
 };
 
+#if CRNERF_P_F16
+constexpr int LEAN_TRIP_SLOT = 65;   // PairScratch::xfeat[65] (free: [0, 64] carry the feature / depth exchange): non-zero = a coarse point of the pair's ray left fp16's range (lean kernel)
+#endif
 constexpr int LDS_DIR_P = LDS_SCRATCH_P + 4 * PAIR_BYTES;        // 8 waves x 64 B: the ray's direction embedding as B operands
 constexpr int LDS_QSLOT_P = LDS_DIR_P + P_WAVES * 64;
 constexpr int LDS_TOTAL_P = LDS_QSLOT_P + 16;
@@ -111,7 +116,15 @@ __device__ __forceinline__ float fold32(float (&v)[32], int p) {
 // FINE_ONLY (crnerf_render_rays_bf16_fine, precision "bf16_hc"): the coarse pass has been rendered by another core (fp32-accurate, so that the fine
 // depths are the fp32 reference's); its weights come in through a.wc_in, the kernel runs sample_pdf + merge on them and the FINE pass only --
 // packed0 == packed1 == the fine model, the ring starts on model 1 and never leaves it.
-template <class HOOK, bool FINE_ONLY = false>
+// LEAN (crnerf_render_rays_lean_bf16 / _f16): the inference render that keeps only what an image needs.  The coarse pass exists for its compositing
+// WEIGHTS alone (sample_pdf's input), so its tiles walk the trunk (mlp_core_bf16p.h "Trunk walk": layers 1..8 + static_sigma, 992 of 1,208 fragments),
+// alpha, the prefix product and the pair's exchange of it stay, and the feature / depth sums, their exchange and every store of the coarse pass are gone;
+// weights_fine is not stored either.  sample_pdf, the merge and the fine pass are the full kernel's: feature_fine, depth_fine and z_fine are bit-identical.
+// A trunk walk turns the ring by 62 stages = half a turn, so the kernel carries the ring phase (0 or 2) in a scalar and every tile exists per phase.
+// fp16 build: the NaN feature_coarse row that marks a ray whose coarse pass left fp16's range does not exist here, so the mark moves: the range guard of
+// the trunk tiles (xyz embedding, outputs of layers 1..8) is ORed over the coarse tiles, the wave and the pair, and a marked ray leaves with its whole
+// feature_fine row and its depth_fine NaN -- never with finite numbers sampled from a wrong pdf.
+template <class HOOK, bool FINE_ONLY = false, bool LEAN = false>
 __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, const HOOK& hook) {
 #ifdef CRNERF_TIMING
   if (threadIdx.x == 0 && blockIdx.x < 1024) crnerf_wg_times_p[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -133,7 +146,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
   // is marked NaN where crnerf_render_rays_f32x3_repair looks for it -- the h2 kernels' convention (render_fused_x3.hip)
   if ((__float_as_uint(((const lds_float*)(lds + LDS_CONST0))[H2_FLAG_WORD]) | __float_as_uint(((const lds_float*)(lds + LDS_CONST1))[H2_FLAG_WORD])) != 0u) {
     for (long rr = (long)blockIdx.x * 512 + threadIdx.x; rr < a.R; rr += (long)gridDim.x * 512) {
-      a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+      if constexpr (!LEAN) a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
       if (a.Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
     }
     return;
@@ -152,6 +165,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
   __attribute__((address_space(3))) unsigned int* qslot = (__attribute__((address_space(3))) unsigned int*)(lds + LDS_QSLOT_P);
   const long quads = (a.R + 3) / 4;
   long quad = blockIdx.x;
+  int ring_ph = 0;   // LEAN: the ring phase of the next tile (scalar; 0 or 2), toggled by every trunk walk
 #pragma unroll 1
   for (int it = 0; a.sched ? quad < quads : it < a.iters; ++it) {
     unsigned int nxt = 0;
@@ -177,6 +191,9 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
     if constexpr (FINE_ONLY) {
       for (int n = lane128; n < Nc; n += 128) scr.wc[n] = a.wc_in[r * Nc + n];
     }
+#if CRNERF_P_F16
+    if (LEAN && lane128 == 0) scr.xfeat[LEAN_TRIP_SLOT] = 0.0f;   // (last read before the barrier that ended the previous quad)
+#endif
     wg_barrier();
 
     const int npass = Ni > 0 ? 2 : 1;
@@ -193,7 +210,8 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
       const int N = pass ? Nf : Nc;
       const lds_float* zsrc = pass ? scr.zs : scr.zc;
       const float* noise_row = pass ? (a.noise_f ? a.noise_f + r * Nf : nullptr) : (a.noise_c ? a.noise_c + r * Nc : nullptr);
-      float* weights_row = pass ? a.weights_f + r * Nf : a.weights_c + r * Nc;
+      float* weights_row = LEAN ? nullptr : (pass ? a.weights_f + r * Nf : a.weights_c + r * Nc);
+      const bool compose = !LEAN || pass;   // wave-uniform, and the same in all eight waves
       double carry = 1.0;
       float fsum = 0.0f, dacc = 0.0f;
       const int steps = (N + 63) >> 6;
@@ -222,7 +240,22 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
           for (int s = 0; s < KS_DIR; ++s)
             __builtin_amdgcn_raw_buffer_store_b128(*(const __attribute__((address_space(3))) u32x4*)(dirbuf + 16 * h + 32 * s), xr, (int)(xo + 32u * (KS_XYZ + s)), 0, 0);
         }
-        mlp_tile_p(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+        if constexpr (LEAN) {
+          if (pass == 0) {   // trunk walk; the ring moves on by half a turn
+            if (ring_ph) mlp_tile_p<PWalk<TRUNKB_USED, 2>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+            else mlp_tile_p<PWalk<TRUNKB_USED, 0>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+            ring_ph ^= 2;
+#if CRNERF_P_F16
+            // the trunk tile poisons sigma by this bit pattern and by nothing else (softplus of a finite sum is finite): mark the ray in the pair's scratch
+            if (__float_as_uint(sigma) == 0x7fc00000u) scr.xfeat[LEAN_TRIP_SLOT] = 1.0f;
+#endif
+          } else {
+            if (ring_ph) mlp_tile_p<PWalk<STREAMB_USED, 2>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+            else mlp_tile_p<PWalk<STREAMB_USED, 0>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+          }
+        } else {
+          mlp_tile_p(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
+        }
         if constexpr (HOOK::on) {   // raw MLP output row (rgb features after the sigmoid, sigma after the softplus): what compositing consumes.
           // 8 x 16 B + sigma, unconditional (SAVE_TILE_BURST); rows are 260 B apart: dword-aligned 16-byte stores
           const long P = hook.R * N;
@@ -258,31 +291,44 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
         const float Tr = (float)(half ? carry * prod_a * excl : carry * excl);
         carry = carry * prod_a * prod_b;
         const float w = alpha * Tr;
-        float v[32];
+        if (compose) {
+          float v[32];
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+          for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) v[16 * t + e] = w * feat[t][e];
-        fsum += fold32(v, p);
-        dacc += w * zn;
+            for (int e = 0; e < 16; ++e) v[16 * t + e] = w * feat[t][e];
+          fsum += fold32(v, p);
+          dacc += w * zn;
+        }
         if (valid && h == 0) {
-          if (ray_ok) weights_row[n] = w;
+          if (!LEAN && ray_ok) weights_row[n] = w;
           if (pass == 0) scr.wc[n] = w;
         }
         tm.tick(T_COMPOSITE);
       }
       // lane (p, h) holds the wave's sum of feature 32(p>>4) + 8((p&15)>>2) + 4h + (p&3); pair combine through LDS
       const int fidx = 32 * (p >> 4) + 8 * ((p & 15) >> 2) + 4 * h + (p & 3);
+      if (compose) {
 #pragma unroll
-      for (int d = 16; d >= 1; d >>= 1) dacc += __shfl_xor(dacc, d);
-      if (half == 1) {
-        scr.xfeat[fidx] = fsum;
-        if (lane == 0) scr.xfeat[64] = dacc;
+        for (int d = 16; d >= 1; d >>= 1) dacc += __shfl_xor(dacc, d);
+        if (half == 1) {
+          scr.xfeat[fidx] = fsum;
+          if (lane == 0) scr.xfeat[64] = dacc;
+        }
       }
-      wg_barrier();
-      if (half == 0 && ray_ok) {
-        ((pass ? a.feature_f : a.feature_c) + r * FEAT_DIM)[fidx] = fsum + scr.xfeat[fidx];
-        if (lane == 0) (pass ? a.depth_f : a.depth_c)[r] = dacc + scr.xfeat[64];
+      wg_barrier();   // (a lean coarse pass too: the last step's scr.wc[] must be in LDS before sample_pdf_pair reads it)
+      if (compose && half == 0 && ray_ok) {
+#if CRNERF_P_F16
+        // the coarse pass of this ray (either wave's tiles, marked a pass ago) left fp16's range: the fine numbers come from a wrong pdf
+        if (LEAN && scr.xfeat[LEAN_TRIP_SLOT] != 0.0f) {
+          (a.feature_f + r * FEAT_DIM)[fidx] = __uint_as_float(0x7fc00000u);
+          if (lane == 0) a.depth_f[r] = __uint_as_float(0x7fc00000u);
+        } else
+#endif
+        {
+          ((pass ? a.feature_f : a.feature_c) + r * FEAT_DIM)[fidx] = fsum + scr.xfeat[fidx];
+          if (lane == 0) (pass ? a.depth_f : a.depth_c)[r] = dacc + scr.xfeat[64];
+        }
       }
       tm.tick(T_X5);
       if (pass == 0 && Ni > 0) {
@@ -313,6 +359,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
 }
 
 __global__ __launch_bounds__(512, 2) void CRNERF_P_RENDER_KERNEL(RenderParamsP a) { render_rays_bf16p_body(a, NoHookP()); }
+__global__ __launch_bounds__(512, 2) void CRNERF_P_RENDER_LEAN_KERNEL(RenderParamsP a) { render_rays_bf16p_body<NoHookP, false, true>(a, NoHookP()); }
 #if !CRNERF_P_F16
 __global__ __launch_bounds__(512, 2) void render_rays_train_bf16p_kernel(RenderParamsP a, TrainHookP hook) { render_rays_bf16p_body(a, hook); }
 __global__ __launch_bounds__(512, 2) void render_rays_bf16p_fine_kernel(RenderParamsP a) { render_rays_bf16p_body<NoHookP, true>(a, NoHookP()); }
@@ -342,6 +389,12 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   const GridPlan plan = plan_grid((a.R + 3) / 4);   // one workgroup per CU, persistent over ray quads
   k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)CRNERF_P_RENDER_SCHED) : nullptr;
+  if (a.lean) {   // crnerf_render_rays_lean_bf16 / _f16: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
+    if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
+    if (a.fine_only || a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
+    k.weights_c = k.feature_c = k.depth_c = k.weights_f = nullptr;
+    return launch_kernel(CRNERF_P_RENDER_LEAN_KERNEL, CRNERF_P_RENDER_LEAN_NAME, plan.grid, 512, LDS_TOTAL_P, stream, k);
+  }
 #if !CRNERF_P_F16
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_bf16)
     if (int rc = check_train_state("render_rays_train_bf16", a)) return rc;

@@ -4,6 +4,8 @@
 // crnerf_pack_mlp_weights_f16.
 #define CRNERF_P_F16 1
 #define CRNERF_P_RENDER_KERNEL render_rays_f16p_kernel
+#define CRNERF_P_RENDER_LEAN_KERNEL render_rays_f16p_lean_kernel
+#define CRNERF_P_RENDER_LEAN_NAME "render_rays_f16p_lean_kernel"
 #define CRNERF_P_RENDER_LAUNCH launch_render_rays_f16p
 #define CRNERF_P_RENDER_SCHED crnerf_sched_f16p
 #define CRNERF_P_RENDER_NAME "render_rays_f16p_kernel"

@@ -139,9 +139,10 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     fp32 accumulation; autograd.set_wgrad_precision("bf16"): weight gradients only) -- neither has a counterpart in the reference.
     lean=True (another keyword of this mirror; inference only, ValueError in grad mode with trainable models): the caller reads the fine image alone.
     With N_importance > 0 the result holds exactly feature_<fine.typ>, depth_<fine.typ> and (under its usual condition) feature_fine_random, with
-    the values of the ordinary call.  precision "f32", no pertubeCord, 3 <= N_samples <= 256, N_importance <= 256: crnerf_render_rays_lean_f32 --
-    the coarse pass stops behind the sigma head and nothing of it goes to HBM; every other case renders as without the flag and drops the other
-    keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
+    the values of the ordinary call.  precision "f32", "bf16" or "f16" (and "bf16_hc" / "bf16_fc" where they fall back to plain "bf16"), no pertubeCord,
+    3 <= N_samples <= 256, N_importance <= 256: crnerf_render_rays_lean_f32 / _lean_bf16 / _lean_f16 -- the coarse pass stops behind the sigma head
+    and nothing of it goes to HBM ("f16": a ray whose coarse pass left fp16's range has a NaN feature / depth instead of the full call's NaN
+    feature_coarse row); every other case renders as without the flag and drops the other keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
     args = kwargs['args']
     jitter = bool(getattr(args, 'pertubeCord', False))
     if getattr(args, 'nerf_out_dim', 64) != 64:
@@ -215,7 +216,7 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
                               N_samples, N_importance, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse,
                               z_steps=tables[0], u=u if u is not None else tables[1],
                               noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std), precision=precision,
-                              lean=lean and precision == "f32" and N_samples >= 3)
+                              lean=lean and precision in ("f32", "bf16", "f16") and N_samples >= 3)
 
     if lean:    # the lean kernel wrote nothing else; the other paths rendered as usual and their other tensors are dropped here
         typ_f = fine.typ

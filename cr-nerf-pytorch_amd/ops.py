@@ -479,6 +479,10 @@ def _render_args(rays, inputs, noise_std, use_disp, Nc, Ni, out):
     return a, keep
 
 
+# the lean entry point of a precision (crnerf.h; crnerf_lean.h for the pair core's two builds)
+_LEAN_RENDER = {"f32": "crnerf_render_rays_lean_f32", "bf16": "crnerf_render_rays_lean_bf16", "f16": "crnerf_render_rays_lean_f16"}
+
+
 def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
                 noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, precision="f32", train=False, launcher=False, rng=None,
                 repair_x3=None, lean=False):
@@ -496,18 +500,24 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     precision="f16": crnerf_render_rays_f16 (packs from pack_mlp_weights(..., precision="f16"); inference only) -- a ray with a point whose operands
     left fp16's range has a NaN feature row.  repair_x3=(coarse x3 pack, fine x3 pack or None): crnerf_render_rays_f32x3_repair re-renders those
     ray quads in the same call, as precision="auto" does behind the h2 core.
-    lean=True (precision="f32", inference, n_importance > 0): crnerf_render_rays_lean_f32 -- the coarse pass stops behind the sigma head and nothing of
-    it reaches HBM; the dict holds feature_fine, depth_fine and (want_z_fine) z_fine only, bit-identical to the full call's."""
+    lean=True (precision="f32", "bf16" or "f16"; inference, n_importance > 0): crnerf_render_rays_lean_f32 / _lean_bf16 / _lean_f16 (include/crnerf.h,
+    include/crnerf_lean.h) -- the coarse pass stops behind the sigma head and nothing of it reaches HBM; the dict holds feature_fine, depth_fine and
+    (want_z_fine) z_fine only, bit-identical to the full call's.  "f16": there is no feature_coarse row to carry the range guard's NaN, so a ray whose
+    coarse pass left fp16's range comes back with its whole feature_fine row and its depth_fine NaN (and repair_x3=, which looks for the NaN rows of
+    the full call, is refused)."""
     name = resolve(precision)
-    lib = _lib.load()
     repair = None
     if lean:
         if train or rng is not None:
             raise ValueError("crnerf_amd: lean=True is an inference render (no training twin, no in-kernel draws: hand them over as tensors)")
-        if name != "f32":
-            raise ValueError("crnerf_amd: lean=True exists for precision='f32' (the trunk-only coarse walk is built on the fp32 core), got %r" % (name,))
+        if name not in _LEAN_RENDER:
+            raise ValueError("crnerf_amd: lean=True exists for precision='f32', 'bf16' and 'f16' (the trunk-only coarse walk is built on the fp32 core "
+                             "and on the pair core), got %r" % (name,))
         if int(n_importance) <= 0:
             raise ValueError("crnerf_amd: lean=True needs n_importance > 0 (it returns the fine pass only)")
+        if repair_x3 is not None:
+            raise ValueError("crnerf_amd: lean=True and repair_x3= are exclusive (the repair re-renders whole rays, coarse outputs included)")
+    lib = _lib.load()
     if repair_x3 is not None:
         if name != "f16":
             raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 packs)")
@@ -581,7 +591,7 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
         if a2 is not None:        # precision="auto": the ray quads the h2 twin poisoned, once more on the scale-free core -- outputs AND saved state
             _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), *saved, _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
         return out
-    fn_name = "crnerf_render_rays_lean_f32" if lean else core.render
+    fn_name = _LEAN_RENDER[name] if lean else core.render
     fn, a2 = getattr(lib, fn_name), _repair_args(a, repair)
     # the argument structs hold raw pointers: a launcher that outlives this call keeps EVERY tensor behind them alive (the outputs too: a caller that
     # drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
