@@ -269,6 +269,26 @@ LEAN_SIGNATURES = {
 }
 
 
+class SweepDecodeArgs(ctypes.Structure):
+    """struct crnerf_sweep_decode_args (include/crnerf_sweep.h)."""
+    _fields_ = [
+        ("content", _c_fp), ("HW", ctypes.c_int64), ("stats", _c_fp), ("style_HW", ctypes.c_int64),
+        ("S", ctypes.c_int32), ("out_kind", ctypes.c_int32),
+        ("weights", ctypes.POINTER(ctypes.c_void_p)), ("workspace", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("style_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64),
+    ]
+
+
+SWEEP_MAX_STYLES, SWEEP_STATS_FLOATS = 16, 1088          # CRNERF_SWEEP_MAX_STYLES, CRNERF_SWEEP_STATS_FLOATS
+SWEEP_OUT_F32, SWEEP_OUT_U8 = 0, 1                       # CRNERF_SWEEP_OUT_*
+# One row per symbol of the companion header include/crnerf_sweep.h (the appearance sweep: S styles' statistics once, one content grid decoded
+# under all of them), bound by the same loader; tests/test_sweep_host.py holds it to that header's prototypes.
+SWEEP_SIGNATURES = {
+    "crnerf_crossray_style_stats_f32": (i32, [vp, i32, i64, i64, pp, vp, vp, vp]),
+    "crnerf_crossray_decode_multi_f32": (i32, [ctypes.POINTER(SweepDecodeArgs), vp]),
+}
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -286,8 +306,8 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()):
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h
+        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h / crnerf_sweep.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

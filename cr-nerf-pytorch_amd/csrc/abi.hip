@@ -7,6 +7,7 @@
 #include "../../include/crnerf.h"
 #include "../../include/crnerf_blender.h"
 #include "../../include/crnerf_lean.h"
+#include "../../include/crnerf_sweep.h"
 #include "crossray.h"
 #include "kernels.h"
 #include "layout.h"
@@ -660,6 +661,45 @@ int crnerf_crossray_apply_f32(const float* x, int64_t HW, const float* affine, f
   if (HW == 0) return 0;
   REQUIRE(x, "x"); REQUIRE(affine, "affine"); REQUIRE(rgb, "rgb");
   return launch_crossray_apply(x, (long)HW, affine, rgb, (long)plane_stride, (hipStream_t)stream);
+}
+
+// include/crnerf_sweep.h
+static_assert(CRNERF_SWEEP_MAX_STYLES == SWEEP_MAX_STYLES && CRNERF_SWEEP_STATS_FLOATS == SWEEP_STATS_FLOATS, "crnerf_sweep.h and crossray.h disagree");
+
+int crnerf_crossray_style_stats_f32(const float* styles, int32_t S, int64_t HWs, int64_t content_HW, const float* const* w, void* workspace,
+                                    float* stats, void* stream) {
+  if (S < 0 || HWs < 0 || content_HW < 0) return set_error(CRNERF_ERR_SHAPE, "crossray_style_stats: negative size");
+  if (S == 0) return 0;
+  if (S > CRNERF_SWEEP_MAX_STYLES) return set_error(CRNERF_ERR_SHAPE, "crossray_style_stats: S exceeds CRNERF_SWEEP_MAX_STYLES (split the sweep)");
+  REQUIRE(styles, "styles"); REQUIRE(w, "weights"); REQUIRE(workspace, "workspace"); REQUIRE(stats, "stats");
+  if (HWs == 0) return set_error(CRNERF_ERR_SHAPE, "crossray_style_stats: empty style grid");
+  if (content_HW == 0) return set_error(CRNERF_ERR_SHAPE, "crossray_style_stats: content_HW must be the size of the content grids (>= 1)");
+  if (!all_set(w, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_style_stats: a weight pointer is NULL");
+  const CnnTensors snet{w[0], w[1], w[2], w[3], w[4], w[5]};
+  return launch_crossray_style_stats(styles, S, (long)HWs, (long)content_HW, snet, w[6], w[7], workspace, stats, (hipStream_t)stream);
+}
+
+int crnerf_crossray_decode_multi_f32(const crnerf_sweep_decode_args* a, void* stream) {
+  REQUIRE(a, "args");
+  if (a->S < 0 || a->HW < 0 || a->style_HW < 0) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_multi: negative size");
+  if (a->S == 0 || a->HW == 0) return 0;
+  if (a->S > CRNERF_SWEEP_MAX_STYLES) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_multi: S exceeds CRNERF_SWEEP_MAX_STYLES (split the sweep)");
+  if (a->out_kind != CRNERF_SWEEP_OUT_F32 && a->out_kind != CRNERF_SWEEP_OUT_U8)
+    return set_error(CRNERF_ERR_CONFIG, "crossray_decode_multi: out_kind must be CRNERF_SWEEP_OUT_F32 or CRNERF_SWEEP_OUT_U8");
+  REQUIRE(a->content, "content"); REQUIRE(a->stats, "stats"); REQUIRE(a->weights, "weights"); REQUIRE(a->workspace, "workspace"); REQUIRE(a->out, "out");
+  if (a->style_HW == 0) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_multi: style_HW must be the size of the style grids behind stats (>= 1)");
+  if (!all_set(a->weights, CRNERF_DECODER_TENSORS)) return set_error(CRNERF_ERR_NULL, "crossray_decode_multi: a weight pointer is NULL");
+  const bool f32 = a->out_kind == CRNERF_SWEEP_OUT_F32;
+  if (f32 && a->plane_stride < a->HW) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_multi: plane_stride is smaller than HW");
+  const int64_t image = f32 ? 2 * a->plane_stride + a->HW : 3 * a->HW;
+  if (a->S > 1 && a->style_stride < image) return set_error(CRNERF_ERR_SHAPE, "crossray_decode_multi: style_stride makes the images overlap");
+  const float* const* w = a->weights;
+  SweepArgs d;
+  d.content = a->content; d.HW = (long)a->HW; d.stats = a->stats; d.style_HW = (long)a->style_HW; d.S = a->S;
+  d.cnet = CnnTensors{w[8], w[9], w[10], w[11], w[12], w[13]}; d.cnet_fc_w = w[14]; d.cnet_fc_b = w[15];
+  d.lin = FoldTensors{w[16], w[17], w[18], w[19], w[20], w[21]};
+  d.workspace = a->workspace; d.out = a->out; d.out_kind = a->out_kind; d.style_stride = (long)a->style_stride; d.plane_stride = (long)a->plane_stride;
+  return launch_crossray_decode_multi(d, (hipStream_t)stream);
 }
 
 

@@ -38,6 +38,20 @@ int launch_crossray_fold(const float* sM, const float* cM, const float* c_mean, 
 int launch_crossray_apply(const float* x, long HW, const float* affine, float* rgb, long plane_stride, hipStream_t stream);
 int launch_crossray_decode(const DecodeArgs& d, hipStream_t stream);
 int launch_crossray_decode_sharded(const DecodeArgs& d, int phase, float* xchg, double count_global, hipStream_t stream);
+// appearance sweep (include/crnerf_sweep.h): S styles' statistics once, then one content grid decoded under all of them
+constexpr int SWEEP_MAX_STYLES = 16;       // CRNERF_SWEEP_MAX_STYLES: the folded maps of a call stay in LDS
+constexpr int SWEEP_STATS_FLOATS = 1088;   // CRNERF_SWEEP_STATS_FLOATS: mean[64] | matrix[1024]
+struct SweepArgs {
+  const float* content; long HW;
+  const float* stats; long style_HW; int S;
+  CnnTensors cnet; const float* cnet_fc_w; const float* cnet_fc_b;
+  FoldTensors lin;
+  void* workspace;
+  void* out; int out_kind; long style_stride; long plane_stride;
+};
+int launch_crossray_style_stats(const float* styles, int S, long HWs, long content_HW, const CnnTensors& snet, const float* fc_w, const float* fc_b,
+                                void* workspace, float* stats, hipStream_t stream);
+int launch_crossray_decode_multi(const SweepArgs& d, hipStream_t stream);
 size_t crossray_backward_workspace_floats(long HW, long HWs);
 int launch_crossray_decode_backward(const DecodeArgs& d, const float* d_rgb, long d_plane_stride, float* workspace, float* d_content,
                                     float* d_style, float* const* grads, hipStream_t stream);

@@ -764,6 +764,155 @@ int launch_crossray_decode_sharded(const DecodeArgs& d, int phase, float* xchg, 
   return launch_crossray_apply(d.content, d.HW, st + ST_AFFINE, d.rgb, d.plane_stride, stream);
 }
 
+// ---------------------------------------------------------------- appearance sweep: one content grid under S styles (include/crnerf_sweep.h)
+// The single decode's two halves, taken apart.  Style half, once per sweep: mean and matrix of every style grid -> stats[S][1088], through the
+// SAME kernels, block plan and reduction path the single decode runs for that style -- two styles per launch through the existing job pairs (the
+// kernels take their jobs by value; an array of 16 GramJobs would be 1.4 KiB of kernel arguments, and the stats are made once per sweep, not per
+// frame).  Content half, once per frame: the content job alone through the same kernels (they accept an empty second job), then S folds in one
+// launch (fold_compute, unchanged) and one apply pass that loads a pixel's row once and runs apply_pixels' arithmetic once per style.
+constexpr size_t WS_SWEEP_AFFINE = WS_STATS + ST_END;                  // [SWEEP_MAX_STYLES][196]
+static_assert((WS_SWEEP_AFFINE + (size_t)SWEEP_MAX_STYLES * 196) * 4 <= CROSSRAY_WORKSPACE_BYTES, "workspace too small for the sweep's affine maps");
+
+// the single decode takes the one-launch Gram reduction + fc only when BOTH grids are small (launch_crossray_decode: g0.coop && g1.coop)
+static bool sweep_small_path(long HW, long HWs) { return HW <= GRAM_COOP_MAX_PIXELS && HWs <= GRAM_COOP_MAX_PIXELS; }
+
+int launch_crossray_style_stats(const float* styles, int S, long HWs, long content_HW, const CnnTensors& snet, const float* fc_w, const float* fc_b,
+                                void* workspace, float* stats, hipStream_t stream) {
+  float* ws = (float*)workspace;
+  float* st = ws + WS_STATS;
+  const bool small = sweep_small_path(content_HW, HWs);
+  const float inv = (float)(1.0 / (double)HWs);
+  for (int s = 0; s < S; s += 2) {
+    const bool two = s + 1 < S;
+    const float* x0 = styles + (size_t)s * (size_t)HWs * 64;
+    const float* x1 = x0 + (size_t)HWs * 64;
+    float* o0 = stats + (size_t)s * SWEEP_STATS_FLOATS;
+    float* o1 = o0 + SWEEP_STATS_FLOATS;
+    SumJob s0{x0, HWs, ws + WS_SUMP0, chansum_blocks(HWs)}, s1{nullptr, 0, nullptr, 0};
+    if (two) s1 = SumJob{x1, HWs, ws + WS_SUMP1, s0.nblk};
+    hipLaunchKernelGGL(chansum_partial_kernel, dim3(s0.nblk + s1.nblk), dim3(SUM_THREADS), 0, stream, s0, s1);
+    GramJob g0{x0, HWs, nullptr, ws + WS_SUMP0, s0.nblk, inv, snet, ws + WS_GRAMP0, o0, gram_blocks(HWs)};
+    gram_plan(g0);
+    GramJob g1{};
+    g1.nblk = 0;
+    if (two) { g1 = g0; g1.x = x1; g1.chan_partial = ws + WS_SUMP1; g1.gram_partial = ws + WS_GRAMP1; g1.mean_out = o1; }
+    if (int rc = launch_gram(g0, g1, stream)) return rc;
+    const unsigned jobs = two ? 2 : 1;
+    if (small) {
+      FcSmallJob f0{ws + WS_GRAMP0, g0.nblk, st + ST_CGRAM, inv, fc_w, fc_b, o0 + 64};
+      FcSmallJob f1{ws + WS_GRAMP1, g0.nblk, st + ST_SGRAM, inv, fc_w, fc_b, o1 + 64};
+      hipLaunchKernelGGL(gram_fc_small_kernel, dim3(32, jobs), dim3(256), 0, stream, f0, two ? f1 : f0);
+    } else {
+      RedJob r0{ws + WS_GRAMP0, g0.nblk, st + ST_CGRAM}, r1{ws + WS_GRAMP1, g0.nblk, st + ST_SGRAM};
+      hipLaunchKernelGGL(reduce_rows_kernel, dim3(16, jobs), dim3(RED_THREADS), 0, stream, r0, two ? r1 : r0, 1024);
+      FcJob f0{st + ST_CGRAM, inv, fc_w, fc_b, o0 + 64}, f1{st + ST_SGRAM, inv, fc_w, fc_b, o1 + 64};
+      hipLaunchKernelGGL(gram_fc_kernel, dim3(256, jobs), dim3(256), 0, stream, f0, two ? f1 : f0);
+    }
+  }
+  return check_launch("crossray_style_stats");
+}
+
+// one workgroup per style: affine[s] = fold(stats[s], the content's matrix and mean)
+__global__ __launch_bounds__(256) void fold_multi_kernel(const float* __restrict__ stats, const float* __restrict__ cM, const float* __restrict__ c_mean,
+                                                         FoldTensors w, float* __restrict__ affine) {
+  __shared__ FoldLds L;
+  const int t = threadIdx.x;
+  const float* s = stats + (size_t)blockIdx.x * SWEEP_STATS_FLOATS;
+  float* aff = affine + (size_t)blockIdx.x * 196;
+  fold_load_weights(L, w, t);
+  fold_compute(L, s + 64, cM, c_mean, s, w, aff, t);
+  if (t == 0) aff[195] = 0.0f;
+}
+
+// CRNERF_SWEEP_OUT_U8: eval.py:296-297 -- (unsigned char)(clamp(v, 0, 1) * 255), a float32 multiply, truncated.  The NaN test is on the bits:
+// the unit is built with -fno-honor-nans, under which a floating-point self-comparison may be folded away.
+__device__ __forceinline__ unsigned char sweep_u8(float v) {
+  if ((__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u) return 0;
+  return (unsigned char)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);
+}
+
+// apply_pixels for S maps at once: 4 lanes per pixel, 16 channels each; the row is loaded ONCE and every style accumulates r, g, b over it in
+// apply_pixels' order (same fmaf chain, same two shuffles, same bias add and sigmoid), so image s carries the single decode's bits.
+// Per pixel: 256 B in, 12 S (float) or 3 S (uint8) bytes out, against S x 268 for S single applies.
+template <int KIND>
+__global__ __launch_bounds__(256) void apply_multi_kernel(const float* __restrict__ x, long HW, const float* __restrict__ affine, int S,
+                                                          void* __restrict__ out, long style_stride, long plane_stride) {
+  __shared__ __attribute__((aligned(16))) float A[SWEEP_MAX_STYLES * 196];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < S * 196; i += 256) A[i] = affine[i];
+  __syncthreads();
+  const int q = tid & 3;
+  for (long px = ((long)blockIdx.x * 256 + tid) >> 2;; px += ((long)gridDim.x * 256) >> 2) {
+    const bool valid = px < HW;
+    if (__all(!valid)) break;
+    f32x4 v[4];
+    if (valid) {
+      const float* row = x + px * 64;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = *(const f32x4*)(row + 4 * q + 16 * k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    for (int s = 0; s < S; ++s) {
+      const float* As = A + s * 196;
+      float r = 0.0f, g = 0.0f, b = 0.0f;
+      if (valid) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int c = 4 * q + 16 * k;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            r = fmaf(As[c + e], v[k][e], r);
+            g = fmaf(As[64 + c + e], v[k][e], g);
+            b = fmaf(As[128 + c + e], v[k][e], b);
+          }
+        }
+      }
+      r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+      r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+      if (valid && q < 3) {
+        const float pre = (q == 0 ? r : (q == 1 ? g : b)) + As[192 + q];
+        const float val = 1.0f / (1.0f + expf(-pre));
+        if (KIND == 0) ((float*)out)[s * style_stride + q * plane_stride + px] = val;
+        else ((unsigned char*)out)[s * style_stride + px * 3 + q] = sweep_u8(val);
+      }
+    }
+  }
+}
+
+int launch_crossray_decode_multi(const SweepArgs& d, hipStream_t stream) {
+  if (d.HW <= 0 || d.S <= 0) return 0;
+  float* ws = (float*)d.workspace;
+  float* st = ws + WS_STATS;
+  float* aff = ws + WS_SWEEP_AFFINE;
+  const float inv = (float)(1.0 / (double)d.HW);
+  SumJob s0{d.content, d.HW, ws + WS_SUMP0, chansum_blocks(d.HW)}, sn{nullptr, 0, nullptr, 0};
+  hipLaunchKernelGGL(chansum_partial_kernel, dim3(s0.nblk), dim3(SUM_THREADS), 0, stream, s0, sn);
+  GramJob g0{d.content, d.HW, nullptr, ws + WS_SUMP0, s0.nblk, inv, d.cnet, ws + WS_GRAMP0, st + ST_CMEAN, gram_blocks(d.HW)};
+  gram_plan(g0);
+  GramJob gn{};
+  gn.nblk = 0;
+  if (int rc = launch_gram(g0, gn, stream)) return rc;
+  if (sweep_small_path(d.HW, d.style_HW)) {
+    FcSmallJob f0{ws + WS_GRAMP0, g0.nblk, st + ST_CGRAM, inv, d.cnet_fc_w, d.cnet_fc_b, st + ST_CMAT};
+    hipLaunchKernelGGL(gram_fc_small_kernel, dim3(32, 1), dim3(256), 0, stream, f0, f0);
+  } else {
+    RedJob r0{ws + WS_GRAMP0, g0.nblk, st + ST_CGRAM}, rn{nullptr, 0, nullptr};
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(16, 1), dim3(RED_THREADS), 0, stream, r0, rn, 1024);
+    FcJob f0{st + ST_CGRAM, inv, d.cnet_fc_w, d.cnet_fc_b, st + ST_CMAT};
+    hipLaunchKernelGGL(gram_fc_kernel, dim3(256, 1), dim3(256), 0, stream, f0, f0);
+  }
+  hipLaunchKernelGGL(fold_multi_kernel, dim3(d.S), dim3(256), 0, stream, d.stats, st + ST_CMAT, st + ST_CMEAN, d.lin, aff);
+  const long blocks = (d.HW * 4 + 255) / 256;
+  const int grid = (int)(blocks < 2048 ? blocks : 2048);
+  if (d.out_kind == 0)
+    hipLaunchKernelGGL(apply_multi_kernel<0>, dim3(grid), dim3(256), 0, stream, d.content, d.HW, aff, d.S, d.out, d.style_stride, d.plane_stride);
+  else
+    hipLaunchKernelGGL(apply_multi_kernel<1>, dim3(grid), dim3(256), 0, stream, d.content, d.HW, aff, d.S, d.out, d.style_stride, d.plane_stride);
+  return check_launch("crossray_decode_multi");
+}
+
 }  // namespace crnerf
 
 // ================================================================= backward of the decode (training)

@@ -145,6 +145,20 @@ class style_net(nn.Module):
             return DecoderFn.apply(xp, sp, *self.decoder_tensors()).view(1, 3, H, W)
         return ops.crossray_decode(xp, sp, self.decoder_tensors()).view(1, 3, H, W)
 
+    def style_stats(self, style_features, content_hw):
+        """The style half of forward for S appearance grids [1,64,h,w] of one size, once per sweep (ops.crossray_style_stats).  content_hw: the
+        content grids' pixel count, or their (H, W).  Inference only."""
+        if not isinstance(content_hw, int):
+            content_hw = int(content_hw[0]) * int(content_hw[1])
+        return ops.crossray_style_stats([_pixel_major(s)[0] for s in style_features], self.decoder_tensors(), content_hw)
+
+    def decode_styles(self, content_feature, stats, u8=False):
+        """forward(content_feature, style_s) for every style of `stats` from one pass over the grid: [S,3,H,W] float32, image s bit-identical to
+        forward's, or with u8=True the frames [S,H,W,3] uint8 = (rgb.clamp(0, 1) * 255) truncated.  Inference only."""
+        xp, (H, W) = _pixel_major(content_feature)
+        out = ops.crossray_decode_multi(xp, stats, self.decoder_tensors(), u8=u8)
+        return out.view(stats.S, H, W, 3) if u8 else out.view(stats.S, 3, H, W)
+
     def decoder_tensors(self):
         """The 22 parameter tensors in state_dict order (crnerf_crossray_decode_f32's `weights`): the 1 x 1 convolutions' [cout, cin, 1, 1] weights as
         [cout, cin] views.  The Parameter objects are looked up once per module (ops.cached_list: a step asks four times, through ~140 attribute

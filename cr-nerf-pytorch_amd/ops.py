@@ -762,6 +762,132 @@ def crossray_decode(content_pm, style_pm, weights, out=None):
     return out
 
 
+# ---- appearance sweep (include/crnerf_sweep.h): the styles' statistics once, then one content grid decoded under all of them
+_COOP_MAX_PIXELS = 4096      # GRAM_COOP_MAX_PIXELS (csrc/crossray.hip): where the single decode switches its Gram reduction
+
+
+def _sweep_small_path(content_hw, style_hw):
+    """The single decode sums its partial Grams in one launch only when BOTH grids have <= 4096 pixels; the order of the sum follows."""
+    return content_hw <= _COOP_MAX_PIXELS and style_hw <= _COOP_MAX_PIXELS
+
+
+class StyleStats:
+    """What a style contributes to a decode, for S styles: `stats` [S,1088] float32 on the device (channel mean, then the 32 x 32 style matrix),
+    `S`, `style_hw` (pixels of each style grid) and `small_path` -- the side of the single decode's reduction switch the stats were made for."""
+    __slots__ = ("stats", "S", "style_hw", "small_path")
+
+    def __init__(self, stats, style_hw, small_path):
+        self.stats, self.S, self.style_hw, self.small_path = stats, int(stats.shape[0]), int(style_hw), bool(small_path)
+
+
+def _sweep_inference_only(weights, what):
+    if torch.is_grad_enabled() and any(getattr(t, "requires_grad", False) for t in weights):
+        raise ValueError("crnerf_amd: %s is an inference call (no backward): run it under torch.no_grad() or with frozen weights" % what)
+
+
+def _sweep_grid(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 64:
+        raise ValueError("crnerf_amd: %s must be a pixel-major [HW,64] grid, got %s" % (name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t
+
+
+def _sweep_on_gpu(tensors, name):
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError("crnerf_amd: %s must be a GPU tensor (the HIP path has no CPU fallback), got one on %s" % (name, t.device))
+
+
+def crossray_style_stats(style_pms, weights, content_hw):
+    """The style half of crossray_decode for S style grids, once per sweep.  style_pms: S tensors [HWs,64] of one size (or one [S,HWs,64]);
+    weights: the 22 decoder tensors; content_hw: the pixel count of the content grids the stats will be used with (it decides the summation
+    order, as in the single decode).  Returns a StyleStats."""
+    grids = list(style_pms.unbind(0)) if isinstance(style_pms, torch.Tensor) and style_pms.dim() == 3 else list(style_pms)
+    if not grids:
+        raise ValueError("crnerf_amd: crossray_style_stats needs at least one style grid")
+    for g in grids:
+        _sweep_grid(g, "style grid")
+    hws = int(grids[0].shape[0])
+    if hws < 1 or any(int(g.shape[0]) != hws for g in grids):
+        raise ValueError("crnerf_amd: the style grids of a sweep must share one size >= 1, got %s" % ([int(g.shape[0]) for g in grids],))
+    content_hw = int(content_hw)
+    if content_hw < 1:
+        raise ValueError("crnerf_amd: content_hw must be the pixel count of the content grids (>= 1), got %d" % content_hw)
+    weights = list(weights)
+    if len(weights) != 22:
+        raise ValueError("crnerf_amd: expected the 22 decoder tensors, got %d" % len(weights))
+    _sweep_inference_only(weights, "crossray_style_stats")
+    _sweep_on_gpu(grids, "a style grid")
+    lib = _lib.load()
+    styles = _f32c(torch.stack([g.detach() for g in grids], 0), "style grids")
+    S = styles.shape[0]
+    stats = torch.empty(S, _lib.SWEEP_STATS_FLOATS, dtype=torch.float32, device=styles.device)
+    ws = crossray_workspace(styles.device)
+    arr = _lib.ptr_array(_wlist(weights, "decoder weight"), "decoder weight")
+    for s0 in range(0, S, _lib.SWEEP_MAX_STYLES):
+        n = min(_lib.SWEEP_MAX_STYLES, S - s0)
+        _lib.check(lib.crnerf_crossray_style_stats_f32(ctypes.c_void_p(styles[s0].data_ptr()), n, hws, content_hw, arr, ctypes.c_void_p(ws.data_ptr()),
+                                                       ctypes.c_void_p(stats[s0].data_ptr()), _lib.stream_ptr()), "crnerf_crossray_style_stats_f32")
+    return StyleStats(stats, hws, _sweep_small_path(content_hw, hws))
+
+
+def _sweep_out(out, S, HW, u8, like):
+    """The destination of a multi decode: [S,3,HW] float32 planes or [S,HW,3] uint8 frames, fresh or the caller's -- which may be a view whose
+    images (and, for float, planes) are padded.  Returns (tensor, style_stride, plane_stride) in elements."""
+    shape, dtype = ((S, HW, 3), torch.uint8) if u8 else ((S, 3, HW), torch.float32)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=like.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != like.device:
+        raise ValueError("crnerf_amd: out must be a %s %s tensor on %s" % (dtype, shape, like.device))
+    if u8:
+        image, plane = 3 * HW, 0
+        dense = out.stride(2) == 1 and (HW <= 1 or out.stride(1) == 3)
+    else:
+        plane = out.stride(1)
+        image = 2 * plane + HW
+        dense = (HW <= 1 or out.stride(2) == 1) and plane >= HW
+    if not dense or (S > 1 and out.stride(0) < image):
+        raise ValueError("crnerf_amd: out %s with strides %s: every image must be dense (padding only between images%s)"
+                         % (shape, out.stride(), "" if u8 else " and planes"))
+    return out, (out.stride(0) if S > 1 else image), plane
+
+
+def crossray_decode_multi(content_pm, stats, weights, out=None, u8=False):
+    """One content grid [HW,64] decoded under the S styles of `stats` (crossray_style_stats): the content's sums and Gram once, S folds, one apply
+    pass over the grid.  Returns [S,3,HW] float32 -- image s bit-identical to crossray_decode(content_pm, style_s, weights) -- or, u8=True,
+    [S,HW,3] uint8 frames (clamp(v, 0, 1) * 255, truncated; NaN -> 0).  More than 16 styles are split into several calls."""
+    _sweep_grid(content_pm, "content")
+    if not isinstance(stats, StyleStats):
+        raise ValueError("crnerf_amd: stats must come from crossray_style_stats, got %s" % type(stats).__name__)
+    HW = int(content_pm.shape[0])
+    if HW > 0 and stats.small_path != _sweep_small_path(HW, stats.style_hw):
+        raise ValueError("crnerf_amd: these stats were made for content grids %s %d pixels and cannot be used with one of %d: the decode sums in "
+                         "another order there; rebuild them with crossray_style_stats(..., content_hw=%d)"
+                         % ("of at most" if stats.small_path else "beyond", _COOP_MAX_PIXELS, HW, HW))
+    weights = list(weights)
+    if len(weights) != 22:
+        raise ValueError("crnerf_amd: expected the 22 decoder tensors, got %d" % len(weights))
+    _sweep_inference_only(weights, "crossray_decode_multi")
+    _sweep_on_gpu([content_pm, stats.stats], "content / stats")
+    if stats.stats.device != content_pm.device:
+        raise ValueError("crnerf_amd: content is on %s, the stats on %s" % (content_pm.device, stats.stats.device))
+    S = stats.S
+    out, style_stride, plane_stride = _sweep_out(out, S, HW, u8, content_pm)
+    lib = _lib.load()
+    x = _f32c(content_pm.detach(), "content")
+    ws = crossray_workspace(x.device)
+    arr = _lib.ptr_array(_wlist(weights, "decoder weight"), "decoder weight")
+    a = _lib.SweepDecodeArgs()
+    a.content, a.HW, a.style_HW = x.data_ptr(), HW, stats.style_hw
+    a.out_kind = _lib.SWEEP_OUT_U8 if u8 else _lib.SWEEP_OUT_F32
+    a.weights, a.workspace = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)), ws.data_ptr()
+    a.style_stride, a.plane_stride = style_stride, plane_stride
+    for s0 in range(0, S, _lib.SWEEP_MAX_STYLES):
+        a.S = min(_lib.SWEEP_MAX_STYLES, S - s0)
+        a.stats, a.out = stats.stats[s0].data_ptr(), out[s0].data_ptr()
+        _lib.check(lib.crnerf_crossray_decode_multi_f32(ctypes.byref(a), _lib.stream_ptr()), "crnerf_crossray_decode_multi_f32")
+    return out
+
+
 def encoder_forward(image, weights):
     """encoder_sameoutputsize.forward: image [1,3,H,W] or [3,H,W] -> pixel-major style grid [1024,64]."""
     lib = _lib.load()

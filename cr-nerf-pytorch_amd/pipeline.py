@@ -6,6 +6,8 @@ reference's drivers can be re-created without Lightning / imageio / torchvision:
     batched_inference(...)        eval.py:29-59 / appearance_modification_video.py:71-102 (ray-chunk loop, dict concat)
     decode_image(...)             eval.py:288-295 (feature -> [1,64,H,W] view -> decoder -> [H*W,3])
     render_frame(...)             one video frame: rays generated on the device, style from the appearance encoder
+    render_frame_styles(...)      one video frame under S style images: ONE render, one multi-style decode (include/crnerf_sweep.h)
+    decode_frame_styles(...)      a kept feature grid under S style images, no render
     evaluate_image(...)           eval.py:271-299 + eval_metric.py:87-93 for one test sample: render, decode, PSNR / SSIM (no PNG, no host copy)
     evaluate_lpips(...)           eval_metric.py:92 on evaluate_image's output: the LPIPS column, given the network's weights
     TrainingSystem                NeRFSystem.decode / forward / training_step, train_mask_grid_sample.py:127-226, :268-290
@@ -118,6 +120,29 @@ def render_frame(models, embeddings, enc_a, style_img, H, W, K, c2w, hparams_, n
     res = batched_inference(models, embeddings, rays, None, hparams_.N_samples, hparams_.N_importance, hparams_.use_disp,
                             chunk, False, args=hparams_, a_embedded_from_img=a_emb, precision=precision, lean=lean)
     return decode_image(models, res, H, W, a_emb).reshape(int(H), int(W), 3).clamp(0, 1)
+
+
+@torch.no_grad()
+def decode_frame_styles(models, feature, H, W, stats, u8=True):
+    """A rendered frame's feature grid [H*W,64] (results['feature_fine'], kept or fresh) under every style of `stats`
+    (models['decoder'].style_stats): [S,H,W,3] uint8 frames on the device -- frame s is (render_frame's image * 255) truncated, byte for byte --
+    or with u8=False [S,3,H,W] float32.  No render: a style that arrives later costs one decode."""
+    grid = feature.t().reshape(1, feature.shape[1], int(H), int(W))  # decode_image's view
+    return models["decoder"].decode_styles(grid, stats, u8=u8)
+
+
+@torch.no_grad()
+def render_frame_styles(models, embeddings, stats, H, W, K, c2w, hparams_, near=0.0, far=5.0, chunk=32768, precision=None, lean=False,
+                        return_features=False):
+    """render_frame for S styles at the cost of one render: the render never reads the appearance embedding (models/rendering.py), so one
+    generate_rays + batched_inference serves every style and only the decode runs per style -- in one pass (decode_frame_styles).
+    Returns [S,H,W,3] uint8 on the device; return_features=True: (frames, feature [H*W,64])."""
+    rays = generate_rays(H, W, K, c2w, near, far, device=stats.stats.device)
+    res = batched_inference(models, embeddings, rays, None, hparams_.N_samples, hparams_.N_importance, hparams_.use_disp,
+                            chunk, False, args=hparams_, precision=precision, lean=lean)
+    feature = res["feature_fine" if "feature_fine" in res else "feature_coarse"]
+    frames = decode_frame_styles(models, feature, H, W, stats, u8=True)
+    return (frames, feature) if return_features else frames
 
 
 @torch.no_grad()

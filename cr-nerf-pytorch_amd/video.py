@@ -88,3 +88,28 @@ def render_video(models, embeddings, enc_a, style_img, hparams_, scene="brandenb
                                     chunk=chunk, precision=precision, a_emb=a_emb, lean=lean)
         frames[i] = (img.clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
     return frames
+
+
+@torch.no_grad()
+def render_appearance_sweep(models, embeddings, enc_a, style_imgs, hparams_, scene="brandenburg_gate", n_frames=N_FRAMES, rank=0, world_size=1,
+                            chunk=32768, precision=None, near=0.0, far=5.0, lean=False, keep_features=False):
+    """render_video for S style images at the cost of ONE video plus S decodes per frame (the outer loop over example images of
+    appearance_modification_video.py:224-263): the render does not depend on the style image, so every frame of this rank is rendered once and
+    decoded under all S styles in one pass (pipeline.render_frame_styles).  style_imgs: S tensors [1,3,h,w] in [0,1] whose encodings share one
+    size.  Returns {style_index: {frame_index: uint8 [H,W,3] ndarray}}, frame for frame the bytes of render_video(..., style_img=style_imgs[s]);
+    keep_features=True: (frames, {frame_index: feature_fine [H*W,64] on the device}) -- pipeline.decode_frame_styles turns a kept feature grid
+    into the frames of a style that arrives later without a render."""
+    w, h = hparams_.img_wh
+    K, poses = define_camera(hparams_.img_wh), define_poses(scene, n_frames)
+    stats = models["decoder"].style_stats([enc_a(img) for img in style_imgs], (h, w))   # once per style image, once per sweep
+    frames = {s: {} for s in range(stats.S)}
+    features = {}
+    for i in range(rank, n_frames, world_size):
+        out = pipeline.render_frame_styles(models, embeddings, stats, h, w, K, poses[i].astype(np.float32), hparams_, near=near, far=far,
+                                           chunk=chunk, precision=precision, lean=lean, return_features=keep_features)
+        if keep_features:
+            out, features[i] = out
+        host = out.cpu().numpy()            # one device-to-host copy per frame for all S images
+        for s in range(stats.S):
+            frames[s][i] = host[s]
+    return (frames, features) if keep_features else frames
