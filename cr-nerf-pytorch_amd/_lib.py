@@ -267,6 +267,15 @@ LEAN_SIGNATURES = {
     "crnerf_render_rays_lean_bf16": (i32, [ra, vp]),
     "crnerf_render_rays_lean_f16": (i32, [ra, vp]),
 }
+# One row per symbol of include/crnerf_lean_composite.h (the coarse-weights renders and the lean fine launch of the composite precisions; the header
+# crnerf_lean.h includes), bound by the same loader; tests/test_lean_composite_host.py holds it to that header's prototypes.
+LEAN_COMPOSITE_SIGNATURES = {
+    "crnerf_render_coarse_weights_f32h2": (i32, [ra, vp]),
+    "crnerf_render_coarse_weights_f32x3": (i32, [ra, vp]),
+    "crnerf_render_coarse_weights_f32x3_repair": (i32, [ra, vp]),
+    "crnerf_render_coarse_weights_f16": (i32, [ra, vp]),
+    "crnerf_render_rays_lean_bf16_fine": (i32, [ra, vp]),
+}
 
 
 class SweepDecodeArgs(ctypes.Structure):
@@ -306,8 +315,8 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h / crnerf_sweep.h
+        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()) + list(LEAN_COMPOSITE_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_sweep.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

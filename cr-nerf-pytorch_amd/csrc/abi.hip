@@ -404,6 +404,51 @@ static int render_rays_lean_pair(const crnerf_render_args* a, void* stream, Core
 int crnerf_render_rays_lean_bf16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::BF16_PAIR); }
 int crnerf_render_rays_lean_f16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::F16_PAIR); }
 
+// include/crnerf_lean.h: the coarse pass for its compositing weights alone (what the lean composite modes put in front of the lean fine launch)
+static int render_coarse_weights(const crnerf_render_args* a, void* stream, Core core) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: negative n_rays");
+  if (a->n_importance != 0) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: n_importance must be 0 (the fine pass is crnerf_render_rays_lean_bf16_fine)");
+  if (a->n_samples < 2 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: n_samples must be in [2, 256]");
+  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->rays, "rays"); REQUIRE(a->weights_coarse, "weights_coarse");
+  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
+    return set_error(CRNERF_ERR_CONFIG, "render_coarse_weights: no in-kernel random draws (hand them over as z_coarse / noise_coarse)");
+  auto r = to_render_args(a);
+  r.packed_fine = nullptr; r.u = nullptr; r.noise_fine = nullptr;                     // ignored, whatever the caller passed
+  r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr; r.feature_fine = nullptr; r.depth_fine = nullptr; r.z_fine = nullptr;
+  r.coarse_weights = 1;
+  switch (core) {
+    case Core::H2: return launch_render_rays_h2(r, (hipStream_t)stream);
+    case Core::X3_REPAIR: r.repair = 1; return launch_render_rays_x3(r, (hipStream_t)stream);
+    case Core::X3: return launch_render_rays_x3(r, (hipStream_t)stream);
+    default: return launch_render_rays_f16p(r, (hipStream_t)stream);
+  }
+}
+int crnerf_render_coarse_weights_f32h2(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::H2); }
+int crnerf_render_coarse_weights_f32x3(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::X3); }
+int crnerf_render_coarse_weights_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::X3_REPAIR); }
+int crnerf_render_coarse_weights_f16(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::F16_PAIR); }
+
+int crnerf_render_rays_lean_bf16_fine(const crnerf_render_args* a, void* stream) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: negative n_rays");
+  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: n_importance must be in [1, 256]");
+  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: n_samples must be in [3, 256]");
+  REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays"); REQUIRE(a->weights_coarse, "weights_coarse (input)");
+  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
+  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
+    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean_bf16_fine: no in-kernel random draws in the bf16 kernels");
+  auto r = to_render_args(a);
+  r.packed_coarse = a->packed_fine;                                                   // one pack: the fine model's
+  r.noise_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr;     // no coarse pass; weights_coarse is the INPUT
+  r.weights_fine = nullptr;                                                           // ignored, whatever the caller passed
+  r.fine_only = 1;
+  r.lean = 1;
+  return launch_render_rays_bf16p(r, (hipStream_t)stream);
+}
+
 size_t crnerf_packed_mlp_mixed_bytes(void) { return gemm_packed_bytes(); }
 size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_acts_bytes((long)n); }
 size_t crnerf_mlp_train_mixed_scratch_bytes(int64_t n) { return mlp_train_mixed_scratch_bytes((long)n); }

@@ -126,6 +126,10 @@ struct RenderArgs {
   // crnerf_render_rays_lean_f32 (render_fused16.hip), crnerf_render_rays_lean_bf16 / _f16 (render_fused_bf16p.hip; include/crnerf_lean.h): trunk-only
   // coarse pass; writes feature_fine, depth_fine and (optional) z_fine only.  The other launchers do not look at it.
   int lean = 0;
+  // crnerf_render_coarse_weights_* (include/crnerf_lean.h; render_fused_x3.hip both builds, the fp16 pair core): Ni == 0, every tile walks the trunk,
+  // weights_coarse is the only output and carries the range mark (0x7fc00000 in [r][0]); with `repair` the x3 launcher looks for that mark.
+  // lean + fine_only (crnerf_render_rays_lean_bf16_fine): the fine-only kernel without weights_fine.
+  int coarse_weights = 0;
   // training twin (crnerf_render_rays_train_f32; all null for inference): saved activations + raw MLP outputs per pass
   void* train_acts_coarse = nullptr;   // crnerf_mlp_train_acts_bytes(R*Nc)
   void* train_acts_fine = nullptr;     // crnerf_mlp_train_acts_bytes(R*(Nc+Ni))

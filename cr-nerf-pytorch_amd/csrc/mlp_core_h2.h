@@ -229,6 +229,12 @@ __device__ __forceinline__ void mma_layer_h2(WeightPipeX& p, xu32x4 (&q)[X_AHEAD
 // Range guard: an activation beyond fp16's range would split into (inf, -inf) pieces, turn into NaN in the next layer and be clamped to 0 by its
 // relu -- a finite, wrong result -- so the tile tracks max |operand| and POISONS the 65 outputs of such a point with NaN.
 // (The kernels call mlp_tile_x3 -- mlp_core_h2t.h -- which is this function for inference and the training form mlp_tile_h2t when rows are saved.)
+// TRUNK (the coarse-weights render, render_fused_x3.hip): layers 1..8 and static_sigma only -- OFFH_FIN fragments of the stream, the pipe running the
+// shorter pass (WeightPipeX::set_stream_frags).  The full tile finishes h8 and feeds static_sigma while xyz_encoding_final walks it; here layer 8
+// hands nothing on (NEXT_FIN = -1, no next bias) and the 128 raw values are finished in one VALU run behind it: relu, then the fma chain in the full
+// tile's order (group 0..15, value 0..7), so sigma is bit-identical.  feat and dv are not touched.  Range guard: the xyz embedding and the operands
+// of layers 1..8 (h8 is multiplied on the VALU in fp32 only); a point that trips it returns sigma = 0x7fc00000.
+template <bool TRUNK = false>
 __device__ __forceinline__ void mlp_tile_h2i(WeightPipeX& p, int model, const f32x16 (&pe)[3], const f32x16 (&dv)[1], f32x16 (&feat)[2], float& sigma,
                                              int h, xu32x4 (&q)[X_AHEAD], PhaseTimer& tm) {
   const lds_float* C = (const lds_float*)(p.lds + (model ? LDS_CONST1 : LDS_CONST0));
@@ -250,19 +256,23 @@ __device__ __forceinline__ void mlp_tile_h2i(WeightPipeX& p, int model, const f3
       c.emax = fmaxf(c.emax, fabsf(v));
       h2_split_into(pep[s][0], pep[s][1], e, v, 1.0f);
     }
+  if constexpr (!TRUNK) {
 #pragma unroll
-  for (int s = 0; s < KS_DIR; ++s)
+    for (int s = 0; s < KS_DIR; ++s)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = dv[0][8 * s + e];
-      c.emax = fmaxf(c.emax, fabsf(v));
-      h2_split_into(dvp[s][0], dvp[s][1], e, v, 1.0f);
-    }
+      for (int e = 0; e < 8; ++e) {
+        const float v = dv[0][8 * s + e];
+        c.emax = fmaxf(c.emax, fabsf(v));
+        h2_split_into(dvp[s][0], dvp[s][1], e, v, 1.0f);
+      }
+  }
   // the embedding operands are read by MFMAs only: they live in the AGPR half, next to the accumulators, and leave the VGPRs to the raw set
 #pragma unroll
   for (int s = 0; s < KS_XYZ; ++s) asm volatile("" : "+a"(pep[s][0]), "+a"(pep[s][1]));
+  if constexpr (!TRUNK) {
 #pragma unroll
-  for (int s = 0; s < KS_DIR; ++s) asm volatile("" : "+a"(dvp[s][0]), "+a"(dvp[s][1]));
+    for (int s = 0; s < KS_DIR; ++s) asm volatile("" : "+a"(dvp[s][0]), "+a"(dvp[s][1]));
+  }
   init_acc<8>(X, B1, h);                                   // xyz_encoding_1's bias (the pack's consts carry the 2^8)
   BOpH b{pep[0][0], pep[0][1]};
   tm.tick(T_PROLOGUE);
@@ -278,6 +288,26 @@ __device__ __forceinline__ void mlp_tile_h2i(WeightPipeX& p, int model, const f3
   tm.tick(T_X2);
   mma_layer_h2<8, true, 0, KS_HID, 1, 8, 1, false, false>(p, q, b, pep, R, X, B1 + 6 * W_HIDDEN, pep[0], WS, c, h);          // 6
   mma_layer_h2<8, true, 0, KS_HID, 1, 8, 1, false, false>(p, q, b, pep, R, X, B1 + 7 * W_HIDDEN, pep[0], WS, c, h);          // 7
+  if constexpr (TRUNK) {
+    static_assert(OFFH_FIN % X_STAGE_FRAGS == 0 && OFFH_FIN % X_AHEAD == 0, "the trunk walk ends on a stage boundary and a whole queue turn");
+    mma_layer_h2<8, true, 0, KS_HID, 1, 0, -1, false, false>(p, q, b, pep, R, X, C + C_BFIN, pep[0], WS, c, h);              // 8 (the walk ends here)
+    tm.tick(T_X3);
+    float sg = 0.0f;                                        // static_sigma on relu(h8), scaled by 2^8 like the raw set
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const f32x4 w0 = *(const __attribute__((address_space(3))) f32x4*)(WS + 32 * (g >> 1) + 16 * (g & 1) + 4 * h);
+      const f32x4 w1 = *(const __attribute__((address_space(3))) f32x4*)(WS + 32 * (g >> 1) + 16 * (g & 1) + 8 + 4 * h);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sg = fmaf(e < 4 ? w0[e & 3] : w1[e & 3], fmaxf(R[g >> 1][8 * (g & 1) + e], 0.0f), sg);
+    }
+    sg += __shfl_xor(sg, 32);
+    sigma = softplus_ref(sg * H2_INV + C[C_BSIG]);
+    float am = fmaxf(c.amax, c.emax * H2_WSCALE);
+    am = fmaxf(am, __shfl_xor(am, 32));
+    if (!(am < H2_ACT_LIMIT * H2_WSCALE)) sigma = __uint_as_float(0x7fc00000u);
+    tm.tick(T_SIGMA);
+    return;
+  }
   mma_layer_h2<8, true, 0, KS_HID, 1, 8, 1, false, true>(p, q, b, pep, R, X, C + C_BFIN, pep[0], WS, c, h);                  // 8 (its tail starts static_sigma)
   tm.tick(T_X3);
   mma_layer_h2<8, true, 0, KS_HID, 1, 4, 2, true, false>(p, q, b, pep, R, X, C + C_BDIR, pep[0], WS, c, h);                  // xyz_encoding_final (+ static_sigma on h8)

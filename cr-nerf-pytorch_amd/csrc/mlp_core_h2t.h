@@ -226,11 +226,13 @@ __device__ __forceinline__ void mlp_tile_h2t(WeightPipeX& p, int model, const f3
 
 // What the kernels built on the h2 core call (the x3 core's name, so that render_fused_x3.hip / mlp_forward_x3.hip compile against either core):
 // the lazy-epilogue inference tile, or -- when the caller saves rows -- the training form.
-template <class SV = NoSaveX>
+// TRUNK: the inference tile's trunk walk (mlp_core_h2.h).
+template <class SV = NoSaveX, bool TRUNK = false>
 __device__ __forceinline__ void mlp_tile_x3(WeightPipeX& p, int model, const f32x16 (&pe)[3], const f32x16 (&dv)[1], f32x16 (&feat)[2], float& sigma,
                                             int h, xu32x4 (&q)[X_AHEAD], PhaseTimer& tm, const SV& sv = SV()) {
+  static_assert(!(TRUNK && SV::on), "the trunk walk is an inference walk");
   if constexpr (SV::on) mlp_tile_h2t(p, model, pe, dv, feat, sigma, h, q, tm, sv);
-  else mlp_tile_h2i(p, model, pe, dv, feat, sigma, h, q, tm);
+  else mlp_tile_h2i<TRUNK>(p, model, pe, dv, feat, sigma, h, q, tm);
 }
 
 }  // inline namespace xcore_h2

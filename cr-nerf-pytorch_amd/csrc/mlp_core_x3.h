@@ -123,7 +123,9 @@ __device__ __forceinline__ void mma_layer_x3(WeightPipeX& p, const f32x16 (&srcA
 
 // One 32-point tile through one model.  pe / dv: the positional embeddings in the register order of posenc_regs (posenc.h), exactly as
 // mlp_core.h's mlp_tile takes them.  Returns feat[t][4q+j] = rgb feature 32t+8q+4h+j of point p, and sigma (both lane halves).
-template <class SV = NoSaveX>
+// TRUNK (the coarse-weights render, render_fused_x3.hip): layers 1..8 and static_sigma only -- OFFX_FIN fragments of the stream, the pipe running
+// the shorter pass (WeightPipeX::set_stream_frags); sigma is the full tile's, feat and dv are not touched.
+template <class SV = NoSaveX, bool TRUNK = false>
 __device__ __forceinline__ void mlp_tile_x3(WeightPipeX& p, int model, const f32x16 (&pe)[3], const f32x16 (&dv)[1], f32x16 (&feat)[2], float& sigma,
                                             int h, xu32x4 (&q)[X_AHEAD], PhaseTimer& tm, const SV& sv = SV()) {
   const lds_float* C = (const lds_float*)(p.lds + (model ? LDS_CONST1 : LDS_CONST0));
@@ -171,6 +173,10 @@ __device__ __forceinline__ void mlp_tile_x3(WeightPipeX& p, int model, const f32
     s += __shfl_xor(s, 32);
     sigma = softplus_ref(s + C[C_BSIG]);
     tm.tick(T_SIGMA);
+  }
+  if constexpr (TRUNK) {
+    static_assert(!SAVE && OFFX_FIN % X_STAGE_FRAGS == 0 && OFFX_FIN % X_AHEAD == 0, "the trunk walk is an inference walk of whole stages and queue turns");
+    return;
   }
   init_acc<8>(acc, C + C_BFIN, h);                         // xyz_encoding_final (no activation); h8 -> slot 7
   mma_layer_x3<8, KS_HID, 0, 0, SAVE, false>(p, act, act, acc, q, sv.row(7), SaveRowX{}, vo);

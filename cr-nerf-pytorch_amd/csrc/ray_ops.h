@@ -109,6 +109,24 @@ __device__ __forceinline__ float composite_tile(CompositeState& st, const f32x16
   return w;
 }
 
+// composite_tile for a caller that reads the weights alone (the coarse-weights render): the same alpha, the same scan, the same w_n; no feature or
+// depth sum.  t_carry: the transmittance entering the tile, 1.0 at the start of a ray.
+__device__ __forceinline__ float composite_weight_tile(double& t_carry, float sigma, float noise, float zn, float znext, bool is_last, bool valid, int p) {
+  const float delta = is_last ? 1e2f : znext - zn;
+  const float alpha = valid ? 1.0f - expf(-delta * fmaxf(sigma + noise, 0.0f)) : 0.0f;
+  double incl = (double)(1.0f - alpha);
+#pragma unroll
+  for (int d = 1; d < 32; d <<= 1) {
+    const double o = shfl_up_f64(incl, d, 32);
+    if (p >= d) incl *= o;
+  }
+  double excl = shfl_up_f64(incl, 1, 32);
+  if (p == 0) excl = 1.0;
+  const float T = (float)(t_carry * excl);
+  t_carry *= shfl_f64(incl, 31, 32);
+  return alpha * T;
+}
+
 // One 64-sample tile held as two 32-point groups (lane (p, h) owns points p and 32 + p, bf16 core): ONE 64-lane scan
 // instead of two 32-lane ones.  Lane 32h + p evaluates alpha of sample 32h + p (= its group-h point), the scan runs
 // over lanes in sample order, and the two halves swap weights at the end.  sigma / noise / zn / znext / is_last /

@@ -124,8 +124,14 @@ __device__ __forceinline__ float fold32(float (&v)[32], int p) {
 // fp16 build: the NaN feature_coarse row that marks a ray whose coarse pass left fp16's range does not exist here, so the mark moves: the range guard of
 // the trunk tiles (xyz embedding, outputs of layers 1..8) is ORed over the coarse tiles, the wave and the pair, and a marked ray leaves with its whole
 // feature_fine row and its depth_fine NaN -- never with finite numbers sampled from a wrong pdf.
-template <class HOOK, bool FINE_ONLY = false, bool LEAN = false>
+// LEAN + FINE_ONLY (crnerf_render_rays_lean_bf16_fine): the fine-only kernel without the weights_fine store; no trunk walk, the ring phase stays 0.
+// CW (crnerf_render_coarse_weights_f16; LEAN, Ni == 0, fp16 build): the lean coarse pass alone, for a caller that reads weights_coarse -- every tile
+// a trunk walk, alternating between the two ring phases, and weights_c is stored as the full kernel stores it.  The range mark is the word 0x7fc00000
+// in weights_c[r][0], written behind the row (by the thread that stored the row's first weight) for a ray the trunk guard tripped on, and for
+// every ray when the pack carries the range flag: what crnerf_render_coarse_weights_f32x3_repair looks for.
+template <class HOOK, bool FINE_ONLY = false, bool LEAN = false, bool CW = false>
 __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, const HOOK& hook) {
+  static_assert(!CW || (LEAN && !FINE_ONLY), "the coarse-weights render is a lean coarse pass");
 #ifdef CRNERF_TIMING
   if (threadIdx.x == 0 && blockIdx.x < 1024) crnerf_wg_times_p[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -146,8 +152,9 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
   // is marked NaN where crnerf_render_rays_f32x3_repair looks for it -- the h2 kernels' convention (render_fused_x3.hip)
   if ((__float_as_uint(((const lds_float*)(lds + LDS_CONST0))[H2_FLAG_WORD]) | __float_as_uint(((const lds_float*)(lds + LDS_CONST1))[H2_FLAG_WORD])) != 0u) {
     for (long rr = (long)blockIdx.x * 512 + threadIdx.x; rr < a.R; rr += (long)gridDim.x * 512) {
+      if constexpr (CW) a.weights_c[rr * a.Nc] = __uint_as_float(0x7fc00000u);
       if constexpr (!LEAN) a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
-      if (a.Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+      if (!CW && a.Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
     }
     return;
   }
@@ -210,7 +217,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
       const int N = pass ? Nf : Nc;
       const lds_float* zsrc = pass ? scr.zs : scr.zc;
       const float* noise_row = pass ? (a.noise_f ? a.noise_f + r * Nf : nullptr) : (a.noise_c ? a.noise_c + r * Nc : nullptr);
-      float* weights_row = LEAN ? nullptr : (pass ? a.weights_f + r * Nf : a.weights_c + r * Nc);
+      float* weights_row = CW ? a.weights_c + r * Nc : LEAN ? nullptr : (pass ? a.weights_f + r * Nf : a.weights_c + r * Nc);
       const bool compose = !LEAN || pass;   // wave-uniform, and the same in all eight waves
       double carry = 1.0;
       float fsum = 0.0f, dacc = 0.0f;
@@ -240,7 +247,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
           for (int s = 0; s < KS_DIR; ++s)
             __builtin_amdgcn_raw_buffer_store_b128(*(const __attribute__((address_space(3))) u32x4*)(dirbuf + 16 * h + 32 * s), xr, (int)(xo + 32u * (KS_XYZ + s)), 0, 0);
         }
-        if constexpr (LEAN) {
+        if constexpr (LEAN && !FINE_ONLY) {
           if (pass == 0) {   // trunk walk; the ring moves on by half a turn
             if (ring_ph) mlp_tile_p<PWalk<TRUNKB_USED, 2>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
             else mlp_tile_p<PWalk<TRUNKB_USED, 0>>(pipe, pass, next_model, pe, dirbuf + 16 * h, feat, sigma, h, q, tm, sv);
@@ -301,7 +308,7 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
           dacc += w * zn;
         }
         if (valid && h == 0) {
-          if (!LEAN && ray_ok) weights_row[n] = w;
+          if ((!LEAN || CW) && ray_ok) weights_row[n] = w;
           if (pass == 0) scr.wc[n] = w;
         }
         tm.tick(T_COMPOSITE);
@@ -330,6 +337,11 @@ __device__ __forceinline__ void render_rays_bf16p_body(const RenderParamsP& a, c
           if (lane == 0) (pass ? a.depth_f : a.depth_c)[r] = dacc + scr.xfeat[64];
         }
       }
+#if CRNERF_P_F16
+      if constexpr (CW) {   // (wave A's lane 0 stored weights_row[0] in step 0: the mark follows it from the same thread)
+        if (half == 0 && lane == 0 && ray_ok && scr.xfeat[LEAN_TRIP_SLOT] != 0.0f) weights_row[0] = __uint_as_float(0x7fc00000u);
+      }
+#endif
       tm.tick(T_X5);
       if (pass == 0 && Ni > 0) {
         sample_pdf_pair(scr, Nc, Ni, a.u ? a.u + r * a.u_stride : nullptr, lane, lane128);
@@ -363,6 +375,9 @@ __global__ __launch_bounds__(512, 2) void CRNERF_P_RENDER_LEAN_KERNEL(RenderPara
 #if !CRNERF_P_F16
 __global__ __launch_bounds__(512, 2) void render_rays_train_bf16p_kernel(RenderParamsP a, TrainHookP hook) { render_rays_bf16p_body(a, hook); }
 __global__ __launch_bounds__(512, 2) void render_rays_bf16p_fine_kernel(RenderParamsP a) { render_rays_bf16p_body<NoHookP, true>(a, NoHookP()); }
+__global__ __launch_bounds__(512, 2) void render_rays_bf16p_lean_fine_kernel(RenderParamsP a) { render_rays_bf16p_body<NoHookP, true, true>(a, NoHookP()); }
+#else
+__global__ __launch_bounds__(512, 2) void render_coarse_weights_f16p_kernel(RenderParamsP a) { render_rays_bf16p_body<NoHookP, false, true, true>(a, NoHookP()); }
 #endif
 
 #if CRNERF_P_F16
@@ -389,6 +404,21 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   const GridPlan plan = plan_grid((a.R + 3) / 4);   // one workgroup per CU, persistent over ray quads
   k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)CRNERF_P_RENDER_SCHED) : nullptr;
+#if CRNERF_P_F16
+  if (a.coarse_weights) {   // crnerf_render_coarse_weights_f16: the lean coarse pass alone; weights_coarse is the only output
+    if (a.Ni != 0) return set_error(-2, "render_coarse_weights: N_importance must be 0");
+    if (a.fine_only || a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_coarse_weights: inference only, random draws come as tensors");
+    k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;
+    return launch_kernel(render_coarse_weights_f16p_kernel, "render_coarse_weights_f16p_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
+  }
+#else
+  if (a.coarse_weights) return set_error(-3, CRNERF_P_RENDER_WHAT ": the coarse-weights render of the pair core exists in the fp16 build only");
+  if (a.lean && a.fine_only) {   // crnerf_render_rays_lean_bf16_fine: weights_fine is never written (abi.hip passes it as null)
+    if (a.train_acts_coarse) return set_error(-3, "render_rays_lean_bf16_fine: no training twin");
+    k.weights_f = nullptr;
+    return launch_kernel(render_rays_bf16p_lean_fine_kernel, "render_rays_bf16p_lean_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
+  }
+#endif
   if (a.lean) {   // crnerf_render_rays_lean_bf16 / _f16: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
     if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
     if (a.fine_only || a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");

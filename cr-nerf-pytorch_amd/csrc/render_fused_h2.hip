@@ -6,6 +6,7 @@
 #define render_rays_x3_rng_kernel render_rays_h2_rng_kernel
 #define render_rays_train_x3_kernel render_rays_train_h2_kernel
 #define render_rays_train_x3_rng_kernel render_rays_train_h2_rng_kernel
+#define render_coarse_weights_x3_kernel render_coarse_weights_h2_kernel
 #define render_rays_x3_body render_rays_h2_body
 #define launch_render_rays_x3 launch_render_rays_h2
 #define RenderParamsX RenderParamsH

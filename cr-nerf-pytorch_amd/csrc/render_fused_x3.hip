@@ -101,7 +101,12 @@ struct TrainHookX {
 
 // RNG: the instantiation with the in-kernel draws -- a template parameter like render_fused16.hip's, so the kernels without draws carry no
 // Philox registers through the MLP loop
-template <bool RNG, class HOOK>
+// CW (crnerf_render_coarse_weights_f32x3 / _f32h2 / _f32x3_repair, include/crnerf_lean_composite.h; Ni == 0): the coarse pass for a caller that reads
+// weights_coarse alone.  Every tile walks the trunk (mlp_tile_x3<.., true>: layers 1..8 + static_sigma, XTRUNK_FRAGS of the stream; the pipe runs that
+// shorter pass), alpha, the scan and the weights are the full kernel's (composite_weight_tile), no feature or depth sum is formed and nothing but
+// weights_c is stored.  There is no feature_c row to carry a NaN, so the mark a repair launch looks for is the word 0x7fc00000 in weights_c[r][0]:
+// written behind the row by the h2 build for a ray with a tile whose range guard tripped, and for every ray when the pack carries the range flag.
+template <bool RNG, class HOOK, bool CW = false>
 __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const HOOK hook) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* lds = (lds_char*)smem;
@@ -113,7 +118,9 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
   if (a.repair) {   // (bit test: this unit is built with -fno-honor-nans)
     const long rr = (long)blockIdx.x * 4 + wave;
     auto is_nan = [](float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; };
-    const bool bad = rr < a.R && (is_nan(a.feature_c[rr * FEAT_DIM]) || (Ni > 0 && is_nan(a.feature_f[rr * FEAT_DIM])));
+    bool bad;
+    if constexpr (CW) bad = rr < a.R && __float_as_uint(a.weights_c[rr * Nc]) == 0x7fc00000u;
+    else bad = rr < a.R && (is_nan(a.feature_c[rr * FEAT_DIM]) || (Ni > 0 && is_nan(a.feature_f[rr * FEAT_DIM])));
     if (!__syncthreads_or(bad)) return;
   }
   load_consts(lds, a.packed0, a.packed1);
@@ -124,8 +131,11 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
     for (int it = 0; it < a.iters; ++it) {
       const long rr = ((long)it * gridDim.x + blockIdx.x) * 4 + wave;
       if (rr < a.R && lane == 0) {
-        a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
-        if (Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+        if constexpr (CW) a.weights_c[rr * Nc] = __uint_as_float(0x7fc00000u);
+        else {
+          a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+          if (Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
+        }
       }
     }
     return;
@@ -142,6 +152,7 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
 
   const int tiles_c = (Nc + 31) >> 5, tiles_f = Ni > 0 ? (Nf + 31) >> 5 : 0;
   WeightPipeX pipe;
+  if constexpr (CW) pipe.set_stream_frags(XTRUNK_FRAGS);
   pipe.start(lds, a.packed0 + CONST_BYTES, a.packed1 + CONST_BYTES, tiles_c, tiles_c + tiles_f, lane, wave);
   xu32x4 cur[X_AHEAD];
   pipe.prime(cur);
@@ -192,7 +203,9 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
       const float* noise_row = pass ? (a.noise_f ? a.noise_f + r * Nf : nullptr) : (a.noise_c ? a.noise_c + r * Nc : nullptr);
       float* weights_row = pass ? a.weights_f + r * Nf : a.weights_c + r * Nc;
       CompositeState st;
-      st.reset();
+      if constexpr (!CW) st.reset();
+      double t_carry = 1.0;   // CW: all the compositing state there is
+      bool trip = false;      // CW, h2: a tile of this ray left fp16's range
       const int tiles = (N + 31) >> 5;
 #pragma unroll 1
       for (int tile = 0; tile < tiles; ++tile) {
@@ -212,7 +225,10 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
         }
         float sigma;
         const auto sv = hook.saver(pass, r, N, n, valid && ray_ok, h);
-        mlp_tile_x3(pipe, pass, pe, dv, feat, sigma, h, cur, tm, sv);
+        if constexpr (CW) {
+          mlp_tile_x3<NoSaveX, true>(pipe, pass, pe, dv, feat, sigma, h, cur, tm);
+          trip |= valid && __float_as_uint(sigma) == 0x7fc00000u;   // (the h2 trunk tile's poison, by bit pattern; softplus of a finite sum is finite)
+        } else mlp_tile_x3(pipe, pass, pe, dv, feat, sigma, h, cur, tm, sv);
         hook.raw(pass, r, N, n, valid && ray_ok, h, feat, sigma);
         float noise = (noise_row && valid) ? noise_row[n] * a.noise_std : 0.0f;
         if (RNG && (a.rng_flags & 4) && valid) {          // rendering.py:125  noise = randn_like(sigma) * noise_std
@@ -221,16 +237,23 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
           float* no = pass ? a.noise_f_out : a.noise_c_out;
           if (no && ray_ok && h == 0) no[r * N + n] = draw;
         }
-        const float w = composite_tile(st, feat, sigma, noise, zn, znext, n == N - 1, valid, p);
+        float w;
+        if constexpr (CW) w = composite_weight_tile(t_carry, sigma, noise, zn, znext, n == N - 1, valid, p);
+        else w = composite_tile(st, feat, sigma, noise, zn, znext, n == N - 1, valid, p);
         if (valid && h == 0) {
           if (ray_ok) weights_row[n] = w;
           if (pass == 0) scr.wc[n] = w;
         }
         tm.tick(T_COMPOSITE);
       }
-      composite_finish(st);
-      if (ray_ok)
-        store_ray_feature(st, (pass ? a.feature_f : a.feature_c) + r * FEAT_DIM, (pass ? a.depth_f : a.depth_c) + r, p, h);
+      if constexpr (CW) {
+        // the mark goes in behind the row, from the lane that stored weights_row[0] in tile 0: one thread's two stores to one address stay in order
+        if (XNP == 2 && __ballot(trip) != 0ull && ray_ok && lane == 0) weights_row[0] = __uint_as_float(0x7fc00000u);
+      } else {
+        composite_finish(st);
+        if (ray_ok)
+          store_ray_feature(st, (pass ? a.feature_f : a.feature_c) + r * FEAT_DIM, (pass ? a.depth_f : a.depth_c) + r, p, h);
+      }
       if (pass == 0 && Ni > 0) {
         wave_lds_fence();
         sample_pdf_wave(scr, Nc, Ni, a.u ? a.u + r * a.u_stride : nullptr, lane, (RNG && (a.rng_flags & 2)) ? &rng : nullptr, rng_ray);
@@ -250,6 +273,7 @@ __global__ __launch_bounds__(256, 1) void render_rays_x3_kernel(RenderParamsX a)
 __global__ __launch_bounds__(256, 1) void render_rays_x3_rng_kernel(RenderParamsX a) { render_rays_x3_body<true>(a, NoHookX()); }
 __global__ __launch_bounds__(256, 1) void render_rays_train_x3_kernel(RenderParamsX a, TrainHookX hook) { render_rays_x3_body<false>(a, hook); }
 __global__ __launch_bounds__(256, 1) void render_rays_train_x3_rng_kernel(RenderParamsX a, TrainHookX hook) { render_rays_x3_body<true>(a, hook); }
+__global__ __launch_bounds__(256, 1) void render_coarse_weights_x3_kernel(RenderParamsX a) { render_rays_x3_body<false, NoHookX, true>(a, NoHookX()); }
 
 int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
   if (a.R <= 0) return 0;
@@ -264,6 +288,12 @@ int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
   const GridPlan plan = plan_grid(quads, a.repair);   // one workgroup per CU, persistent over ray quads (repair: one per quad)
   k.iters = plan.iters;
   const size_t shmem = LDS_SCRATCH_X + 4 * SCRATCH_BYTES;
+  if (a.coarse_weights) {   // crnerf_render_coarse_weights_f32x3 / _f32h2 / _f32x3_repair: weights_coarse only (abi.hip passes the other outputs as null)
+    if (a.Ni != 0) return set_error(-2, "render_coarse_weights: N_importance must be 0");
+    if (rngk || a.train_acts_coarse) return set_error(-3, "render_coarse_weights: inference only, random draws come as tensors");
+    k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;
+    return launch_kernel(render_coarse_weights_x3_kernel, "render_coarse_weights_x3_kernel", plan.grid, 256, shmem, stream, k);
+  }
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_f32x3 / _f32h2; repair: the rays the h2 twin poisoned, saved rows included)
     if (int rc = check_train_state("render_rays_train_f32x3", a)) return rc;
     if ((unsigned long long)a.R * (unsigned)(a.Nc + a.Ni) * 1024ull >= (unsigned long long)SAVEX_OOB)

@@ -25,7 +25,8 @@ inline namespace xcore_x3 {
 constexpr int XNP = CRNERF_X_NP;
 static_assert(XNP == 2 || XNP == 3, "x core: two fp16 pieces or three bf16 pieces");
 constexpr int XSTREAM_FRAGS = XNP == 2 ? STREAMH_FRAGS : STREAMX_FRAGS;       // forward stream of a model
-constexpr int XPAD_DIR = XNP == 2 ? 0 : FX_DIR - FX_DIR_USED;                 // stage / queue padding behind dir_encoding
+constexpr int XTRUNK_FRAGS = XNP == 2 ? OFFH_FIN : OFFX_FIN;                  // its trunk: layers 1..8 (the stream is in layer order)
+constexpr int XPAD_DIR =XNP == 2 ? 0 : FX_DIR - FX_DIR_USED;                 // stage / queue padding behind dir_encoding
 constexpr float XWSCALE = XNP == 2 ? H2_WSCALE : 1.0f;                        // the packed weights carry this factor
 
 #if CRNERF_X_NP == 2

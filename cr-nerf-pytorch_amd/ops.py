@@ -607,10 +607,58 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     return out
 
 
+# the coarse-weights entry of a precision (include/crnerf_lean_composite.h)
+_COARSE_WEIGHTS = {"f32h2": "crnerf_render_coarse_weights_f32h2", "f32x3": "crnerf_render_coarse_weights_f32x3", "f16": "crnerf_render_coarse_weights_f16"}
+
+
+def render_coarse_weights(packed_coarse, rays, n_samples, precision="auto", use_disp=False, z_coarse=None, z_steps=None, noise_coarse=None, noise_std=0.0,
+                          repair_x3=None):
+    """The coarse pass for its compositing weights alone: {"weights_coarse": [R,Nc]}, bit-identical to render_rays(packed_coarse, None, rays, n_samples, 0,
+    precision=...)["weights_coarse"] -- every tile stops behind static_sigma, no feature or depth is composited, nothing else is written
+    (crnerf_render_coarse_weights_*, include/crnerf_lean_composite.h).  Inference only; random draws come as tensors.
+    precision "f32h2" / "f32x3" / "f16": that core, packs as for render_rays.  "f32h2" and "f16" mark a ray that left fp16's range by the word 0x7fc00000
+    (a NaN) in weights_coarse[r, 0].  "auto" (an AutoPack): the h2 entry, then crnerf_render_coarse_weights_f32x3_repair, which renders the marked ray
+    quads again on the x3 core and leaves at once when there is none; a refused h2 pack: the x3 entry throughout.  "f16" with repair_x3=(the coarse
+    model's x3 pack): the same repair behind the fp16 entry."""
+    name = resolve(precision)
+    if name not in _COARSE_WEIGHTS and name != "auto":
+        raise ValueError("crnerf_amd: render_coarse_weights exists for precision='f32h2', 'f32x3', 'auto' and 'f16', got %r" % (name,))
+    if repair_x3 is not None and name != "f16":
+        raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 pack)")
+    lib = _lib.load()
+    repair = repair_x3
+    if name == "auto":
+        if not isinstance(packed_coarse, AutoPack):
+            raise ValueError("crnerf_amd: precision='auto' needs a pack from pack_mlp_weights(..., precision='auto')")
+        if packed_coarse.h2 is None:
+            name, packed_coarse = "f32x3", packed_coarse.x3
+        else:
+            name, repair, packed_coarse = "f32h2", packed_coarse.x3, packed_coarse.h2
+    _check_pack(lib, name, packed_coarse)
+    _check_pack(lib, "f32x3", repair)
+    rays = _f32c(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be [R,8], got %s" % (tuple(rays.shape),))
+    R, Nc = rays.shape[0], int(n_samples)
+    out = {"weights_coarse": torch.empty(R, Nc, dtype=torch.float32, device=rays.device)}
+    if R == 0:
+        return out
+    a, keep = _render_args(rays, {"view_dir": None, "z_coarse": z_coarse, "z_steps": z_steps, "u": None, "noise_coarse": noise_coarse, "noise_fine": None},
+                           noise_std, use_disp, Nc, 0, out)
+    a.packed_coarse = packed_coarse.data_ptr()
+    _lib.check(getattr(lib, _COARSE_WEIGHTS[name])(ctypes.byref(a), _lib.stream_ptr()), _COARSE_WEIGHTS[name])
+    if repair is not None:
+        a.packed_coarse = repair.data_ptr()
+        _lib.check(lib.crnerf_render_coarse_weights_f32x3_repair(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_coarse_weights_f32x3_repair")
+    return out
+
+
 def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
-                          noise_fine=None, noise_std=0.0, want_z_fine=False):
+                          noise_fine=None, noise_std=0.0, want_z_fine=False, lean=False):
     """crnerf_render_rays_bf16_fine: sample_pdf + z merge on `weights_coarse` [R,Nc] (rendered by another core, e.g. render_rays(..., n_importance=0,
-    precision="auto")) and the fine model on the bf16 matrix cores, fused -- {"weights_fine", "feature_fine", "depth_fine"[, "z_fine"]}."""
+    precision="auto")) and the fine model on the bf16 matrix cores, fused -- {"weights_fine", "feature_fine", "depth_fine"[, "z_fine"]}.
+    lean=True: crnerf_render_rays_lean_bf16_fine -- the same launch without weights_fine (neither allocated nor written); the other tensors are
+    bit-identical."""
     lib = _lib.load()
     _check_pack(lib, "bf16", packed_fine_bf16)
     rays, weights_coarse = _f32c(rays, "rays"), _f32c(weights_coarse, "weights_coarse")
@@ -620,7 +668,7 @@ def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_i
         raise ValueError("render_rays_bf16_fine: rays [R,8], weights_coarse [R,%d] and n_importance > 0 expected, got %s / %s / %d"
                          % (Nc, tuple(rays.shape), tuple(weights_coarse.shape), Ni))
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    out = {"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)}
+    out = {"feature_fine": new(R, 64), "depth_fine": new(R)} if lean else {"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)}
     if want_z_fine:
         out["z_fine"] = new(R, Nc + Ni)
     if R == 0:
@@ -629,7 +677,8 @@ def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_i
                            Nc, Ni, out)
     a.packed_fine = packed_fine_bf16.data_ptr()
     a.weights_coarse = weights_coarse.data_ptr()                    # INPUT of this entry point
-    _lib.check(lib.crnerf_render_rays_bf16_fine(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_rays_bf16_fine")
+    fn_name = "crnerf_render_rays_lean_bf16_fine" if lean else "crnerf_render_rays_bf16_fine"
+    _lib.check(getattr(lib, fn_name)(ctypes.byref(a), _lib.stream_ptr()), fn_name)
     return out
 
 

@@ -22,6 +22,7 @@
 #define CRNERF_LEAN_H
 
 #include "crnerf.h"
+#include "crnerf_lean_composite.h"   /* the coarse-weights renders and the lean fine launch behind lean=True in "bf16_hc" / "bf16_fc" */
 
 #ifdef __cplusplus
 extern "C" {
