@@ -27,9 +27,9 @@ def set_precision(precision):
     core refuses runs on f32x3, a ray (a 128-point group) the h2 core poisoned is re-rendered on f32x3 inside the same call, so that no NaN of
     the h2 core's making reaches the caller (include/crnerf.h "auto"), or "bf16_hc": bf16 with an fp32-accurate COARSE pass ("auto" arithmetic on the
     coarse network's 25 % of the points, the fine network on the bf16 matrix cores: the fine depths then follow the fp32 reference;
-    models/rendering.py::_render_bf16_accurate_coarse), or "bf16_fc": bf16 with an FP16 coarse pass -- the coarse network with one-piece fp16
+    models/rendering.py::_render_bf16_composite), or "bf16_fc": bf16 with an FP16 coarse pass -- the coarse network with one-piece fp16
     operands (11 significand bits instead of bf16's 8 at bf16's cost; include/crnerf.h "f16"), rays whose activations leave fp16's range re-rendered on
-    f32x3 inside the call, the fine network on the bf16 matrix cores (models/rendering.py::_render_bf16_f16_coarse): between "bf16" and "bf16_hc" in
+    f32x3 inside the call, the fine network on the bf16 matrix cores (models/rendering.py::_render_bf16_composite, f16_coarse): between "bf16" and "bf16_hc" in
     accuracy, at about "bf16"'s frame time; "f16": both networks with fp16 operands (NaN rows where a point leaves fp16's range -- no repair).
     A `precision=` keyword to render_rays_cross_ray / batched_inference /
     NeRF_sigma.forward overrides it per call.

@@ -6,6 +6,7 @@ eager/CPU fallback behind these functions.
 import ctypes
 import os
 import threading
+import types
 
 import torch
 
@@ -296,6 +297,8 @@ SWEEP_SIGNATURES = {
     "crnerf_crossray_style_stats_f32": (i32, [vp, i32, i64, i64, pp, vp, vp, vp]),
     "crnerf_crossray_decode_multi_f32": (i32, [ctypes.POINTER(SweepDecodeArgs), vp]),
 }
+# The five tables as one read-only view, in the order load() binds them: every symbol the library must export.
+ALL_SIGNATURES = types.MappingProxyType({**SIGNATURES, **BLENDER_SIGNATURES, **LEAN_SIGNATURES, **LEAN_COMPOSITE_SIGNATURES, **SWEEP_SIGNATURES})
 
 
 _lib = None
@@ -315,7 +318,7 @@ def load():
                 "crnerf_amd: %s not found -- build it with `python cr-nerf-pytorch_amd/build.py` "
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BLENDER_SIGNATURES.items()) + list(LEAN_SIGNATURES.items()) + list(LEAN_COMPOSITE_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
+        for name, (res, args) in ALL_SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_sweep.h
             fn.restype = res
             fn.argtypes = args

@@ -1,6 +1,8 @@
 // extern "C" surface of libcrnerf_hip.so -- see include/crnerf.h for the contract of every symbol.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <mutex>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -201,16 +203,59 @@ static int require_train_state(const crnerf_render_args* a, const TrainState& t)
   return 0;
 }
 
-static int render_rays_common(const crnerf_render_args* a, void* stream, Core core, const TrainState& train = TrainState()) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays: negative n_rays");
-  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->rays, "rays");
-  REQUIRE(a->weights_coarse, "weights_coarse"); REQUIRE(a->feature_coarse, "feature_coarse"); REQUIRE(a->depth_coarse, "depth_coarse");
-  if (a->n_importance > 0) {
-    REQUIRE(a->packed_fine, "packed_fine");
-    REQUIRE(a->weights_fine, "weights_fine"); REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
+// A pointer field of crnerf_render_args: where it is, and what is said when it is missing
+struct Field { size_t at; const char* null_text; };
+typedef crnerf_render_args A;
+static const Field PACKED_COARSE = {offsetof(A, packed_coarse), "packed_coarse is NULL"}, PACKED_FINE = {offsetof(A, packed_fine), "packed_fine is NULL"}, RAYS = {offsetof(A, rays), "rays is NULL"},
+                   U = {offsetof(A, u), "u is NULL"}, NOISE_COARSE = {offsetof(A, noise_coarse), "noise_coarse is NULL"}, NOISE_FINE = {offsetof(A, noise_fine), "noise_fine is NULL"},
+                   WEIGHTS_COARSE = {offsetof(A, weights_coarse), "weights_coarse is NULL"}, WEIGHTS_COARSE_IN = {offsetof(A, weights_coarse), "weights_coarse (input) is NULL"},
+                   FEATURE_COARSE = {offsetof(A, feature_coarse), "feature_coarse is NULL"}, DEPTH_COARSE = {offsetof(A, depth_coarse), "depth_coarse is NULL"},
+                   WEIGHTS_FINE = {offsetof(A, weights_fine), "weights_fine is NULL"}, FEATURE_FINE = {offsetof(A, feature_fine), "feature_fine is NULL"},
+                   DEPTH_FINE = {offsetof(A, depth_fine), "depth_fine is NULL"}, Z_FINE = {offsetof(A, z_fine), "z_fine is NULL"};
+
+// the range an entry accepts a sample count in; what == nullptr: no rule of the entry's own (the launch layer's stand)
+struct Range { int lo, hi, code; const char* what; };
+static const Range LEAN_NI = {1, 256, CRNERF_ERR_SHAPE, "n_importance must be in [1, 256]"}, LEAN_NS = {3, 256, CRNERF_ERR_SHAPE, "n_samples must be in [3, 256]"};
+
+// One render entry: what it checks, in the order render_entry checks it, and what it hands its launcher.  The Field lists end at an empty Field.
+struct RenderEntry {
+  const char* who;                // the name in its error texts
+  Range n_importance, n_samples;
+  Field required[7];              // non-null, asked for in this order
+  Field required_fine[5];         // the same, when n_importance > 0
+  const char* no_draws;           // the one refusal of rng_flags and the three *_out; nullptr: render_rays' rule by rule (check_draws)
+  RenderMode mode;
+  Field ignored[10];              // null for the launcher, whatever the caller passed
+};
+static const RenderEntry
+    RENDER_RAYS = {"render_rays", {}, {}, {PACKED_COARSE, RAYS, WEIGHTS_COARSE, FEATURE_COARSE, DEPTH_COARSE}, {PACKED_FINE, WEIGHTS_FINE, FEATURE_FINE, DEPTH_FINE},
+                   nullptr, RenderMode::Full, {}},
+    // no coarse pass: one pack, the fine model's, and weights_coarse is the INPUT
+    BF16_FINE = {"render_rays_bf16_fine", {1, INT_MAX, CRNERF_ERR_CONFIG, "n_importance must be > 0"}, {},
+                 {PACKED_FINE, RAYS, WEIGHTS_COARSE_IN, WEIGHTS_FINE, FEATURE_FINE, DEPTH_FINE}, {},
+                 "no in-kernel random draws in the bf16 kernels", RenderMode::FineOnly, {NOISE_COARSE, FEATURE_COARSE, DEPTH_COARSE}},
+    LEAN = {"render_rays_lean", LEAN_NI, LEAN_NS, {PACKED_COARSE, PACKED_FINE, RAYS, FEATURE_FINE, DEPTH_FINE}, {},
+            "no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)", RenderMode::Lean,
+            {WEIGHTS_COARSE, FEATURE_COARSE, DEPTH_COARSE, WEIGHTS_FINE}},
+    // include/crnerf_lean_composite.h: the coarse pass for its compositing weights alone, and the lean fine launch behind it
+    COARSE_WEIGHTS = {"render_coarse_weights", {0, 0, CRNERF_ERR_SHAPE, "n_importance must be 0 (the fine pass is crnerf_render_rays_lean_bf16_fine)"},
+                      {2, 256, CRNERF_ERR_SHAPE, "n_samples must be in [2, 256]"}, {PACKED_COARSE, RAYS, WEIGHTS_COARSE}, {},
+                      "no in-kernel random draws (hand them over as z_coarse / noise_coarse)", RenderMode::CoarseWeights,
+                      {PACKED_FINE, U, NOISE_FINE, FEATURE_COARSE, DEPTH_COARSE, WEIGHTS_FINE, FEATURE_FINE, DEPTH_FINE, Z_FINE}},
+    LEAN_BF16_FINE = {"render_rays_lean_bf16_fine", LEAN_NI, LEAN_NS, {PACKED_FINE, RAYS, WEIGHTS_COARSE_IN, FEATURE_FINE, DEPTH_FINE}, {},
+                      "no in-kernel random draws in the bf16 kernels", RenderMode::LeanFineOnly, {NOISE_COARSE, FEATURE_COARSE, DEPTH_COARSE, WEIGHTS_FINE}};
+
+static int require_fields(const crnerf_render_args* a, const Field* list) {
+  for (const void* p; list->null_text; ++list) {
+    memcpy(&p, (const char*)a + list->at, sizeof p);
+    if (!p) return set_error(CRNERF_ERR_NULL, list->null_text);
   }
+  return 0;
+}
+static int check_range(const RenderEntry& e, const Range& r, int n) { return (r.what && (n < r.lo || n > r.hi)) ? fail(r.code, e.who, r.what) : 0; }
+
+// crnerf_render_rays_*: what may be drawn in the kernel, flag by flag
+static int check_draws(const crnerf_render_args* a, Core core) {
   if (a->rng_flags) {
     if (a->rng_flags & ~(CRNERF_RNG_JITTER | CRNERF_RNG_U | CRNERF_RNG_NOISE)) return set_error(CRNERF_ERR_CONFIG, "render_rays: unknown rng_flags bits");
     if (is_pair_core(core)) return set_error(CRNERF_ERR_CONFIG, "render_rays: in-kernel random draws exist in the fp32, f32x3 and f32h2 kernels only");
@@ -220,25 +265,51 @@ static int render_rays_common(const crnerf_render_args* a, void* stream, Core co
   }
   if ((a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out) && is_pair_core(core))   // (the bf16 kernels do not write them)
     return set_error(CRNERF_ERR_CONFIG, "render_rays: z_coarse_out / noise_*_out are written by the fp32, f32x3 and f32h2 kernels only");
-  auto r = to_render_args(a);
-  r.train_acts_coarse = train.acts_coarse; r.train_acts_fine = train.acts_fine; r.train_raw_coarse = train.raw_coarse; r.train_raw_fine = train.raw_fine;
-  switch (core) {
-    case Core::H2: return launch_render_rays_h2(r, (hipStream_t)stream);
-    case Core::X3_REPAIR: r.repair = 1; return launch_render_rays_x3(r, (hipStream_t)stream);
-    case Core::X3: return launch_render_rays_x3(r, (hipStream_t)stream);
-    case Core::F16_PAIR: return launch_render_rays_f16p(r, (hipStream_t)stream);
-    case Core::BF16_PAIR: return launch_render_rays_bf16p(r, (hipStream_t)stream);
-    case Core::F32: break;
-  }
-  return launch_render_rays16(r, (hipStream_t)stream);
+  return 0;
 }
 
-// the five crnerf_render_rays_train_*: the saved state is checked before anything render_rays_common checks
+static int launch_core(Core core, RenderArgs& r, hipStream_t stream) {
+  switch (core) {
+    case Core::H2: return launch_render_rays_h2(r, stream);
+    case Core::X3_REPAIR: r.repair = 1; [[fallthrough]];
+    case Core::X3: return launch_render_rays_x3(r, stream);
+    case Core::F16_PAIR: return launch_render_rays_f16p(r, stream);
+    case Core::BF16_PAIR: return launch_render_rays_bf16p(r, stream);
+    case Core::F32: break;
+  }
+  return launch_render_rays16(r, stream);
+}
+
+// The sequence every render entry follows.
+static int render_entry(const crnerf_render_args* a, void* stream, const RenderEntry& e, Core core, const TrainState& train = TrainState()) {
+  REQUIRE(a, "args");
+  if (a->n_rays == 0) return 0;
+  if (a->n_rays < 0) return fail(CRNERF_ERR_SHAPE, e.who, "negative n_rays");
+  if (int rc = check_range(e, e.n_importance, a->n_importance)) return rc;
+  if (int rc = check_range(e, e.n_samples, a->n_samples)) return rc;
+  if (int rc = require_fields(a, e.required)) return rc;
+  if (a->n_importance > 0)
+    if (int rc = require_fields(a, e.required_fine)) return rc;
+  if (!e.no_draws) {
+    if (int rc = check_draws(a, core)) return rc;
+  } else if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out) {
+    return fail(CRNERF_ERR_CONFIG, e.who, e.no_draws);
+  }
+  crnerf_render_args b = *a;
+  for (const Field* f = e.ignored; f->null_text; ++f) memset((char*)&b + f->at, 0, sizeof(void*));
+  if (e.mode == RenderMode::FineOnly || e.mode == RenderMode::LeanFineOnly) b.packed_coarse = b.packed_fine;
+  auto r = to_render_args(&b);
+  r.mode = e.mode;
+  r.train_acts_coarse = train.acts_coarse; r.train_acts_fine = train.acts_fine; r.train_raw_coarse = train.raw_coarse; r.train_raw_fine = train.raw_fine;
+  return launch_core(core, r, (hipStream_t)stream);
+}
+
+// the five crnerf_render_rays_train_*: the saved state is checked before anything render_entry checks
 static int render_rays_train(const crnerf_render_args* a, const TrainState& train, void* stream, Core core) {
   REQUIRE(a, "args");
   if (a->n_rays == 0) return 0;
   if (int rc = require_train_state(a, train)) return rc;
-  return render_rays_common(a, stream, core, train);
+  return render_entry(a, stream, RENDER_RAYS, core, train);
 }
 
 extern "C" {
@@ -342,7 +413,7 @@ int crnerf_sample_pdf_merge_f32(const float* z_coarse, const float* weights_coar
   return launch_sample_pdf_merge(z_coarse, weights_coarse, u, (long)u_stride, z_sorted, z_samples, (long)R, Nc, Ni, (hipStream_t)stream);
 }
 
-int crnerf_render_rays_f32(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::F32); }
+int crnerf_render_rays_f32(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::F32); }
 int crnerf_rng_fill_f32(float* out, int64_t n_rays, int n, uint64_t seed, int stream_id, int64_t ray_offset, void* stream) {
   if (n_rays == 0 || n == 0) return 0;
   REQUIRE(out, "out");
@@ -351,103 +422,19 @@ int crnerf_rng_fill_f32(float* out, int64_t n_rays, int n, uint64_t seed, int st
   return launch_rng_fill(out, (long)n_rays, n, seed, stream_id, (long)ray_offset, (hipStream_t)stream);
 }
 
-int crnerf_render_rays_bf16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::BF16_PAIR); }
+int crnerf_render_rays_bf16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::BF16_PAIR); }
 
-int crnerf_render_rays_bf16_fine(const crnerf_render_args* a, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_bf16_fine: negative n_rays");
-  if (a->n_importance <= 0) return set_error(CRNERF_ERR_CONFIG, "render_rays_bf16_fine: n_importance must be > 0");
-  REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays"); REQUIRE(a->weights_coarse, "weights_coarse (input)");
-  REQUIRE(a->weights_fine, "weights_fine"); REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
-  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
-    return set_error(CRNERF_ERR_CONFIG, "render_rays_bf16_fine: no in-kernel random draws in the bf16 kernels");
-  auto r = to_render_args(a);
-  r.packed_coarse = a->packed_fine;                                                   // one pack: the fine model's
-  r.noise_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr;     // no coarse pass; weights_coarse is the INPUT
-  r.fine_only = 1;
-  return launch_render_rays_bf16p(r, (hipStream_t)stream);
-}
-
-int crnerf_render_rays_lean_f32(const crnerf_render_args* a, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: negative n_rays");
-  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_importance must be in [1, 256]");
-  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_samples must be in [3, 256]");
-  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays");
-  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
-  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
-    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean: no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)");
-  auto r = to_render_args(a);
-  r.weights_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr;   // ignored, whatever the caller passed
-  r.lean = 1;
-  return launch_render_rays16(r, (hipStream_t)stream);
-}
-
-// include/crnerf_lean.h: the same checks, codes and texts on the pair core's two builds
-static int render_rays_lean_pair(const crnerf_render_args* a, void* stream, Core core) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: negative n_rays");
-  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_importance must be in [1, 256]");
-  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean: n_samples must be in [3, 256]");
-  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays");
-  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
-  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
-    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean: no in-kernel random draws in the lean kernel (hand them over as z_coarse / u / noise_*)");
-  auto r = to_render_args(a);
-  r.weights_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr;   // ignored, whatever the caller passed
-  r.lean = 1;
-  return core == Core::F16_PAIR ? launch_render_rays_f16p(r, (hipStream_t)stream) : launch_render_rays_bf16p(r, (hipStream_t)stream);
-}
-int crnerf_render_rays_lean_bf16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::BF16_PAIR); }
-int crnerf_render_rays_lean_f16(const crnerf_render_args* a, void* stream) { return render_rays_lean_pair(a, stream, Core::F16_PAIR); }
-
-// include/crnerf_lean.h: the coarse pass for its compositing weights alone (what the lean composite modes put in front of the lean fine launch)
-static int render_coarse_weights(const crnerf_render_args* a, void* stream, Core core) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: negative n_rays");
-  if (a->n_importance != 0) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: n_importance must be 0 (the fine pass is crnerf_render_rays_lean_bf16_fine)");
-  if (a->n_samples < 2 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_coarse_weights: n_samples must be in [2, 256]");
-  REQUIRE(a->packed_coarse, "packed_coarse"); REQUIRE(a->rays, "rays"); REQUIRE(a->weights_coarse, "weights_coarse");
-  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
-    return set_error(CRNERF_ERR_CONFIG, "render_coarse_weights: no in-kernel random draws (hand them over as z_coarse / noise_coarse)");
-  auto r = to_render_args(a);
-  r.packed_fine = nullptr; r.u = nullptr; r.noise_fine = nullptr;                     // ignored, whatever the caller passed
-  r.feature_coarse = nullptr; r.depth_coarse = nullptr; r.weights_fine = nullptr; r.feature_fine = nullptr; r.depth_fine = nullptr; r.z_fine = nullptr;
-  r.coarse_weights = 1;
-  switch (core) {
-    case Core::H2: return launch_render_rays_h2(r, (hipStream_t)stream);
-    case Core::X3_REPAIR: r.repair = 1; return launch_render_rays_x3(r, (hipStream_t)stream);
-    case Core::X3: return launch_render_rays_x3(r, (hipStream_t)stream);
-    default: return launch_render_rays_f16p(r, (hipStream_t)stream);
-  }
-}
-int crnerf_render_coarse_weights_f32h2(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::H2); }
-int crnerf_render_coarse_weights_f32x3(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::X3); }
-int crnerf_render_coarse_weights_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::X3_REPAIR); }
-int crnerf_render_coarse_weights_f16(const crnerf_render_args* a, void* stream) { return render_coarse_weights(a, stream, Core::F16_PAIR); }
-
-int crnerf_render_rays_lean_bf16_fine(const crnerf_render_args* a, void* stream) {
-  REQUIRE(a, "args");
-  if (a->n_rays == 0) return 0;
-  if (a->n_rays < 0) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: negative n_rays");
-  if (a->n_importance < 1 || a->n_importance > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: n_importance must be in [1, 256]");
-  if (a->n_samples < 3 || a->n_samples > 256) return set_error(CRNERF_ERR_SHAPE, "render_rays_lean_bf16_fine: n_samples must be in [3, 256]");
-  REQUIRE(a->packed_fine, "packed_fine"); REQUIRE(a->rays, "rays"); REQUIRE(a->weights_coarse, "weights_coarse (input)");
-  REQUIRE(a->feature_fine, "feature_fine"); REQUIRE(a->depth_fine, "depth_fine");
-  if (a->rng_flags || a->z_coarse_out || a->noise_coarse_out || a->noise_fine_out)
-    return set_error(CRNERF_ERR_CONFIG, "render_rays_lean_bf16_fine: no in-kernel random draws in the bf16 kernels");
-  auto r = to_render_args(a);
-  r.packed_coarse = a->packed_fine;                                                   // one pack: the fine model's
-  r.noise_coarse = nullptr; r.feature_coarse = nullptr; r.depth_coarse = nullptr;     // no coarse pass; weights_coarse is the INPUT
-  r.weights_fine = nullptr;                                                           // ignored, whatever the caller passed
-  r.fine_only = 1;
-  r.lean = 1;
-  return launch_render_rays_bf16p(r, (hipStream_t)stream);
-}
+int crnerf_render_rays_bf16_fine(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, BF16_FINE, Core::BF16_PAIR); }
+int crnerf_render_rays_lean_f32(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::F32); }
+// include/crnerf_lean.h
+int crnerf_render_rays_lean_bf16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::BF16_PAIR); }
+int crnerf_render_rays_lean_f16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::F16_PAIR); }
+// include/crnerf_lean_composite.h
+int crnerf_render_coarse_weights_f32h2(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::H2); }
+int crnerf_render_coarse_weights_f32x3(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::X3); }
+int crnerf_render_coarse_weights_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::X3_REPAIR); }
+int crnerf_render_coarse_weights_f16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::F16_PAIR); }
+int crnerf_render_rays_lean_bf16_fine(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN_BF16_FINE, Core::BF16_PAIR); }
 
 size_t crnerf_packed_mlp_mixed_bytes(void) { return gemm_packed_bytes(); }
 size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_acts_bytes((long)n); }
@@ -534,7 +521,7 @@ int crnerf_mlp_forward_f32x3(const void* packed, const float* x, float* out, int
   return forward_entry("mlp_forward_f32x3", packed, x, out, n, [&](long P) { return launch_mlp_forward_x3(packed, x, out, P, sigma_only, (hipStream_t)stream, 0); });
 }
 
-int crnerf_render_rays_f32x3(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::X3); }
+int crnerf_render_rays_f32x3(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::X3); }
 
 size_t crnerf_packed_mlp_h2_bytes(void) { return PACKEDH_BYTES; }
 
@@ -556,11 +543,11 @@ int crnerf_mlp_forward_f32h2(const void* packed, const float* x, float* out, int
   return forward_entry("mlp_forward_f32h2", packed, x, out, n, [&](long P) { return launch_mlp_forward_h2(packed, x, out, P, sigma_only, (hipStream_t)stream, 0); });
 }
 
-int crnerf_render_rays_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::X3_REPAIR); }
+int crnerf_render_rays_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::X3_REPAIR); }
 int crnerf_mlp_forward_f32x3_repair(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
   return forward_entry("mlp_forward_f32x3_repair", packed, x, out, n, [&](long P) { return launch_mlp_forward_x3(packed, x, out, P, sigma_only, (hipStream_t)stream, 1); });
 }
-int crnerf_render_rays_f32h2(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::H2); }
+int crnerf_render_rays_f32h2(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::H2); }
 
 int crnerf_render_rays_train_f32x3(const crnerf_render_args* a, void* acts_coarse, void* acts_fine, float* raw_coarse, float* raw_fine, void* stream) {
   return render_rays_train(a, {acts_coarse, acts_fine, raw_coarse, raw_fine}, stream, Core::X3);
@@ -594,7 +581,7 @@ int crnerf_mlp_forward_f16(const void* packed, const float* x, float* out, int64
   return forward_entry("mlp_forward_f16", packed, x, out, n, [&](long P) { return launch_mlp_forward_f16p(packed, x, out, P, sigma_only, (hipStream_t)stream); });
 }
 
-int crnerf_render_rays_f16(const crnerf_render_args* a, void* stream) { return render_rays_common(a, stream, Core::F16_PAIR); }
+int crnerf_render_rays_f16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, RENDER_RAYS, Core::F16_PAIR); }
 
 size_t crnerf_encoder_workspace_bytes(int H, int W) { return encoder_workspace_bytes(H, W); }
 

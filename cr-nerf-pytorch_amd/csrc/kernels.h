@@ -89,6 +89,18 @@ int launch_composite_backward(const float* raw, const float* z, const float* noi
 int launch_sample_pdf_merge(const float* z_coarse, const float* weights_coarse, const float* u, long u_stride, float* z_fine_sorted,
                             float* z_samples, long R, int Nc, int Ni, hipStream_t stream);
 
+// What a fused render launch computes.  The launchers of the cores that do not have a mode do not look at it.
+enum class RenderMode {
+  Full,            // coarse pass, sample_pdf + merge, fine pass
+  FineOnly,        // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT (rendered by another core); sample_pdf + merge + the fine pass only
+  Lean,            // crnerf_render_rays_lean_f32 (render_fused16.hip), _lean_bf16 / _lean_f16 (render_fused_bf16p.hip; include/crnerf_lean.h): trunk-only
+                   // coarse pass; writes feature_fine, depth_fine and (optional) z_fine only
+  LeanFineOnly,    // crnerf_render_rays_lean_bf16_fine: the fine-only kernel without weights_fine
+  CoarseWeights,   // crnerf_render_coarse_weights_* (include/crnerf_lean_composite.h; render_fused_x3.hip both builds, the fp16 pair core): Ni == 0, every
+                   // tile walks the trunk, weights_coarse is the only output and carries the range mark (0x7fc00000 in [r][0]); with `repair` the x3
+                   // launcher looks for that mark
+};
+
 struct RenderArgs {
   const void* packed_coarse;
   const void* packed_fine;     // may be null when n_importance == 0
@@ -121,15 +133,8 @@ struct RenderArgs {
   float* noise_fine_out = nullptr;
   // crnerf_render_rays_f32x3_repair: only ray quads whose feature_coarse / feature_fine hold a NaN are rendered (again)
   int repair = 0;
-  // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT (rendered by another core); sample_pdf + merge + the fine pass only
-  int fine_only = 0;
-  // crnerf_render_rays_lean_f32 (render_fused16.hip), crnerf_render_rays_lean_bf16 / _f16 (render_fused_bf16p.hip; include/crnerf_lean.h): trunk-only
-  // coarse pass; writes feature_fine, depth_fine and (optional) z_fine only.  The other launchers do not look at it.
-  int lean = 0;
-  // crnerf_render_coarse_weights_* (include/crnerf_lean.h; render_fused_x3.hip both builds, the fp16 pair core): Ni == 0, every tile walks the trunk,
-  // weights_coarse is the only output and carries the range mark (0x7fc00000 in [r][0]); with `repair` the x3 launcher looks for that mark.
-  // lean + fine_only (crnerf_render_rays_lean_bf16_fine): the fine-only kernel without weights_fine.
-  int coarse_weights = 0;
+  // which render this is (RenderMode above); `repair` combines with Full and CoarseWeights
+  RenderMode mode = RenderMode::Full;
   // training twin (crnerf_render_rays_train_f32; all null for inference): saved activations + raw MLP outputs per pass
   void* train_acts_coarse = nullptr;   // crnerf_mlp_train_acts_bytes(R*Nc)
   void* train_acts_fine = nullptr;     // crnerf_mlp_train_acts_bytes(R*(Nc+Ni))

@@ -268,7 +268,7 @@ int launch_render_rays16(const RenderArgs& a, hipStream_t stream) {
   k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)crnerf_sched16) : nullptr;
   const size_t shmem = LDS_SCRATCH + 4 * PAIR_BYTES + V16_WAVES * 32 * sizeof(float) + 16;
-  if (a.lean) {   // crnerf_render_rays_lean_f32: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
+  if (a.mode == RenderMode::Lean) {   // crnerf_render_rays_lean_f32: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
     if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
     if (a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
     return launch_kernel(render_rays16_lean_kernel, "render_rays16_lean_kernel", plan.grid, 512, shmem, stream, k);

@@ -390,10 +390,11 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   RenderParamsP k;
   fill_render_params(k, a);
   k.wc_in = nullptr;
+  const bool fine_only = a.mode == RenderMode::FineOnly || a.mode == RenderMode::LeanFineOnly;
 #if CRNERF_P_F16
-  if (a.fine_only || a.train_acts_coarse) return set_error(-3, CRNERF_P_RENDER_WHAT ": the fp16 build has the inference kernel only");
+  if (fine_only || a.train_acts_coarse) return set_error(-3, CRNERF_P_RENDER_WHAT ": the fp16 build has the inference kernel only");
 #else
-  if (a.fine_only) {   // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT, the fine model runs alone
+  if (fine_only) {   // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT, the fine model runs alone
     if (a.Ni <= 0 || !a.packed_fine || !a.weights_coarse) return set_error(-3, "render_rays_bf16_fine: needs N_importance > 0, the fine model and weights_coarse");
     if (a.train_acts_coarse) return set_error(-3, "render_rays_bf16_fine: no training twin");
     k.packed0 = k.packed1 = (const char*)a.packed_fine;
@@ -404,26 +405,27 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
   const GridPlan plan = plan_grid((a.R + 3) / 4);   // one workgroup per CU, persistent over ray quads
   k.iters = plan.iters;
   k.sched = k.iters > 1 ? sched_slot((const void*)CRNERF_P_RENDER_SCHED) : nullptr;
+  switch (a.mode) {
 #if CRNERF_P_F16
-  if (a.coarse_weights) {   // crnerf_render_coarse_weights_f16: the lean coarse pass alone; weights_coarse is the only output
-    if (a.Ni != 0) return set_error(-2, "render_coarse_weights: N_importance must be 0");
-    if (a.fine_only || a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_coarse_weights: inference only, random draws come as tensors");
-    k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;
-    return launch_kernel(render_coarse_weights_f16p_kernel, "render_coarse_weights_f16p_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
-  }
+    case RenderMode::CoarseWeights:   // crnerf_render_coarse_weights_f16: the lean coarse pass alone; weights_coarse is the only output
+      if (a.Ni != 0) return set_error(-2, "render_coarse_weights: N_importance must be 0");
+      if (a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_coarse_weights: inference only, random draws come as tensors");
+      k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;
+      return launch_kernel(render_coarse_weights_f16p_kernel, "render_coarse_weights_f16p_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
 #else
-  if (a.coarse_weights) return set_error(-3, CRNERF_P_RENDER_WHAT ": the coarse-weights render of the pair core exists in the fp16 build only");
-  if (a.lean && a.fine_only) {   // crnerf_render_rays_lean_bf16_fine: weights_fine is never written (abi.hip passes it as null)
-    if (a.train_acts_coarse) return set_error(-3, "render_rays_lean_bf16_fine: no training twin");
-    k.weights_f = nullptr;
-    return launch_kernel(render_rays_bf16p_lean_fine_kernel, "render_rays_bf16p_lean_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
-  }
+    case RenderMode::CoarseWeights:
+      return set_error(-3, CRNERF_P_RENDER_WHAT ": the coarse-weights render of the pair core exists in the fp16 build only");
+    case RenderMode::LeanFineOnly:   // crnerf_render_rays_lean_bf16_fine: weights_fine is never written (abi.hip passes it as null)
+      if (a.train_acts_coarse) return set_error(-3, "render_rays_lean_bf16_fine: no training twin");
+      k.weights_f = nullptr;
+      return launch_kernel(render_rays_bf16p_lean_fine_kernel, "render_rays_bf16p_lean_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
 #endif
-  if (a.lean) {   // crnerf_render_rays_lean_bf16 / _f16: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
-    if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
-    if (a.fine_only || a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
-    k.weights_c = k.feature_c = k.depth_c = k.weights_f = nullptr;
-    return launch_kernel(CRNERF_P_RENDER_LEAN_KERNEL, CRNERF_P_RENDER_LEAN_NAME, plan.grid, 512, LDS_TOTAL_P, stream, k);
+    case RenderMode::Lean:   // crnerf_render_rays_lean_bf16 / _f16: the coarse outputs and weights_fine are never written (abi.hip passes them as null)
+      if (a.Ni < 1) return set_error(-2, "render_rays_lean: N_importance must be in [1, 256] (the coarse pass alone has nothing lean to return)");
+      if (a.train_acts_coarse || a.rng_flags || a.z_coarse_out) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
+      k.weights_c = k.feature_c = k.depth_c = k.weights_f = nullptr;
+      return launch_kernel(CRNERF_P_RENDER_LEAN_KERNEL, CRNERF_P_RENDER_LEAN_NAME, plan.grid, 512, LDS_TOTAL_P, stream, k);
+    default: break;   // Full, and FineOnly in the bf16 build
   }
 #if !CRNERF_P_F16
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_bf16)
@@ -433,7 +435,7 @@ int CRNERF_P_RENDER_LAUNCH(const RenderArgs& a, hipStream_t stream) {
     const TrainHookP h{{(char*)a.train_acts_coarse, (char*)a.train_acts_fine}, {a.train_raw_coarse, a.train_raw_fine}, a.R};
     return launch_kernel(render_rays_train_bf16p_kernel, "render_rays_train_bf16p_kernel", plan.grid, 512, LDS_TOTAL_TRAIN_P, stream, k, h);
   }
-  if (a.fine_only) return launch_kernel(render_rays_bf16p_fine_kernel, "render_rays_bf16p_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
+  if (fine_only) return launch_kernel(render_rays_bf16p_fine_kernel, "render_rays_bf16p_fine_kernel", plan.grid, 512, LDS_TOTAL_P, stream, k);
 #endif
   return launch_kernel(CRNERF_P_RENDER_KERNEL, CRNERF_P_RENDER_NAME, plan.grid, 512, LDS_TOTAL_P, stream, k);
 }

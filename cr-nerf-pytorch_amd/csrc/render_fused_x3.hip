@@ -288,7 +288,7 @@ int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
   const GridPlan plan = plan_grid(quads, a.repair);   // one workgroup per CU, persistent over ray quads (repair: one per quad)
   k.iters = plan.iters;
   const size_t shmem = LDS_SCRATCH_X + 4 * SCRATCH_BYTES;
-  if (a.coarse_weights) {   // crnerf_render_coarse_weights_f32x3 / _f32h2 / _f32x3_repair: weights_coarse only (abi.hip passes the other outputs as null)
+  if (a.mode == RenderMode::CoarseWeights) {   // crnerf_render_coarse_weights_f32x3 / _f32h2 / _f32x3_repair: weights_coarse only (abi.hip passes the other outputs as null)
     if (a.Ni != 0) return set_error(-2, "render_coarse_weights: N_importance must be 0");
     if (rngk || a.train_acts_coarse) return set_error(-3, "render_coarse_weights: inference only, random draws come as tensors");
     k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;

@@ -78,7 +78,10 @@ def _render_unfused(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u,
     return out
 
 
-def _render_bf16_accurate_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, chunk, want_z_fine=False, lean=False):
+_warned_f16_refused = [False]
+
+
+def _render_bf16_composite(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, want_z_fine=False, lean=False, f16_coarse=False):
     """precision="bf16_hc" (inference, perturb = 0): the COARSE pass in fp32 accuracy on the fp16 matrix cores (precision "auto": f32h2 with the
     f32x3 safety net; 25 % of the points), the FINE pass on the bf16 matrix cores.  Why: bf16's end-to-end pixel error on a trained checkpoint is
     sampling sensitivity -- bf16 coarse weights move the fine depths (weights_fine rel-L2 2.8e-2, tests/test_gpu_trained_ckpt.py) -- so with
@@ -86,52 +89,40 @@ def _render_bf16_accurate_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir,
     Two fused launches (+ the repair kernel that leaves at once): the coarse-only render on the h2 core, then crnerf_render_rays_bf16_fine --
     sample_pdf, merge, embedding, fine MLP and compositing in one kernel on the coarse weights (round 6; rounds 4-5 ran five un-fused calls with
     the [P,120] embeddings and [P,65] raw rows through HBM: 297 ms per 800 x 800 frame).
-    lean: the caller reads the fine image alone.  The coarse launch becomes ops.render_coarse_weights (crnerf_render_coarse_weights_f32h2 + its x3
-    repair: every tile stops behind the sigma head, weights_coarse is all it writes, bit-identical to the ordinary launch's) and the fine launch
+    f16_coarse: precision="bf16_fc", the same with the coarse pass on ONE-PIECE FP16 operands -- one MFMA per product like bf16 instead of the h2
+    core's three, 11 significand bits instead of bf16's 8: the coarse weights, and with them the fine depths, land ~7x closer to fp32's than bf16's
+    do (tests/test_gpu_f16_trained.py) at bf16's cost.  Three launches: the coarse-only crnerf_render_rays_f16, crnerf_render_rays_f32x3_repair over
+    its outputs (re-renders the ray quads the fp16 range guard poisoned; leaves at once otherwise -- so the mode returns no NaN that "f32" would
+    not), crnerf_render_rays_bf16_fine on those coarse weights.  A coarse model whose weights do not fit fp16 (the pack refuses them) takes
+    bf16_hc's coarse pass instead; said once in a warning.
+    lean: the caller reads the fine image alone.  The coarse launch becomes ops.render_coarse_weights (crnerf_render_coarse_weights_f32h2 / _f16 + the
+    x3 repair: every tile stops behind the sigma head, weights_coarse is all it writes, bit-identical to the ordinary launch's) and the fine launch
     crnerf_render_rays_lean_bf16_fine (no weights_fine); the dict holds feature_fine, depth_fine and (want_z_fine) z_fine."""
+    # how the coarse pass is obtained: its precision, its pack and (f16) the x3 pack of the repair behind it
+    precision, pk, repair = "auto", None, None
+    if f16_coarse:
+        try:
+            precision, pk = "f16", coarse.packed_weights("f16")
+        except ops.PackRangeError:
+            if not _warned_f16_refused[0]:
+                _warned_f16_refused[0] = True
+                import warnings
+                warnings.warn("crnerf_amd: precision='bf16_fc': a weight of the coarse model does not fit fp16 (|w| <= 65,504, finite); "
+                              "its coarse pass runs as in 'bf16_hc'")
     z_steps, u_steps = _linspace_tables(Nc, Ni, rays.device)
+    if pk is None:
+        pk = coarse.packed_weights("auto")
+    else:
+        repair = coarse.packed_weights("f32x3")
+    kw = dict(use_disp=use_disp, z_steps=z_steps, noise_coarse=noise_c, noise_std=float(noise_std), precision=precision)
     if lean:
-        wc = ops.render_coarse_weights(coarse.packed_weights("auto"), rays, Nc, precision="auto", use_disp=use_disp, z_steps=z_steps,
-                                       noise_coarse=noise_c, noise_std=float(noise_std))["weights_coarse"]
-        return ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, wc, Nc, Ni, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, u=u_steps,
-                                         noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine, lean=True)
-    out = ops.render_rays(coarse.packed_weights("auto"), None, rays, Nc, 0, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps,
-                          noise_coarse=noise_c, noise_std=float(noise_std), precision="auto")
-    out.update(ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, out["weights_coarse"], Nc, Ni, use_disp=use_disp, view_dir=view_dir,
-                                         z_steps=z_steps, u=u_steps, noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine))
-    return out
-
-
-_warned_f16_refused = [False]
-
-
-def _render_bf16_f16_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, chunk, want_z_fine=False, lean=False):
-    """precision="bf16_fc" (inference, perturb = 0): _render_bf16_accurate_coarse with the coarse pass on ONE-PIECE FP16 operands -- one MFMA per product
-    like bf16 instead of the h2 core's three, 11 significand bits instead of bf16's 8: the coarse weights, and with them the fine depths, land
-    ~7x closer to fp32's than bf16's do (tests/test_gpu_f16_trained.py) at bf16's cost.  Three launches: the coarse-only crnerf_render_rays_f16,
-    crnerf_render_rays_f32x3_repair over its outputs (re-renders the ray quads the fp16 range guard poisoned; leaves at once otherwise -- so the
-    mode returns no NaN that "f32" would not), crnerf_render_rays_bf16_fine on those coarse weights.  A coarse model whose weights do not fit
-    fp16 (the pack refuses them) takes bf16_hc's coarse pass instead; said once in a warning.
-    lean: as in _render_bf16_accurate_coarse, with crnerf_render_coarse_weights_f16 and the same x3 repair behind it."""
-    try:
-        pk = coarse.packed_weights("f16")
-    except ops.PackRangeError:
-        if not _warned_f16_refused[0]:
-            _warned_f16_refused[0] = True
-            import warnings
-            warnings.warn("crnerf_amd: precision='bf16_fc': a weight of the coarse model does not fit fp16 (|w| <= 65,504, finite); "
-                          "its coarse pass runs as in 'bf16_hc'")
-        return _render_bf16_accurate_coarse(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, chunk, want_z_fine, lean)
-    z_steps, u_steps = _linspace_tables(Nc, Ni, rays.device)
-    if lean:
-        wc = ops.render_coarse_weights(pk, rays, Nc, precision="f16", use_disp=use_disp, z_steps=z_steps, noise_coarse=noise_c, noise_std=float(noise_std),
-                                       repair_x3=coarse.packed_weights("f32x3"))["weights_coarse"]
-        return ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, wc, Nc, Ni, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, u=u_steps,
-                                         noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine, lean=True)
-    out = ops.render_rays(pk, None, rays, Nc, 0, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, noise_coarse=noise_c, noise_std=float(noise_std),
-                          precision="f16", repair_x3=(coarse.packed_weights("f32x3"), None))
-    out.update(ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, out["weights_coarse"], Nc, Ni, use_disp=use_disp, view_dir=view_dir,
-                                         z_steps=z_steps, u=u_steps, noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine))
+        out = {}
+        wc = ops.render_coarse_weights(pk, rays, Nc, repair_x3=repair, **kw)["weights_coarse"]
+    else:     # (view_dir: the full launch also composites feature_coarse)
+        out = ops.render_rays(pk, None, rays, Nc, 0, view_dir=view_dir, repair_x3=None if repair is None else (repair, None), **kw)
+        wc = out["weights_coarse"]
+    out.update(ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, wc, Nc, Ni, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, u=u_steps,
+                                         noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine, lean=lean))
     return out
 
 
@@ -220,11 +211,10 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         out = fused_render_with_grad(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
                                      float(noise_std), rng=rng)
     elif bf16_hc and N_importance > 0 and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
-        out = _render_bf16_accurate_coarse(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), int(chunk),
-                                           lean=lean)
+        out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), lean=lean)
     elif bf16_fc and 0 < N_importance <= _FUSED_MAX and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
-        out = _render_bf16_f16_coarse(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), int(chunk),
-                                      lean=lean)
+        out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), lean=lean,
+                                     f16_coarse=True)
     elif train or N_samples > _FUSED_MAX or N_importance > _FUSED_MAX or jitter:
         # general path: the same HIP kernels, un-fused (posenc -> MLP -> compositing -> sample_pdf/merge), for
         # sample counts beyond the fused kernel's LDS scratch and for args.pertubeCord (rendering.py:102-104)

@@ -125,20 +125,24 @@ class F16Pack:
 
 
 # One record per arithmetic a kernel family exists for (precision.CORES): the library's entry points BY NAME (looked up on the loaded library, so
-# importing this module does not load it) and `tag`, the type a pack of that core has where its byte size cannot tell it from another's.
-_Core = collections.namedtuple("_Core", "bytes pack forward render render_train tag")
+# importing this module does not load it), `tag`, the type a pack of that core has where its byte size cannot tell it from another's, and the entries
+# of the lean render (crnerf.h; crnerf_lean.h for the pair core's two builds) and of the coarse-weights render (crnerf_lean_composite.h): None where
+# the core has none.
+_Core = collections.namedtuple("_Core", "bytes pack forward render render_train tag render_lean coarse_weights")
 _CORES = {
-    "f32": _Core("crnerf_packed_mlp_bytes", "crnerf_pack_mlp_weights", "crnerf_mlp_forward_f32", "crnerf_render_rays_f32", "crnerf_render_rays_train_f32", None),
+    "f32": _Core("crnerf_packed_mlp_bytes", "crnerf_pack_mlp_weights", "crnerf_mlp_forward_f32", "crnerf_render_rays_f32", "crnerf_render_rays_train_f32", None,
+                 "crnerf_render_rays_lean_f32", None),
     "bf16": _Core("crnerf_packed_mlp_bf16_bytes", "crnerf_pack_mlp_weights_bf16", "crnerf_mlp_forward_bf16", "crnerf_render_rays_bf16",
-                  "crnerf_render_rays_train_bf16", None),
+                  "crnerf_render_rays_train_bf16", None, "crnerf_render_rays_lean_bf16", None),
     # one-piece fp16 operands: a point whose operands leave fp16's range comes out as NaN; inference only
-    "f16": _Core("crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16", None, F16Pack),
+    "f16": _Core("crnerf_packed_mlp_f16_bytes", "crnerf_pack_mlp_weights_f16", "crnerf_mlp_forward_f16", "crnerf_render_rays_f16", None, F16Pack,
+                 "crnerf_render_rays_lean_f16", "crnerf_render_coarse_weights_f16"),
     # fp32 on the bf16 matrix cores: every weight as three bf16 pieces, k-step-major fragment stream; six MFMAs per product
     "f32x3": _Core("crnerf_packed_mlp_x3_bytes", "crnerf_pack_mlp_weights_x3", "crnerf_mlp_forward_f32x3", "crnerf_render_rays_f32x3",
-                   "crnerf_render_rays_train_f32x3", None),
+                   "crnerf_render_rays_train_f32x3", None, None, "crnerf_render_coarse_weights_f32x3"),
     # fp32 on the fp16 matrix cores: every weight, scaled by 2^8, as two fp16 pieces; three MFMAs per product
     "f32h2": _Core("crnerf_packed_mlp_h2_bytes", "crnerf_pack_mlp_weights_h2", "crnerf_mlp_forward_f32h2", "crnerf_render_rays_f32h2",
-                   "crnerf_render_rays_train_f32h2", None),
+                   "crnerf_render_rays_train_f32h2", None, None, "crnerf_render_coarse_weights_f32h2"),
 }
 
 
@@ -479,8 +483,54 @@ def _render_args(rays, inputs, noise_std, use_disp, Nc, Ni, out):
     return a, keep
 
 
-# the lean entry point of a precision (crnerf.h; crnerf_lean.h for the pair core's two builds)
-_LEAN_RENDER = {"f32": "crnerf_render_rays_lean_f32", "bf16": "crnerf_render_rays_lean_bf16", "f16": "crnerf_render_rays_lean_f16"}
+def _resolve_packs(name, packs, repair, what="packs"):
+    """(core name, packs, x3 packs of the repair launch or None) of a render under precision `name`; `packs`: a tuple, None where a model is absent.
+    "auto" (AutoPacks): the h2 core with the x3 core as its safety net -- render on h2, then the *_f32x3_repair entry re-renders the ray quads that came
+    out NaN (a point's activations left fp16's range).  A refused h2 pack (a weight >= 255): the x3 core throughout."""
+    if name != "auto":
+        return name, packs, repair
+    if not isinstance(packs[0], AutoPack) or any(pk is not None and not isinstance(pk, AutoPack) for pk in packs):
+        raise ValueError("crnerf_amd: precision='auto' needs %s from pack_mlp_weights(..., precision='auto')" % what)
+    x3 = tuple(pk.x3 if pk is not None else None for pk in packs)
+    if any(pk is not None and pk.h2 is None for pk in packs):
+        return "f32x3", x3, None
+    return "f32h2", tuple(pk.h2 if pk is not None else None for pk in packs), x3
+
+
+def _render(lib, entry, repair_entry, checks, packs, repair, rays, shapes, inputs, noise_std, use_disp, Nc, Ni, extras=None, launcher=False):
+    """What every render function does behind its own mode rules: check the packs (`checks`: (core name, pack) pairs) and rays, allocate the output dict
+    from `shapes` ((key, shape behind R) pairs), fill the argument block, call `entry` and, with `repair` (x3 packs), `repair_entry` on the same block
+    with those packs.  extras(a, out, R, device): the caller's additions to the block and to `out`; returns the arguments of the entry between the block and the
+    stream.  launcher=True: (launch, out) -- measurement helper: re-launch the same call on the same buffers with nothing but the C calls on the host."""
+    for core_name, pk in checks:
+        _check_pack(lib, core_name, pk)
+    rays = _f32c(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be [R,8], got %s" % (tuple(rays.shape),))
+    R, dev = rays.shape[0], rays.device
+    out = {k: torch.empty(R, *shape, dtype=torch.float32, device=dev) for k, shape in shapes}      # (sizes as arguments: a tuple parses slower)
+    if R == 0:
+        return out
+    a, keep = _render_args(rays, inputs, noise_std, use_disp, Nc, Ni, out)
+    if packs[0] is not None:
+        a.packed_coarse = packs[0].data_ptr()
+    if packs[1] is not None:
+        a.packed_fine = packs[1].data_ptr()
+    tail = extras(a, out, R, dev) if extras is not None else ()
+    fn, a2 = getattr(lib, entry), _repair_args(a, repair)
+    fn2 = getattr(lib, repair_entry) if a2 is not None else None
+    # the argument structs hold raw pointers: a launcher that outlives this call keeps EVERY tensor behind them alive (the outputs too: a caller that
+    # drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
+    held = (keep, rays, packs, out, repair)
+
+    def launch(_held=held):
+        _lib.check(fn(ctypes.byref(a), *tail, _lib.stream_ptr()), entry)
+        if a2 is not None:        # the ray quads the fp16 range guard poisoned, once more on the scale-free core (a training twin: outputs AND saved state)
+            _lib.check(fn2(ctypes.byref(a2), *tail, _lib.stream_ptr()), repair_entry)
+    if launcher:
+        return launch, out
+    launch()
+    return out
 
 
 def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
@@ -510,7 +560,7 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
     if lean:
         if train or rng is not None:
             raise ValueError("crnerf_amd: lean=True is an inference render (no training twin, no in-kernel draws: hand them over as tensors)")
-        if name not in _LEAN_RENDER:
+        if name == "auto" or _CORES[name].render_lean is None:
             raise ValueError("crnerf_amd: lean=True exists for precision='f32', 'bf16' and 'f16' (the trunk-only coarse walk is built on the fp32 core "
                              "and on the pair core), got %r" % (name,))
         if int(n_importance) <= 0:
@@ -526,89 +576,53 @@ def render_rays(packed_coarse, packed_fine, rays, n_samples, n_importance, use_d
         raise ValueError("crnerf_amd: precision='f16' is an inference mode (no training twin, no in-kernel draws)")
     if launcher and train:
         raise ValueError("crnerf_amd: launcher=True is for the inference entry points")
-    if name == "auto":
-        # the h2 core with the x3 core as its safety net: render on h2, then crnerf_render_rays_f32x3_repair re-renders the ray quads that came out NaN
-        # (a point's activations left fp16's range).  A refused h2 pack (a weight >= 255): the x3 core throughout.
-        packs = [pk for pk in (packed_coarse, packed_fine) if pk is not None]
-        if any(not isinstance(pk, AutoPack) for pk in packs):
-            raise ValueError("crnerf_amd: precision='auto' needs packs from pack_mlp_weights(..., precision='auto')")
-        if any(pk.h2 is None for pk in packs):
-            name = "f32x3"
-            packed_coarse, packed_fine = packed_coarse.x3, (packed_fine.x3 if packed_fine is not None else None)
-        else:
-            name = "f32h2"
-            repair = (packed_coarse.x3, packed_fine.x3 if packed_fine is not None else None)
-            packed_coarse, packed_fine = packed_coarse.h2, (packed_fine.h2 if packed_fine is not None else None)
+    name, packs, repair = _resolve_packs(name, (packed_coarse, packed_fine), repair)
     core = _CORES[name]
-    want_z_fine = want_z_fine or train
-    _check_pack(lib, name, packed_coarse)
-    _check_pack(lib, name, packed_fine)
-    rays = _f32c(rays, "rays")
-    if rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError("rays must be [R,8], got %s" % (tuple(rays.shape),))
-    R, dev = rays.shape[0], rays.device
     Nc, Ni = int(n_samples), int(n_importance)
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
     if lean:
-        out = {"feature_fine": new(R, 64), "depth_fine": new(R)}
+        shapes = [("feature_fine", (64,)), ("depth_fine", ())]
+    elif Ni > 0:
+        shapes = [("weights_coarse", (Nc,)), ("feature_coarse", (64,)), ("depth_coarse", ()), ("weights_fine", (Nc + Ni,)), ("feature_fine", (64,)), ("depth_fine", ())]
     else:
-        out = {"weights_coarse": new(R, Nc), "feature_coarse": new(R, 64), "depth_coarse": new(R)}
-        if Ni > 0:
-            out.update({"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)})
-    if Ni > 0 and want_z_fine:
-        out["z_fine"] = new(R, Nc + Ni)
-    if R == 0:
-        return out
-    a, keep = _render_args(rays, {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_coarse": noise_coarse,
-                                  "noise_fine": noise_fine}, noise_std, use_disp, Nc, Ni, out)
-    a.packed_coarse = packed_coarse.data_ptr()
-    a.packed_fine = packed_fine.data_ptr() if packed_fine is not None else None
-    if rng is not None:
-        if name == "bf16":
-            raise ValueError("crnerf_amd: in-kernel random draws exist in the fp32 kernels only")
-        flags = (_lib.RNG_JITTER if rng.get("jitter") else 0) | (_lib.RNG_U if (rng.get("u") and Ni > 0) else 0) | (_lib.RNG_NOISE if rng.get("noise") else 0)
-        a.rng_seed, a.rng_ray_offset, a.rng_flags, a.perturb = int(rng["seed"]) & (2 ** 64 - 1), int(rng.get("ray_offset", 0)), flags, float(rng.get("perturb", 1.0))
-        out["z_coarse_used"] = new(R, Nc)
-        a.z_coarse_out = out["z_coarse_used"].data_ptr()
-        if flags & _lib.RNG_NOISE:
-            out["noise_coarse_used"] = new(R, Nc)
-            a.noise_coarse_out = out["noise_coarse_used"].data_ptr()
+        shapes = [("weights_coarse", (Nc,)), ("feature_coarse", (64,)), ("depth_coarse", ())]
+    if Ni > 0 and (want_z_fine or train):
+        shapes.append(("z_fine", (Nc + Ni,)))
+
+    extras = None
+    if train or rng is not None:       # (inference pays for no closure)
+        def extras(a, out, R, dev):
+            """The in-kernel draws and what they write; train: what the backward needs -- the saved state, handed to the twin behind the block."""
+            new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+            if rng is not None:
+                if name == "bf16":
+                    raise ValueError("crnerf_amd: in-kernel random draws exist in the fp32 kernels only")
+                flags = (_lib.RNG_JITTER if rng.get("jitter") else 0) | (_lib.RNG_U if (rng.get("u") and Ni > 0) else 0) | (_lib.RNG_NOISE if rng.get("noise") else 0)
+                a.rng_seed, a.rng_ray_offset, a.rng_flags, a.perturb = int(rng["seed"]) & (2 ** 64 - 1), int(rng.get("ray_offset", 0)), flags, float(rng.get("perturb", 1.0))
+                out["z_coarse_used"] = new(R, Nc)
+                a.z_coarse_out = out["z_coarse_used"].data_ptr()
+                if flags & _lib.RNG_NOISE:
+                    out["noise_coarse_used"] = new(R, Nc)
+                    a.noise_coarse_out = out["noise_coarse_used"].data_ptr()
+                    if Ni > 0:
+                        out["noise_fine_used"] = new(R, Nc + Ni)
+                        a.noise_fine_out = out["noise_fine_used"].data_ptr()
+            if not train:
+                return ()
+            Nf = Nc + Ni
+            acts_bytes = lib.crnerf_mlp_train_mixed_acts_bytes if name == "bf16" else lib.crnerf_mlp_train_acts_bytes
+            out["acts_coarse"] = torch.empty(acts_bytes(R * Nc), dtype=torch.uint8, device=dev)
+            out["raw_coarse"] = new(R, Nc, 65)
             if Ni > 0:
-                out["noise_fine_used"] = new(R, Nc + Ni)
-                a.noise_fine_out = out["noise_fine_used"].data_ptr()
-    if train:
-        Nf = Nc + Ni
-        acts_bytes = lib.crnerf_mlp_train_mixed_acts_bytes if name == "bf16" else lib.crnerf_mlp_train_acts_bytes
-        out["acts_coarse"] = torch.empty(acts_bytes(R * Nc), dtype=torch.uint8, device=dev)
-        out["raw_coarse"] = new(R, Nc, 65)
-        if Ni > 0:
-            out["acts_fine"] = torch.empty(acts_bytes(R * Nf), dtype=torch.uint8, device=dev)
-            out["raw_fine"] = new(R, Nf, 65)
-        vp = lambda k: ctypes.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
-        saved = (vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine"))
-        _lib.check(getattr(lib, core.render_train)(ctypes.byref(a), *saved, _lib.stream_ptr()), core.render_train)
-        a2 = _repair_args(a, repair)
-        if a2 is not None:        # precision="auto": the ray quads the h2 twin poisoned, once more on the scale-free core -- outputs AND saved state
-            _lib.check(lib.crnerf_render_rays_train_f32x3_repair(ctypes.byref(a2), *saved, _lib.stream_ptr()), "crnerf_render_rays_train_f32x3_repair")
-        return out
-    fn_name = _LEAN_RENDER[name] if lean else core.render
-    fn, a2 = getattr(lib, fn_name), _repair_args(a, repair)
-    # the argument structs hold raw pointers: a launcher that outlives this call keeps EVERY tensor behind them alive (the outputs too: a caller that
-    # drops `out` must not hand their memory back to the caching allocator while launch() can still write it)
-    held = (keep, rays, packed_coarse, packed_fine, out, repair)
+                out["acts_fine"] = torch.empty(acts_bytes(R * Nf), dtype=torch.uint8, device=dev)
+                out["raw_fine"] = new(R, Nf, 65)
+            vp = lambda k: ctypes.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
+            return vp("acts_coarse"), vp("acts_fine"), vp("raw_coarse"), vp("raw_fine")
 
-    def launch(_held=held):
-        _lib.check(fn(ctypes.byref(a), _lib.stream_ptr()), fn_name)
-        if a2 is not None:        # "auto" / repair_x3=: the ray quads the fp16 range guard poisoned, once more on the scale-free core
-            _lib.check(lib.crnerf_render_rays_f32x3_repair(ctypes.byref(a2), _lib.stream_ptr()), "crnerf_render_rays_f32x3_repair")
-    if launcher:      # measurement helper: re-launch the same call on the same buffers with nothing but the C call on the host side
-        return launch, out
-    launch()
-    return out
-
-
-# the coarse-weights entry of a precision (include/crnerf_lean_composite.h)
-_COARSE_WEIGHTS = {"f32h2": "crnerf_render_coarse_weights_f32h2", "f32x3": "crnerf_render_coarse_weights_f32x3", "f16": "crnerf_render_coarse_weights_f16"}
+    entry, repair_entry = ((core.render_train, "crnerf_render_rays_train_f32x3_repair") if train else
+                           (core.render_lean if lean else core.render, "crnerf_render_rays_f32x3_repair"))
+    return _render(lib, entry, repair_entry, ((name, packs[0]), (name, packs[1])), packs, repair, rays, shapes,
+                   {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_coarse": noise_coarse, "noise_fine": noise_fine},
+                   noise_std, use_disp, Nc, Ni, extras, launcher)
 
 
 def render_coarse_weights(packed_coarse, rays, n_samples, precision="auto", use_disp=False, z_coarse=None, z_steps=None, noise_coarse=None, noise_std=0.0,
@@ -621,36 +635,16 @@ def render_coarse_weights(packed_coarse, rays, n_samples, precision="auto", use_
     quads again on the x3 core and leaves at once when there is none; a refused h2 pack: the x3 entry throughout.  "f16" with repair_x3=(the coarse
     model's x3 pack): the same repair behind the fp16 entry."""
     name = resolve(precision)
-    if name not in _COARSE_WEIGHTS and name != "auto":
+    if name != "auto" and _CORES[name].coarse_weights is None:
         raise ValueError("crnerf_amd: render_coarse_weights exists for precision='f32h2', 'f32x3', 'auto' and 'f16', got %r" % (name,))
     if repair_x3 is not None and name != "f16":
         raise ValueError("crnerf_amd: repair_x3= goes with precision='f16' (precision='auto' brings its own x3 pack)")
     lib = _lib.load()
-    repair = repair_x3
-    if name == "auto":
-        if not isinstance(packed_coarse, AutoPack):
-            raise ValueError("crnerf_amd: precision='auto' needs a pack from pack_mlp_weights(..., precision='auto')")
-        if packed_coarse.h2 is None:
-            name, packed_coarse = "f32x3", packed_coarse.x3
-        else:
-            name, repair, packed_coarse = "f32h2", packed_coarse.x3, packed_coarse.h2
-    _check_pack(lib, name, packed_coarse)
-    _check_pack(lib, "f32x3", repair)
-    rays = _f32c(rays, "rays")
-    if rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError("rays must be [R,8], got %s" % (tuple(rays.shape),))
-    R, Nc = rays.shape[0], int(n_samples)
-    out = {"weights_coarse": torch.empty(R, Nc, dtype=torch.float32, device=rays.device)}
-    if R == 0:
-        return out
-    a, keep = _render_args(rays, {"view_dir": None, "z_coarse": z_coarse, "z_steps": z_steps, "u": None, "noise_coarse": noise_coarse, "noise_fine": None},
-                           noise_std, use_disp, Nc, 0, out)
-    a.packed_coarse = packed_coarse.data_ptr()
-    _lib.check(getattr(lib, _COARSE_WEIGHTS[name])(ctypes.byref(a), _lib.stream_ptr()), _COARSE_WEIGHTS[name])
-    if repair is not None:
-        a.packed_coarse = repair.data_ptr()
-        _lib.check(lib.crnerf_render_coarse_weights_f32x3_repair(ctypes.byref(a), _lib.stream_ptr()), "crnerf_render_coarse_weights_f32x3_repair")
-    return out
+    name, packs, repair = _resolve_packs(name, (packed_coarse, None), None if repair_x3 is None else (repair_x3, None), what="a pack")
+    return _render(lib, _CORES[name].coarse_weights, "crnerf_render_coarse_weights_f32x3_repair", [(name, packs[0]), ("f32x3", repair[0] if repair else None)],
+                   packs, repair, rays, [("weights_coarse", (int(n_samples),))],
+                   {"view_dir": None, "z_coarse": z_coarse, "z_steps": z_steps, "u": None, "noise_coarse": noise_coarse, "noise_fine": None},
+                   noise_std, use_disp, int(n_samples), 0)
 
 
 def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
@@ -662,24 +656,15 @@ def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_i
     lib = _lib.load()
     _check_pack(lib, "bf16", packed_fine_bf16)
     rays, weights_coarse = _f32c(rays, "rays"), _f32c(weights_coarse, "weights_coarse")
-    R, dev = rays.shape[0], rays.device
     Nc, Ni = int(n_samples), int(n_importance)
-    if rays.dim() != 2 or rays.shape[1] != 8 or tuple(weights_coarse.shape) != (R, Nc) or Ni <= 0:
+    if rays.dim() != 2 or rays.shape[1] != 8 or tuple(weights_coarse.shape) != (rays.shape[0], Nc) or Ni <= 0:
         raise ValueError("render_rays_bf16_fine: rays [R,8], weights_coarse [R,%d] and n_importance > 0 expected, got %s / %s / %d"
                          % (Nc, tuple(rays.shape), tuple(weights_coarse.shape), Ni))
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    out = {"feature_fine": new(R, 64), "depth_fine": new(R)} if lean else {"weights_fine": new(R, Nc + Ni), "feature_fine": new(R, 64), "depth_fine": new(R)}
-    if want_z_fine:
-        out["z_fine"] = new(R, Nc + Ni)
-    if R == 0:
-        return out
-    a, keep = _render_args(rays, {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_fine": noise_fine}, noise_std, use_disp,
-                           Nc, Ni, out)
-    a.packed_fine = packed_fine_bf16.data_ptr()
-    a.weights_coarse = weights_coarse.data_ptr()                    # INPUT of this entry point
-    fn_name = "crnerf_render_rays_lean_bf16_fine" if lean else "crnerf_render_rays_bf16_fine"
-    _lib.check(getattr(lib, fn_name)(ctypes.byref(a), _lib.stream_ptr()), fn_name)
-    return out
+    shapes = ([] if lean else [("weights_fine", (Nc + Ni,))]) + [("feature_fine", (64,)), ("depth_fine", ())] + ([("z_fine", (Nc + Ni,))] if want_z_fine else [])
+    # weights_coarse is an INPUT of this entry point
+    return _render(lib, "crnerf_render_rays_lean_bf16_fine" if lean else "crnerf_render_rays_bf16_fine", None, (), (None, packed_fine_bf16), None, rays, shapes,
+                   {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_fine": noise_fine, "weights_coarse": weights_coarse},
+                   noise_std, use_disp, Nc, Ni)
 
 
 def _repair_args(a, repair):

@@ -24,7 +24,7 @@ def test_fixture_holds_every_case_and_none_that_reached_a_launch(table):
     assert sorted(table) == sorted(G.key(e, label) for e, label, _, _ in G.CASES)
     assert len(table) == len(G.CASES)                                   # no two cases share a name
     assert G.fixture_faults(table) == []
-    assert {e for e, _, _, _ in G.CASES} <= set(_lib.SIGNATURES)
+    assert {e for e, _, _, _ in G.CASES} <= set(_lib.ALL_SIGNATURES)
     assert sum(is_noop for _, _, _, is_noop in G.CASES) >= 40 and all(table[G.key(e, label)]["message"] == G.PRIME[1]
                                                                       for e, label, _, is_noop in G.CASES if is_noop)
 

@@ -4,6 +4,10 @@ bit, what the build before launch.h returned -- with every optional field of the
 map and at one that needs the scheduler slot.  That build's outputs are tests/golden/g_render_launch_parent.npz
 (tools/make_render_launch_golden.py, which also owns the cases and their inputs).
 
+The render entries of the companion headers (the lean renders of the pair core, the coarse-weights renders, the lean fine launch) came later; the
+entry layer of csrc/abi.hip above them decides nothing about what is computed either, and they are held the same way to
+tests/golden/g_render_entries_parent.npz, recorded from the build before every render entry became one descriptor.
+
 The large ray count is 4 * CUs + 6, so its hashes hold for the CU count they were recorded on: on another device those cases skip and say so.  The
 small cases never skip."""
 import importlib.util
@@ -56,6 +60,24 @@ def test_render_equals_the_recorded_build(case, inputs, parent):
     res = G.run_render(inputs, case)
     assert res["feature_fine"].shape[0] == G.n_rays(case[2], inputs.cus)
     _same(G.case_name(case), res, parent)
+
+
+@pytest.fixture(scope="module")
+def parent_entries(golden):
+    """The same of tests/golden/g_render_entries_parent.npz: the render entries of the companion headers, from the build before csrc/abi.hip described
+    every render entry by one descriptor."""
+    arrays = golden(os.path.splitext(os.path.basename(G.ENTRIES_GOLDEN))[0])
+    meta = json.loads(str(arrays["meta"]))
+    return arrays, meta["sha256"], meta["cus"]
+
+
+@pytest.mark.parametrize("case", G.ENTRY_CASES, ids=G.case_name)
+def test_companion_entry_equals_the_recorded_build(case, inputs, parent_entries):
+    if case[2] == "large" and inputs.cus != parent_entries[2]:
+        pytest.skip("the fixture's large ray count is 4 * %d CUs + %d, this device has %d CUs" % (parent_entries[2], G.SMALL_R, inputs.cus))
+    res = G.run_entry(inputs, case)
+    assert all(v.shape[0] == G.n_rays(case[2], inputs.cus) for v in res.values())
+    _same(G.case_name(case), res, parent_entries)
 
 
 @pytest.mark.parametrize("case", G.MLP_CASES, ids=G.case_name)

@@ -22,6 +22,9 @@ Checks that no case reaches:
     come first), the lean and fine-only refusals of render_fused16.hip / render_fused_bf16p.hip (abi.hip checks the same conditions under its own
     texts) and the fp16 build's "inference kernel only" (no entry point routes there); the 3.9 M point limit of the two data-gradient launchers
     is not recorded either (launch_mlp_backward may touch the scratch buffer before it gets there);
+  * behind the seven render entries of crnerf_lean.h / crnerf_lean_composite.h: all of launch.h's check_sample_counts and the launchers' own
+    "N_importance must be 0" / "must be in [1, 256]" -- abi.hip's ranges for these entries ([3, 256] and [1, 256]; [2, 256] and 0 for the
+    coarse-weights ones) come first and are no wider; what is reachable is the repair launch's one-workgroup-per-quad limit;
   * the saved-row limit of crnerf_render_rays_train_f32: that launcher has none, the call would go on to a launch;
   * crnerf_stream_create_cu_share's range check and crnerf_cus_per_xcd: they query the device before validating (only the NULL `stream` case is here);
   * crnerf_scene_bounds_f64 "workspace is NULL": scene_bounds_workspace_bytes() is 0 for every size;
@@ -212,7 +215,7 @@ noop(e, "n=0", n=0)
 
 # ---- the fused renderers
 def render_checks(e, pair):
-    """What render_rays_common refuses (the inference entries and, behind their own checks, the training twins)."""
+    """What render_entry refuses under the RENDER_RAYS descriptor (the inference entries and, behind their own checks, the training twins)."""
     bad(e, "args.n_rays", -1)
     nulls(e, "args.packed_coarse", "args.rays", "args.weights_coarse", "args.feature_coarse", "args.depth_coarse", "args.packed_fine", "args.weights_fine",
           "args.feature_fine", "args.depth_fine")
@@ -259,6 +262,40 @@ bad(e, "args.rng_flags", 1, 8)
 for k in ("z_coarse_out", "noise_coarse_out", "noise_fine_out"):
     case(e, k, **{"args." + k: P})
 noop(e, "n_rays=0", **{"args.n_rays": 0})
+
+
+# ---- the render entries of include/crnerf_lean.h and include/crnerf_lean_composite.h, check by check in abi.hip's order
+def companion_checks(e, ni, ns, required):
+    """ni, ns: (refused below, lowest accepted, highest accepted, refused above) of n_importance and n_samples.  A bound's accepting side shows in the
+    NEXT check answering: n_samples behind n_importance, the first required pointer behind n_samples."""
+    nulls(e, "args")
+    noop(e, "n_rays=0", **{"args.n_rays": 0})
+    bad(e, "args.n_rays", -1)
+    bad(e, "args.n_importance", ni[0], ni[3])
+    for v in sorted({ni[1], ni[2]}):
+        case(e, "n_importance=%d passes, n_samples answers" % v, **{"args.n_importance": v, "args.n_samples": ns[3]})
+    bad(e, "args.n_samples", ns[0], ns[3])
+    for v in (ns[1], ns[2]):
+        case(e, "n_samples=%d passes, %s answers" % (v, required[0]), **{"args.n_samples": v, "args." + required[0]: None})
+    nulls(e, *["args." + k for k in required])
+    bad(e, "args.rng_flags", 1, 8)
+    for k in ("z_coarse_out", "noise_coarse_out", "noise_fine_out"):
+        case(e, k, **{"args." + k: P})
+
+
+for e in ("crnerf_render_rays_lean_bf16", "crnerf_render_rays_lean_f16"):
+    entry(e, args=RENDER_LEAN, stream=None)
+    companion_checks(e, (0, 1, 256, 257), (2, 3, 256, 257), ("packed_coarse", "packed_fine", "rays", "feature_fine", "depth_fine"))
+RENDER_CW = S("RenderArgs", packed_coarse=P, rays=P, n_rays=1, n_samples=2, n_importance=0, weights_coarse=P)
+for e in ("crnerf_render_coarse_weights_f32h2", "crnerf_render_coarse_weights_f32x3", "crnerf_render_coarse_weights_f32x3_repair",
+          "crnerf_render_coarse_weights_f16"):
+    entry(e, args=RENDER_CW, stream=None)
+    companion_checks(e, (-1, 0, 0, 1), (1, 2, 256, 257), ("packed_coarse", "rays", "weights_coarse"))
+RENDER_LEAN_FINE = S("RenderArgs", packed_fine=P, rays=P, n_rays=1, n_samples=3, n_importance=1, weights_coarse=P, feature_fine=P, depth_fine=P)
+e = entry("crnerf_render_rays_lean_bf16_fine", args=RENDER_LEAN_FINE, stream=None)
+companion_checks(e, (0, 1, 256, 257), (2, 3, 256, 257), ("packed_fine", "rays", "weights_coarse", "feature_fine", "depth_fine"))
+# the launch layer behind them: the one-workgroup-per-quad grid of the repair launch
+case("crnerf_render_coarse_weights_f32x3_repair", "more ray quads than a launch", **{"args.n_rays": 2 ** 34, "args.n_samples": 4})
 
 
 # ---- the launch layer behind abi.hip (csrc/launch.h and the launchers' own refusals): every one fires before anything is launched
@@ -532,7 +569,7 @@ def _set_field(obj, f, v):
 
 def build_args(_lib, e, mut, is_noop):
     """The ctypes arguments of one case (and what they point to, to be kept alive across the call)."""
-    base, argtypes = BASES[e], _lib.SIGNATURES[e][1]
+    base, argtypes = BASES[e], _lib.ALL_SIGNATURES[e][1]
     assert len(base) == len(argtypes), "%s: the base call has %d arguments, the signature table %d" % (e, len(base), len(argtypes))
     known = set(base)
     for m in mut:

@@ -19,7 +19,13 @@ The file holds the SHA-256 of every returned tensor except acts_* (those buffers
 tests/test_gpu_train_fused.py and tests/test_gpu_mixed_fused.py cover them), and for the R = 6 cases the arrays themselves, so that a failure names
 the first element that differs.  The raw_* rows of the training twins would alone take the file past its 200 KB budget: of those it holds one
 CRC-32 per sample point (a failure names the first row).  It also holds the CU count it was recorded on, because the large ray count depends on
-it.  The test module imports its cases and inputs from here, so both always issue the same calls."""
+it.  The test module imports its cases and inputs from here, so both always issue the same calls.
+
+A second fixture, tests/golden/g_render_entries_parent.npz (--fixture entries), holds the same for the render entries of include/crnerf_lean.h and
+include/crnerf_lean_composite.h, which did not exist when the first one was recorded: ENTRY_VARIANTS, on the same Inputs, forms "all" and "zc" and
+ray counts.  The fixture in the tree was recorded from the build before csrc/abi.hip described every render entry by one descriptor.  The inputs
+keep the fp16 cores in range, so the repair launches behind "auto" and repair_x3= leave at once (tests/test_gpu_lean_composite.py covers the other
+side)."""
 import argparse
 import hashlib
 import json
@@ -35,6 +41,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g_render_launch_parent.npz")
+ENTRIES_GOLDEN = os.path.join(ROOT, "tests", "golden", "g_render_entries_parent.npz")
 DEV = "cuda:0"
 SEED = 20261020
 NC, NI, SMALL_R, MLP_P = 5, 4, 6, 130
@@ -56,6 +63,14 @@ SIZES = ("small", "large")
 # (variant, form, size) of every render case; (precision, sigma_only) of every MLP case
 RENDER_CASES = ([(v, f, s) for v in RENDER_VARIANTS for f in ("all", "zc") for s in SIZES] + [(v, "draw", s) for v in DRAW_VARIANTS for s in SIZES])
 MLP_CASES = [(p, so) for p in PRECISIONS for so in (False, True)]
+# name: (the ops function, precision, keyword arguments on top of the form's); "x3" as repair_x3 stands for the coarse model's f32x3 pack
+ENTRY_VARIANTS = {
+    "lean_bf16": ("render_rays", "bf16", {"lean": True}), "lean_f16": ("render_rays", "f16", {"lean": True}),
+    "cw_f32h2": ("render_coarse_weights", "f32h2", {}), "cw_f32x3": ("render_coarse_weights", "f32x3", {}), "cw_auto": ("render_coarse_weights", "auto", {}),
+    "cw_f16_repair": ("render_coarse_weights", "f16", {"repair_x3": "x3"}),
+    "lean_bf16_fine": ("render_rays_bf16_fine", "bf16", {"lean": True}),
+}
+ENTRY_CASES = [(v, f, s) for v in ENTRY_VARIANTS for f in ("all", "zc") for s in SIZES]
 
 
 def case_name(case):
@@ -130,6 +145,30 @@ def run_render(inp, case):
     return {k: v for k, v in res.items() if not k.startswith("acts_")}
 
 
+def run_entry(inp, case):
+    """The returned dict of one case of ENTRY_VARIANTS: every optional input the entry reads is in use."""
+    from crnerf_amd import ops
+    variant, form, size = case
+    fn, precision, extra = ENTRY_VARIANTS[variant]
+    t = inp.t[size]
+    pc, pf = inp.packs[precision]
+    kw = dict(use_disp=True, noise_std=0.5, **extra)
+    kw.update(dict(z_steps=inp.z_steps) if form == "all" else dict(z_coarse=t["z_coarse"]))
+    with torch.no_grad():
+        if fn == "render_coarse_weights":
+            if kw.get("repair_x3") == "x3":
+                kw["repair_x3"] = inp.packs["f32x3"][0]
+            res = ops.render_coarse_weights(pc, t["rays"], NC, precision=precision, noise_coarse=t["noise_coarse"], **kw)
+        else:
+            kw.update(view_dir=t["view_dir"], noise_fine=t["noise_fine"], want_z_fine=True, u=t["u_rays"] if form == "all" else inp.u_shared)
+            if fn == "render_rays_bf16_fine":
+                res = ops.render_rays_bf16_fine(pf, t["rays"], t["weights_coarse"], NC, NI, **kw)
+            else:
+                res = ops.render_rays(pc, pf, t["rays"], NC, NI, precision=precision, noise_coarse=t["noise_coarse"], **kw)
+    torch.cuda.synchronize()
+    return res
+
+
 def run_mlp(inp, case):
     from crnerf_amd import ops
     precision, sigma_only = case
@@ -158,16 +197,28 @@ def stored(key, w):
     return row_crcs(w) if key.startswith("raw_") else w
 
 
-def record():
-    cus = device_cus()
-    inp = Inputs(cus)
-    shas, arrays = {}, {}
-    for case in RENDER_CASES:
-        for k, v in run_render(inp, case).items():
+def _record_cases(inp, cases, run, shas, arrays):
+    for case in cases:
+        for k, v in run(inp, case).items():
             w = words(v)
             shas["%s/%s" % (case_name(case), k)] = sha(w)
             if case[2] == "small":
                 arrays["%s/%s" % (case_name(case), k)] = stored(k, w)
+
+
+def record_entries():
+    cus = device_cus()
+    shas, arrays = {}, {}
+    _record_cases(Inputs(cus), ENTRY_CASES, run_entry, shas, arrays)
+    arrays["meta"] = np.array(json.dumps({"cus": cus, "sha256": shas}, sort_keys=True))
+    return arrays
+
+
+def record():
+    cus = device_cus()
+    inp = Inputs(cus)
+    shas, arrays = {}, {}
+    _record_cases(inp, RENDER_CASES, run_render, shas, arrays)
     for case in MLP_CASES:
         for k, v in run_mlp(inp, case).items():
             shas["mlp/%s/%s" % (case_name(case), k)] = sha(words(v))
@@ -177,9 +228,11 @@ def record():
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--fixture", choices=("launch", "entries"), default="launch")
+    ap.add_argument("--out")
     a = ap.parse_args()
-    arrays = record()
+    a.out = a.out or (GOLDEN if a.fixture == "launch" else ENTRIES_GOLDEN)
+    arrays = record() if a.fixture == "launch" else record_entries()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez_compressed(a.out, **arrays)
     size = os.path.getsize(a.out)
