@@ -38,7 +38,8 @@ def set_precision(precision):
     delta tensor; bf16x3 -- three-piece bf16 splits -- inside the same launch where an operand leaves fp16's range) -- every
     product fp32-ACCURATE (float64 distance of the fp32 MFMA), none bit-for-bit the reference's fp32 arithmetic.  Opt out with
     autograd.set_training_forward_precision("f32") / CRNERF_TRAIN_FWD=f32 and autograd.set_wgrad_precision("f32") / CRNERF_WGRAD_F32=1
-    (every product on the fp32 matrix cores); autograd.set_training_precision("bf16") is the opt-in mixed-precision mode."""
+    (every product on the fp32 matrix cores); autograd.set_training_precision("bf16") is the opt-in mixed-precision mode.
+    autograd.training_plan() answers what a grad-mode render starting now would run as (setters and environment, resolved once per call)."""
     global _precision
     from .precision import resolve
     _precision = resolve(precision, composite=True)

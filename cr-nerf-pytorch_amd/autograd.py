@@ -10,6 +10,9 @@ path is one autograd.Function whose backward calls the HIP backward twins.
 Inputs that the reference does not train through this path (ray geometry, embeddings, hierarchical
 depths -- the latter are .detach()ed at models/rendering.py:184) get no gradient.
 """
+import os
+from typing import NamedTuple, Optional
+
 import torch
 
 from . import ops
@@ -18,12 +21,12 @@ from .precision import resolve
 
 class MlpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, module, *params):
+    def forward(ctx, x, module, plan, *params):
         if module is not None and hasattr(module, "invalidate_packed"):
             module.invalidate_packed()       # an optimiser step follows; optimisers that write p.data do not bump p._version
         state = dict(zip(ops.MLP_TENSOR_NAMES, params))
-        ctx.mixed = None
-        if get_training_bf16():
+        ctx.mixed, ctx.plan = None, plan
+        if plan.family == "bf16":
             packed, tensors = ops.pack_mlp_weights_mixed(state)
             out, acts = ops.mlp_forward_train_mixed(packed, tensors, x)
             ctx.mixed = packed          # forward and transposed fragment streams: the backward needs no second pack
@@ -37,22 +40,64 @@ class MlpFn(torch.autograd.Function):
         x, out, acts, *params = ctx.saved_tensors
         if ctx.mixed is not None:
             tensors = [p.detach() for p in params]
-            return (None, None) + tuple(ops.mlp_backward_mixed(ctx.mixed, tensors, x, out, d_out.contiguous(), acts))
+            return (None, None, None) + tuple(ops.mlp_backward_mixed(ctx.mixed, tensors, x, out, d_out.contiguous(), acts))
         packed_t = ops.pack_mlp_weights_t(dict(zip(ops.MLP_TENSOR_NAMES, params)))
-        grads = ops.mlp_backward(packed_t, x, out, d_out.contiguous(), acts, wgrad_bf16=get_wgrad_bf16())
-        return (None, None) + tuple(grads)
+        grads = ops.mlp_backward(packed_t, x, out, d_out.contiguous(), acts, wgrad_bf16=ctx.plan.wgrad_code())
+        return (None, None, None) + tuple(grads)
 
 
-def mlp_forward_with_grad(module, x):
+def mlp_forward_with_grad(module, x, plan=None):
+    """NeRF_sigma.forward on embedded points with gradients for its 24 tensors.  plan: the caller's TrainPlan (None: resolved here); the backward
+    follows it."""
     params = list(ops.mlp_params(module))
     if x.requires_grad:
         raise NotImplementedError("crnerf_amd: gradients w.r.t. the embedded input of NeRF_sigma are not implemented "
                                   "(the rendering path never needs them: embeddings are functions of fixed ray geometry)")
-    return MlpFn.apply(x, module, *params)
+    return MlpFn.apply(x, module, plan or training_plan(), *params)
 
 
-_RECOMPUTE = [False]
-_WGRAD_BF16 = [None]
+# ---- the training settings.  What the four setters stored (forward / wgrad None: not set -- the environment, then the default, decides; bf16 and
+# recompute are OR-ed with the environment), and training_plan(), which resolves setters and environment into one immutable TrainPlan.  A grad-mode
+# render resolves it ONCE (models/rendering.py, or fused_render_with_grad / mlp_forward_with_grad for their direct callers) and its nodes read
+# nothing else, forward and backward: one render call is one consistent mode, whatever is set or exported before its backward runs.
+_TRAIN_FWD, _WGRAD_BF16, _TRAIN_BF16, _RECOMPUTE = [None], [None], [False], [False]     # one slot each (tests/test_precision_host.py reads and restores them)
+_FWD_ENV = {"x3": "f32x3", "f32x3": "f32x3", "h2": "f32h2", "f32h2": "f32h2", "f32": "f32", "fp32": "f32", "auto": "auto"}
+
+
+def _env_flag(name):
+    return os.environ.get(name, "") not in ("", "0")
+
+
+class TrainPlan(NamedTuple):
+    family: str            # "f32": the fp32-accurate twins | "bf16": the mixed-precision mode (set_training_precision)
+    forward: str           # "f32" | "f32x3" | "f32h2" | "auto": the core of the f32 family's forward and data gradient (set_training_forward_precision)
+    recompute: bool        # set_training_recompute
+    bf16_fused: bool       # get_training_bf16_fused
+    wgrad: Optional[int]   # set_wgrad_precision's code 0..3, None: the default (wgrad_code)
+    chunk_points: int      # fine-pass sample points per ray chunk (fused_render_with_grad)
+
+    def wgrad_code(self, h2=False):
+        """0: exact fp32 MFMA; 1: bf16-rounded operands; 2: three-piece bf16 split (fp32-accurate); 3: two-piece fp16 split of the full blocks
+        (fp32-accurate, h2 data gradient only: `h2` says whether the caller runs it -- without it 3 means 2)."""
+        if self.wgrad is None:
+            return 3 if h2 else 2
+        return self.wgrad if h2 else min(self.wgrad, 2)
+
+
+def training_plan():
+    """The training settings in force now: the setters' state and the environment, read here (at call time, once per call) and nowhere else.
+    A setter value wins over the environment for forward and wgrad; bf16 and recompute are each setter OR environment."""
+    forward, wgrad = _TRAIN_FWD[0], _WGRAD_BF16[0]
+    if forward is None:
+        forward = _FWD_ENV.get(os.environ.get("CRNERF_TRAIN_FWD", "").lower()) or ("f32x3" if _env_flag("CRNERF_TRAIN_FWD_X3") else "auto")
+    if wgrad is None:
+        wgrad = 0 if _env_flag("CRNERF_WGRAD_F32") else 2 if _env_flag("CRNERF_WGRAD_BF16X3") else 1 if _env_flag("CRNERF_WGRAD_BF16") else None
+    recompute = _RECOMPUTE[0] or _env_flag("CRNERF_TRAIN_RECOMPUTE")
+    # ray chunks of <= 2^21 fine-pass points (round 6; 2^20 before): half as many launches, partial-sum slabs and kernel tails -- the 65,536-ray
+    # step 191.8 -> 186.9 / 188.3 ms, 16,384 rays 50.8 -> 49.5 ms, +11 GB of backward scratch (2.8 M points: no better; the kernels address rows
+    # with 32-bit offsets, < 3.9 M points per call).  Recompute mode keeps 2^20: there the chunk IS the step's activation memory.
+    return TrainPlan("bf16" if (_TRAIN_BF16[0] or _env_flag("CRNERF_TRAIN_BF16")) else "f32", forward, recompute, not _env_flag("CRNERF_TRAIN_BF16_UNFUSED"), wgrad,
+                     int(os.environ.get("CRNERF_TRAIN_CHUNK_POINTS", 1 << (20 if recompute else 21))))
 
 
 def set_wgrad_precision(precision=None):
@@ -81,10 +126,6 @@ def set_wgrad_precision(precision=None):
                                                      (1 if resolve(precision) == "bf16" else 0))
 
 
-_TRAIN_BF16 = [False]
-_TRAIN_FWD = [None]
-
-
 def set_training_forward_precision(precision=None):
     """None: the default ("auto", see get_training_forward_mode).  "f32": the grad-mode forward of render_rays_cross_ray on the fp32 matrix cores (crnerf_render_rays_train_f32).  "f32x3": the same
     fp32 forward on the bf16 matrix cores (crnerf_render_rays_train_f32x3: three-piece bf16 splits of every fp32 operand, six MFMAs per
@@ -110,23 +151,7 @@ def get_training_forward_mode():
     Why "auto" is the default: it is fp32-accurate (every saved row, output and gradient held to the fp32 twins' bars, tests/test_gpu_h2.py), it
     cannot fail on range (device-side fall-back to the scale-free f32x3 twins), and it is what the part is fast at -- the 65,536-ray train.sh
     step 343 -> 256 ms, the 1,024-ray one 9.1 -> 7.6-8.1 ms.  "f32" keeps every product on the fp32 matrix cores, the reference's arithmetic."""
-    import os
-    if _TRAIN_FWD[0] is not None:
-        return _TRAIN_FWD[0]
-    env = os.environ.get("CRNERF_TRAIN_FWD", "").lower()
-    if env in ("x3", "f32x3"):
-        return "f32x3"
-    if env in ("h2", "f32h2"):
-        return "f32h2"
-    if env in ("f32", "fp32"):
-        return "f32"
-    if env == "auto":
-        return "auto"
-    return "f32x3" if os.environ.get("CRNERF_TRAIN_FWD_X3", "") not in ("", "0") else "auto"
-
-
-def get_training_forward_x3():
-    return get_training_forward_mode() == "f32x3"
+    return training_plan().forward
 
 
 def _pack_for_training(mode, state):
@@ -150,23 +175,12 @@ def set_training_precision(precision="f32"):
 
 
 def get_training_bf16():
-    import os
-    return _TRAIN_BF16[0] or os.environ.get("CRNERF_TRAIN_BF16", "") not in ("", "0")
+    return training_plan().family == "bf16"
 
 
 def get_wgrad_bf16(h2=False):
-    """0: exact fp32 MFMA; 1: bf16-rounded operands; 2: three-piece bf16 split (fp32-accurate); 3: two-piece fp16 split of the full blocks
-    (fp32-accurate, h2 data gradient only: `h2` says whether the caller runs it -- without it 3 means 2)."""
-    import os
-    if _WGRAD_BF16[0] is not None:
-        return int(_WGRAD_BF16[0]) if h2 else min(int(_WGRAD_BF16[0]), 2)
-    if os.environ.get("CRNERF_WGRAD_F32", "") not in ("", "0"):
-        return 0
-    if os.environ.get("CRNERF_WGRAD_BF16X3", "") not in ("", "0"):
-        return 2
-    if os.environ.get("CRNERF_WGRAD_BF16", "") not in ("", "0"):
-        return 1
-    return 3 if h2 else 2
+    """TrainPlan.wgrad_code of the settings in force now."""
+    return training_plan().wgrad_code(h2)
 
 
 def set_training_recompute(flag=True):
@@ -177,8 +191,14 @@ def set_training_recompute(flag=True):
 
 
 def get_training_recompute():
-    import os
-    return _RECOMPUTE[0] or os.environ.get("CRNERF_TRAIN_RECOMPUTE", "") not in ("", "0")
+    return training_plan().recompute
+
+
+def get_training_bf16_fused():
+    """The mixed-precision mode trains through the fused bf16 renderer (FusedRenderFn on crnerf_render_rays_train_bf16) unless
+    CRNERF_TRAIN_BF16_UNFUSED=1 asks for the round-2 path (embedded points -> per-layer GEMM twins -> compositing), kept for A/B runs and as the
+    module-level twin."""
+    return training_plan().bf16_fused
 
 
 def _embed_points(rays, z, view_dir):
@@ -188,48 +208,114 @@ def _embed_points(rays, z, view_dir):
     return ops.embed_points(rays, z, demb)       # one pass, one 480-byte row per point (the torch composition moved ~1.5 KB)
 
 
+def _render(cfg, packed, rays, precision, train, **extra):
+    """The training path's one call of the fused renderer for a chunk of rays: train=True is the training twin (crnerf_render_rays_train_*), which
+    also returns acts_* / raw_* per pass; train=False the inference kernel, the forward of a recomputing node."""
+    return ops.render_rays(packed[0], packed[1] if cfg["Ni"] > 0 else None, rays, cfg["Nc"], cfg["Ni"], use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
+                           z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"], noise_std=cfg["noise_std"],
+                           precision=precision, train=train, **extra)
+
+
+def _draws(plan, cfg):
+    """Only the f32 family's kernels draw (in-kernel jitter / uniforms / noise from cfg["rng"] and the z_steps table)."""
+    return {"rng": cfg.get("rng"), "z_steps": cfg.get("z_steps")} if plan.family == "f32" else {}
+
+
+def _cached(shared, key, make):
+    """One set of packs per render call, shared by its ray chunks (fused_render_with_grad's `shared`; None: a single chunk).  Round 6: eight chunks
+    of a 65,536-ray step packed the same weights eight times, forward and transposed: ~130 launches and 0.7 ms."""
+    if shared is None:
+        return make()
+    if key not in shared:
+        shared[key] = make()
+    return shared[key]
+
+
+def _forward_packs(plan, mode, shared, states):
+    """What _render reads.  The f32 family shares them between the chunks of a call (and between a recomputing node's forward and backward); the
+    bf16 family packs per node."""
+    if plan.family == "bf16":
+        return [ops.pack_mlp_weights(st, precision="bf16") for st in states]
+    return _cached(shared, ("fwd", mode), lambda: [_pack_for_training(mode, st) for st in states])
+
+
+def _pass_backward(plan, mode, cfg, state, m, rays, z, noise, rows, d_w, d_f, d_d):
+    """The 24 parameter gradients of pass m (0 coarse, 1 fine) from the gradients of its three outputs: crnerf_composite_backward_f32, then the MLP
+    backward of the plan's family.  rows: (acts, raw) as the training twin wrote them, or None -- CRNERF_TRAIN_BF16_UNFUSED=1, the round-2 rebuild
+    of the bf16 family (embedded points -> per-layer GEMM twins), whose outputs differ from the forward's by the bf16 kernels' mutual tolerance
+    (mean 3e-5, tests/test_gpu_bf16.py)."""
+    f32, x = plan.family == "f32", None
+    if not f32:
+        packed, tensors = ops.pack_mlp_weights_mixed(state)
+    if rows is None:
+        x = _embed_points(rays, z, cfg["view_dir"])
+        raw, acts = ops.mlp_forward_train_mixed(packed, tensors, x)
+    else:
+        acts, raw = rows
+    R, N = z.shape
+    if d_f is None:
+        d_f = torch.zeros(R, 64, device=raw.device)
+    d_raw = ops.composite_backward(raw.view(R, N, 65), z, d_f.contiguous(), None if d_d is None else d_d.contiguous(),
+                                   None if d_w is None else d_w.contiguous(), noise=noise, noise_std=cfg["noise_std"]).view(-1, 65)
+    if not f32:    # per-layer bf16 GEMMs for the data gradients, weight gradients from the stored rows (crnerf_mlp_backward_mixed_ex_f32)
+        return ops.mlp_backward_mixed(packed, tensors, x, raw.view(-1, 65), d_raw, acts, fused_acts=rows is not None)
+    x = _embed_points(rays, z, cfg["view_dir"])
+    x3, h2 = mode == "f32x3", mode in ("f32h2", "auto")   # a split-core forward brings the data gradient on the same core with it (set_training_forward_precision)
+    core, shared = "h2" if h2 else "x3" if x3 else "f32", cfg.get("shared")
+    # the transposed packs of a step's weights: made by the first chunk's backward, used by all of them
+    packed_t = _cached(shared, ("t", core, m), lambda: (ops.pack_mlp_weights_t_h2 if h2 else ops.pack_mlp_weights_t_x3 if x3 else ops.pack_mlp_weights_t)(state))
+    net = _cached(shared, ("t", "x3", m), lambda: ops.pack_mlp_weights_t_x3(state)) if mode == "auto" else None      # "auto": the f32x3 data gradient stands by (device-side range flag)
+    return ops.mlp_backward(packed_t, x, raw.view(-1, 65), d_raw, acts, wgrad_bf16=plan.wgrad_code(h2), dgrad_x3=x3, dgrad_h2=h2, fallback_t_x3=net)
+
+
 class FusedRenderFn(torch.autograd.Function):
-    """render_rays_cross_ray's arithmetic (rendering.py:100-194) for one chunk of rays as ONE differentiable node:
-    fwd crnerf_render_rays_train_f32 (posenc + both MLPs + activation save + compositing + sample_pdf/merge in one launch),
-    bwd per pass crnerf_composite_backward_f32 -> crnerf_mlp_backward_f32.  weights_coarse -> sample_pdf carries no gradient
-    (.detach() at rendering.py:184); rays, depths and noise are inputs, not differentiated."""
+    """render_rays_cross_ray's arithmetic (rendering.py:100-194) for one chunk of rays as ONE differentiable node, in every training mode: what it
+    does is cfg["plan"] (a TrainPlan, resolved once per render call), read alike by forward and backward.  weights_coarse -> sample_pdf carries no
+    gradient (.detach() at rendering.py:184); rays, depths and noise are inputs, not differentiated.
+
+    Family f32: fwd crnerf_render_rays_train_f32 / _f32x3 / _f32h2 (+ the x3 repair under "auto") -- posenc + both MLPs + activation save +
+    compositing + sample_pdf/merge in one launch; bwd per pass crnerf_composite_backward_f32 -> crnerf_mlp_backward_f32 on the forward's core.
+    Family bf16 (set_training_precision("bf16")): fwd crnerf_render_rays_train_bf16 -- the fused bf16 renderer that also keeps, per pass, the bf16
+    activation rows / relu bits / embedded input (written from the registers they are born in) and the raw MLP outputs; bwd per pass
+    crnerf_composite_backward_f32 -> crnerf_mlp_backward_mixed_ex_f32.  The gradient is taken at exactly the activations the loss saw.
+    plan.recompute: the forward IS the inference renderer (bf16: crnerf_render_rays_bf16, ~0.22 ms per 1,024 rays) and keeps nothing but rays /
+    depths / noise; backward re-runs the chunk through the training twin -- bit-identical outputs, same (seed, ray, sample) -> same draws, so the
+    gradient is again taken at the activations the loss saw -- or, bf16 with CRNERF_TRAIN_BF16_UNFUSED=1, rebuilds the rows (_pass_backward).
+
+    What the families do NOT share, on purpose:
+      * only f32 defers its parameter gradients (_DEFER_ON): deferral changes the summation order over the chunks of a call;
+      * only f32 takes cfg["rng"] / cfg["z_steps"] and composites its backward with what the kernel drew (z_coarse_bwd, noise_c_bwd, noise_f_bwd);
+      * only f32 shares packs between the chunks of a call (_forward_packs, _pass_backward); bf16 packs per node;
+      * bf16 with stored rows does not save rays (its backward embeds nothing); every other mode does;
+      * ctx.mode differs from the plan's forward only for "auto" (_effective_mode); it is "bf16" for the bf16 family."""
 
     @staticmethod
     def forward(ctx, cfg, rays, *params):
         ctx.set_materialize_grads(False)     # an unused pass (e.g. coarse when only feature_fine feeds the loss) gets None, not zeros
-        Nc, Ni = cfg["Nc"], cfg["Ni"]
+        plan, Ni = cfg["plan"], cfg["Ni"]
+        f32 = plan.family == "f32"
         n_models = 2 if Ni > 0 else 1
         states = [dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])) for m in range(n_models)]
         for mod in cfg["modules"]:
             if mod is not None and hasattr(mod, "invalidate_packed"):
                 mod.invalidate_packed()      # an optimiser step follows (see MlpFn)
-        mode = get_training_forward_mode()
-        # one set of packs per render call, shared by its ray chunks (fused_render_with_grad; round 6: eight chunks of a 65,536-ray step packed
-        # the same weights eight times, forward and transposed: ~130 launches and 0.7 ms)
-        shared = cfg.get("shared")
-        packed = shared.get(("fwd", mode)) if shared is not None else None
-        if packed is None:
-            packed = [_pack_for_training(mode, st) for st in states]
-            if shared is not None:
-                shared[("fwd", mode)] = packed
-        recompute = get_training_recompute()
+        mode = plan.forward if f32 else "bf16"
+        packed = _forward_packs(plan, mode, cfg.get("shared"), states)
         ctx.mode = _effective_mode(mode, packed)   # the backward follows the forward's core
-        out = ops.render_rays(packed[0], packed[1] if Ni > 0 else None, rays, Nc, Ni, use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
-                              z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"],
-                              noise_std=cfg["noise_std"], want_z_fine=True, train=not recompute, rng=cfg.get("rng"), z_steps=cfg.get("z_steps"),
-                              precision=mode)
-        if cfg.get("rng") is not None:       # what the kernel drew is what the backward composites with (a few KB per ray chunk)
+        out = _render(cfg, packed, rays, mode, not plan.recompute, want_z_fine=True, **_draws(plan, cfg))
+        if f32 and cfg.get("rng") is not None:       # what the kernel drew is what the backward composites with (a few KB per ray chunk)
             cfg = dict(cfg, z_coarse_bwd=out["z_coarse_used"], noise_c_bwd=out.get("noise_coarse_used", cfg["noise_c"]),
                        noise_f_bwd=out.get("noise_fine_used", cfg["noise_f"]))
-        ctx.cfg, ctx.recompute, ctx.n_models = cfg, recompute, n_models
-        keep = [rays, out["z_fine"] if Ni > 0 else rays.new_empty(0)]
-        if not recompute:
+        ctx.cfg, ctx.n_models = cfg, n_models
+        keep = ([rays] if f32 or plan.recompute else []) + [out["z_fine"] if Ni > 0 else rays.new_empty(0)]
+        if not plan.recompute:
             keep += [out["acts_coarse"], out["raw_coarse"]] + ([out["acts_fine"], out["raw_fine"]] if Ni > 0 else [])
         ctx.n_keep = len(keep)
         ctx.save_for_backward(*keep, *params)
         # a batch of more rays than hparams.chunk runs this node once per chunk: with deferral on, the chunks' parameter gradients are summed by one
         # multi-tensor add per chunk at the end of backward instead of 48 AccumulateGrad adds per chunk (336 launches of a 65,536-ray step)
-        ctx.defer, ctx.leaves = _DEFER_ON[0], ([_leaf_of(t) for t in params] if _DEFER_ON[0] else None)
+        ctx.defer = f32 and _DEFER_ON[0]
+        ctx.leaves = [_leaf_of(t) for t in params] if ctx.defer else None
         res = (out["weights_coarse"], out["feature_coarse"], out["depth_coarse"])
         if Ni > 0:
             res += (out["weights_fine"], out["feature_fine"], out["depth_fine"])
@@ -238,188 +324,38 @@ class FusedRenderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *g):
         cfg = ctx.cfg
-        Nc, Ni = cfg["Nc"], cfg["Ni"]
+        plan, Ni = cfg["plan"], cfg["Ni"]
         saved = ctx.saved_tensors
-        keep, params = saved[:ctx.n_keep], saved[ctx.n_keep:]
-        rays, z_fine = keep[0], keep[1]
+        keep, params = list(saved[:ctx.n_keep]), saved[ctx.n_keep:]
+        rays = keep.pop(0) if (plan.family == "f32" or plan.recompute) else None
+        z_fine = keep.pop(0)                 # what is left of keep: (acts, raw) per pass, unless the node recomputes
         states = [dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])) for m in range(ctx.n_models)]
-        shared = cfg.get("shared")
-
-        def cached(key, make):     # the transposed packs of a step's weights: made by the first chunk's backward, used by all of them
-            if shared is None:
-                return make()
-            if key not in shared:
-                shared[key] = make()
-            return shared[key]
-        if ctx.recompute:
-            packed = cached(("fwd", ctx.mode), lambda: [_pack_for_training(ctx.mode, st) for st in states])
-            out = ops.render_rays(packed[0], packed[1] if Ni > 0 else None, rays, Nc, Ni, use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
-                                  z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"],
-                                  noise_std=cfg["noise_std"], train=True, rng=cfg.get("rng"), z_steps=cfg.get("z_steps"),
-                                  precision=ctx.mode)   # same (seed, ray, sample) -> same draws
-            per_pass = [(out["acts_coarse"], out["raw_coarse"])] + ([(out["acts_fine"], out["raw_fine"])] if Ni > 0 else [])
+        rebuild = plan.recompute and plan.family == "bf16" and not plan.bf16_fused
+        if plan.recompute and not rebuild:
+            out = _render(cfg, _forward_packs(plan, ctx.mode, cfg.get("shared"), states), rays, ctx.mode, True, **_draws(plan, cfg))
+            keep = [out["acts_coarse"], out["raw_coarse"]] + ([out["acts_fine"], out["raw_fine"]] if Ni > 0 else [])
             z_fine = out["z_fine"] if Ni > 0 else z_fine
             del out
-        else:
-            per_pass = [(keep[2], keep[3])] + ([(keep[4], keep[5])] if Ni > 0 else [])
         grads = []
-        for m, (acts, raw) in enumerate(per_pass):
+        for m in range(ctx.n_models):
             d_w, d_f, d_d = g[3 * m], g[3 * m + 1], g[3 * m + 2]
-            z = z_fine if m == 1 else cfg.get("z_coarse_bwd", cfg["z_coarse"])
-            noise = cfg.get("noise_f_bwd", cfg["noise_f"]) if m == 1 else cfg.get("noise_c_bwd", cfg["noise_c"])
             if d_w is None and d_f is None and d_d is None:
                 grads += [None] * 24
                 continue
-            if d_f is None:
-                d_f = torch.zeros(raw.shape[0], 64, device=raw.device)
-            d_raw = ops.composite_backward(raw, z, d_f.contiguous(), None if d_d is None else d_d.contiguous(),
-                                           None if d_w is None else d_w.contiguous(), noise=noise, noise_std=cfg["noise_std"])
-            x = _embed_points(rays, z, cfg["view_dir"])
-            mode = getattr(ctx, "mode", "f32")   # a split-core forward brings the data gradient on the same core with it (set_training_forward_precision)
-            x3, h2 = mode == "f32x3", mode in ("f32h2", "auto")
-            packed_t = cached(("t", "h2" if h2 else "x3" if x3 else "f32", m),
-                              lambda: ops.pack_mlp_weights_t_h2(states[m]) if h2 else (ops.pack_mlp_weights_t_x3(states[m]) if x3 else ops.pack_mlp_weights_t(states[m])))
-            net = cached(("t", "x3", m), lambda: ops.pack_mlp_weights_t_x3(states[m])) if mode == "auto" else None      # "auto": the f32x3 data gradient stands by (device-side range flag)
-            grads += ops.mlp_backward(packed_t, x, raw.view(-1, 65), d_raw.view(-1, 65), acts, wgrad_bf16=get_wgrad_bf16(h2), dgrad_x3=x3, dgrad_h2=h2,
-                                      fallback_t_x3=net)
-            del x, d_raw
-        if getattr(ctx, "defer", False):
+            z = z_fine if m == 1 else cfg.get("z_coarse_bwd", cfg["z_coarse"])
+            noise = cfg.get("noise_f_bwd", cfg["noise_f"]) if m == 1 else cfg.get("noise_c_bwd", cfg["noise_c"])
+            grads += _pass_backward(plan, ctx.mode, cfg, states[m], m, rays, z, noise, None if rebuild else (keep[2 * m], keep[2 * m + 1]), d_w, d_f, d_d)
+        if ctx.defer:
             todo = [(leaf, gr.view(leaf.shape)) for leaf, gr in zip(ctx.leaves, grads) if leaf is not None and gr is not None]
             _defer([t[0] for t in todo], [t[1] for t in todo])
             grads = [None if (leaf is not None or gr is None) else gr for leaf, gr in zip(ctx.leaves, grads)]
         return (None, None) + tuple(grads)
 
 
-class MixedRecomputeRenderFn(torch.autograd.Function):
-    """set_training_precision("bf16") + set_training_recompute(True), one chunk of rays: the forward IS the fused bf16 inference
-    renderer (crnerf_render_rays_bf16: ~0.22 ms per 1,024 rays, nothing kept but rays / depths / noise); backward re-runs the chunk through
-    the renderer's training twin (crnerf_render_rays_train_bf16 -- bit-identical outputs, so the gradient is taken at exactly the activations
-    the loss saw) and then runs MixedFusedRenderFn's backward.  CRNERF_TRAIN_BF16_UNFUSED=1: the round-2 rebuild (embedded points -> per-layer
-    GEMM twins), whose outputs differ from the forward's by the bf16 kernels' mutual tolerance (mean 3e-5, tests/test_gpu_bf16.py)."""
-
-    @staticmethod
-    def forward(ctx, cfg, rays, *params):
-        ctx.set_materialize_grads(False)
-        Nc, Ni = cfg["Nc"], cfg["Ni"]
-        n_models = 2 if Ni > 0 else 1
-        states = [dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])) for m in range(n_models)]
-        for mod in cfg["modules"]:
-            if mod is not None and hasattr(mod, "invalidate_packed"):
-                mod.invalidate_packed()
-        packed = [ops.pack_mlp_weights(st, precision="bf16") for st in states]
-        out = ops.render_rays(packed[0], packed[1] if Ni > 0 else None, rays, Nc, Ni, use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
-                              z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"],
-                              noise_std=cfg["noise_std"], want_z_fine=True, precision="bf16")
-        ctx.cfg, ctx.n_models = cfg, n_models
-        ctx.save_for_backward(rays, out["z_fine"] if Ni > 0 else rays.new_empty(0), *params)
-        res = (out["weights_coarse"], out["feature_coarse"], out["depth_coarse"])
-        if Ni > 0:
-            res += (out["weights_fine"], out["feature_fine"], out["depth_fine"])
-        return res
-
-    @staticmethod
-    def backward(ctx, *g):
-        cfg = ctx.cfg
-        Nc, Ni = cfg["Nc"], cfg["Ni"]
-        rays, z_fine, *params = ctx.saved_tensors
-        states = [dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])) for m in range(ctx.n_models)]
-        fused = get_training_bf16_fused()
-        if fused:
-            packed_b = [ops.pack_mlp_weights(st, precision="bf16") for st in states]
-            trn = ops.render_rays(packed_b[0], packed_b[1] if Ni > 0 else None, rays, Nc, Ni, use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
-                                  z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"],
-                                  noise_std=cfg["noise_std"], precision="bf16", train=True)
-            z_fine = trn["z_fine"] if Ni > 0 else z_fine
-        grads = []
-        for m in range(ctx.n_models):
-            d_w, d_f, d_d = g[3 * m], g[3 * m + 1], g[3 * m + 2]
-            if d_w is None and d_f is None and d_d is None:
-                grads += [None] * 24
-                continue
-            z = z_fine if m == 1 else cfg["z_coarse"]
-            noise = cfg["noise_f"] if m == 1 else cfg["noise_c"]
-            packed, tensors = ops.pack_mlp_weights_mixed(states[m])
-            R, N = z.shape
-            if fused:
-                tag = "fine" if m == 1 else "coarse"
-                raw, acts, x = trn["raw_" + tag].view(-1, 65), trn["acts_" + tag], None
-            else:
-                x = _embed_points(rays, z, cfg["view_dir"])
-                raw, acts = ops.mlp_forward_train_mixed(packed, tensors, x)
-            if d_f is None:
-                d_f = torch.zeros(R, 64, device=raw.device)
-            d_raw = ops.composite_backward(raw.view(R, N, 65), z, d_f.contiguous(), None if d_d is None else d_d.contiguous(),
-                                           None if d_w is None else d_w.contiguous(), noise=noise, noise_std=cfg["noise_std"])
-            grads += ops.mlp_backward_mixed(packed, tensors, x, raw, d_raw.view(-1, 65), acts, fused_acts=fused)
-            del x, raw, acts, d_raw
-        return (None, None) + tuple(grads)
-
-
-class MixedFusedRenderFn(torch.autograd.Function):
-    """set_training_precision("bf16"), one chunk of rays as ONE differentiable node: fwd crnerf_render_rays_train_bf16 -- the fused bf16
-    renderer that also keeps, per pass, the bf16 activation rows / relu bits / embedded input (written from the registers they are born
-    in) and the raw MLP outputs; bwd per pass crnerf_composite_backward_f32 -> crnerf_mlp_backward_mixed_ex_f32 (per-layer bf16 GEMMs for
-    the data gradients, weight gradients from the stored rows).  The gradient is taken at exactly the activations the loss saw."""
-
-    @staticmethod
-    def forward(ctx, cfg, rays, *params):
-        ctx.set_materialize_grads(False)
-        Nc, Ni = cfg["Nc"], cfg["Ni"]
-        n_models = 2 if Ni > 0 else 1
-        states = [dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])) for m in range(n_models)]
-        for mod in cfg["modules"]:
-            if mod is not None and hasattr(mod, "invalidate_packed"):
-                mod.invalidate_packed()
-        packed = [ops.pack_mlp_weights(st, precision="bf16") for st in states]
-        out = ops.render_rays(packed[0], packed[1] if Ni > 0 else None, rays, Nc, Ni, use_disp=cfg["use_disp"], view_dir=cfg["view_dir"],
-                              z_coarse=cfg["z_coarse"], u=cfg["u"], noise_coarse=cfg["noise_c"], noise_fine=cfg["noise_f"],
-                              noise_std=cfg["noise_std"], want_z_fine=True, precision="bf16", train=True)
-        ctx.cfg, ctx.n_models = cfg, n_models
-        keep = [out["z_fine"] if Ni > 0 else rays.new_empty(0), out["acts_coarse"], out["raw_coarse"]]
-        if Ni > 0:
-            keep += [out["acts_fine"], out["raw_fine"]]
-        ctx.n_keep = len(keep)
-        ctx.save_for_backward(*keep, *params)
-        res = (out["weights_coarse"], out["feature_coarse"], out["depth_coarse"])
-        if Ni > 0:
-            res += (out["weights_fine"], out["feature_fine"], out["depth_fine"])
-        return res
-
-    @staticmethod
-    def backward(ctx, *g):
-        cfg = ctx.cfg
-        saved = ctx.saved_tensors
-        keep, params = saved[:ctx.n_keep], saved[ctx.n_keep:]
-        z_fine = keep[0]
-        grads = []
-        for m in range(ctx.n_models):
-            d_w, d_f, d_d = g[3 * m], g[3 * m + 1], g[3 * m + 2]
-            if d_w is None and d_f is None and d_d is None:
-                grads += [None] * 24
-                continue
-            acts, raw = keep[1 + 2 * m], keep[2 + 2 * m]
-            z = z_fine if m == 1 else cfg["z_coarse"]
-            noise = cfg["noise_f"] if m == 1 else cfg["noise_c"]
-            if d_f is None:
-                d_f = torch.zeros(raw.shape[0], 64, device=raw.device)
-            d_raw = ops.composite_backward(raw, z, d_f.contiguous(), None if d_d is None else d_d.contiguous(),
-                                           None if d_w is None else d_w.contiguous(), noise=noise, noise_std=cfg["noise_std"])
-            packed, tensors = ops.pack_mlp_weights_mixed(dict(zip(ops.MLP_TENSOR_NAMES, params[24 * m:24 * m + 24])))
-            grads += ops.mlp_backward_mixed(packed, tensors, None, raw.view(-1, 65), d_raw.view(-1, 65), acts, fused_acts=True)
-            del d_raw
-        return (None, None) + tuple(grads)
-
-
-def get_training_bf16_fused():
-    """The mixed-precision mode trains through the fused bf16 renderer (MixedFusedRenderFn) unless CRNERF_TRAIN_BF16_UNFUSED=1 asks for the
-    round-2 path (embedded points -> per-layer GEMM twins -> compositing), kept for A/B runs and as the module-level twin."""
-    import os
-    return os.environ.get("CRNERF_TRAIN_BF16_UNFUSED", "") in ("", "0")
-
-
-def fused_render_with_grad(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u, noise_c, noise_f, noise_std, rng=None):
+def fused_render_with_grad(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u, noise_c, noise_f, noise_std, rng=None, plan=None):
     """Grad-mode render of `rays` in ray chunks of <= 2^21 fine sample points (rays are independent; the chunk bounds the
-    backward's scratch -- 10 KB of layer deltas per point -- and, in recompute mode, the live activations)."""
+    backward's scratch -- 10 KB of layer deltas per point -- and, in recompute mode, the live activations).  plan: the caller's TrainPlan (None:
+    resolved here); every chunk's node runs, forward and backward, as it says."""
     from .models.rendering import _linspace_tables
     R = rays.shape[0]
     z_steps, u_steps = _linspace_tables(Nc, Ni, rays.device)
@@ -428,14 +364,9 @@ def fused_render_with_grad(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coa
         near, far = rays[:, 6:7], rays[:, 7:8]
         z_coarse = (near * (1 - z_steps) + far * z_steps) if not use_disp else 1 / (1 / near * (1 - z_steps) + 1 / far * z_steps)
         z_coarse = z_coarse.expand(R, Nc).contiguous()
-    names = ops.MLP_TENSOR_NAMES
     params = list(ops.mlp_params(coarse)) + (list(ops.mlp_params(fine)) if Ni > 0 else [])
-    import os
-    # ray chunks of <= 2^21 fine-pass points (round 6; 2^20 before): half as many launches, partial-sum slabs and kernel tails -- the 65,536-ray
-    # step 191.8 -> 186.9 / 188.3 ms, 16,384 rays 50.8 -> 49.5 ms, +11 GB of backward scratch (2.8 M points: no better; the kernels address rows
-    # with 32-bit offsets, < 3.9 M points per call).  Recompute mode keeps 2^20: there the chunk IS the step's activation memory.
-    max_pts = int(os.environ.get("CRNERF_TRAIN_CHUNK_POINTS", str(1 << (20 if get_training_recompute() else 21))))
-    n_chunks = max(1, -(-R * (Nc + Ni) // max_pts))                 # equal chunks of at most max_pts fine-pass points
+    plan = plan or training_plan()
+    n_chunks = max(1, -(-R * (Nc + Ni) // plan.chunk_points))       # equal chunks of at most plan.chunk_points fine-pass points
     step = max(4, -(-(-(-R // n_chunks)) // 4) * 4)
     parts = []
     # packs of this call's weights, made once and shared by the chunks' nodes (forward packs, and the transposed ones their backward makes); the
@@ -447,16 +378,13 @@ def fused_render_with_grad(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coa
         sl = lambda t: None if t is None else t[lo:hi].contiguous()  # noqa: E731
         cfg = {"Nc": Nc, "Ni": Ni, "use_disp": use_disp, "view_dir": sl(view_dir), "z_coarse": sl(z_coarse),
                "u": (u_steps if u is None else sl(u)) if Ni > 0 else None, "noise_c": sl(noise_c), "noise_f": sl(noise_f),
-               "noise_std": float(noise_std), "modules": (coarse, fine), "shared": shared}
+               "noise_std": float(noise_std), "modules": (coarse, fine), "shared": shared, "plan": plan}
         if rng is not None:
             cfg["rng"] = dict(rng, ray_offset=int(rng.get("ray_offset", 0)) + lo)
             cfg["z_steps"] = z_steps          # the reference's torch.linspace table (rendering.py:160): the jitter is formed from it in-kernel
             if rng.get("u") and Ni > 0:
                 cfg["u"] = None
-        fn = FusedRenderFn
-        if get_training_bf16():
-            fn = MixedRecomputeRenderFn if get_training_recompute() else MixedFusedRenderFn
-        parts.append(fn.apply(cfg, rays[lo:hi].contiguous(), *params))
+        parts.append(FusedRenderFn.apply(cfg, rays[lo:hi].contiguous(), *params))
     keys = ["weights_coarse", "feature_coarse", "depth_coarse"] + (["weights_fine", "feature_fine", "depth_fine"] if Ni > 0 else [])
     return {k: (parts[0][i] if len(parts) == 1 else torch.cat([p[i] for p in parts], 0)) for i, k in enumerate(keys)}
 

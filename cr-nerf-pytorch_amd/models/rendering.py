@@ -37,7 +37,11 @@ def _linspace_tables(n_samples, n_importance, device):
 
 
 def _render_unfused(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u, noise_c, noise_f, noise_std, jitter, chunk, train=False,
-                    precision="f32"):
+                    precision="f32", plan=None):
+    """train: `plan` is the caller's autograd.TrainPlan (None: resolved here, once for every MLP call of this render)."""
+    if train:   # autograd.Functions over the HIP forward/backward twins (autograd.py)
+        from ..autograd import CompositeFn, mlp_forward_with_grad, training_plan
+        plan = plan or training_plan()
     R = rays.shape[0]
     o, d = rays[:, None, 0:3], rays[:, None, 3:6]
     z_steps, u_steps = _linspace_tables(Nc, Ni, rays.device)
@@ -62,9 +66,8 @@ def _render_unfused(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u,
                 rstep = max(step // N, 1)
                 zc = z.contiguous()
                 xs = [ops.embed_points(rays[i:i + rstep], zc[i:i + rstep], demb[i:i + rstep]) for i in range(0, R, rstep)]
-        if train:   # autograd.Functions over the HIP forward/backward twins (autograd.py)
-            from ..autograd import CompositeFn, mlp_forward_with_grad
-            raw = torch.cat([mlp_forward_with_grad(model, x) for x in xs], 0)
+        if train:
+            raw = torch.cat([mlp_forward_with_grad(model, x, plan) for x in xs], 0)
             return CompositeFn.apply(raw.view(R, N, 65), z.contiguous(), noise, noise_std)
         raw = torch.cat([ops.mlp_forward(model.packed_weights(precision), x, precision=precision) for x in xs], 0)   # point chunks, rendering.py:110-114
         return ops.composite(raw.view(R, N, 65), z.contiguous(), noise, noise_std)
@@ -182,9 +185,10 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     R = rays.shape[0]
     view_dir = kwargs.get('view_dir', None)
     z_coarse = u = noise_c = noise_f = None
-    from ..autograd import get_training_bf16, get_training_recompute, get_training_bf16_fused, get_training_forward_x3
-    fused_train = (train and not get_training_bf16() and not jitter and N_samples <= _FUSED_MAX and N_importance <= _FUSED_MAX
-                   and (N_importance == 0 or N_samples >= 3))
+    from ..autograd import fused_render_with_grad, training_plan
+    plan = training_plan() if train else None      # the training settings, asked once: this call's nodes run as it says, forward and backward
+    fusable = train and not jitter and N_samples <= _FUSED_MAX and N_importance <= _FUSED_MAX and (N_importance == 0 or N_samples >= 3)
+    fused_train = fusable and plan.family == "f32"
     rng = None
     if fused_train and (perturb > 0 or noise_std != 0) and ops.in_kernel_rng():
         # the fused fp32 training kernel draws the jitter / sample_pdf uniforms / density noise itself (csrc/philox.h): no [R,N] random
@@ -202,14 +206,11 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         if N_importance > 0:
             noise_f = torch.randn(R, N_samples + N_importance, device=rays.device)
 
-    if (train and (not get_training_bf16() or get_training_recompute() or get_training_bf16_fused()) and not jitter
-            and N_samples <= _FUSED_MAX and N_importance <= _FUSED_MAX
-            and (N_importance == 0 or N_samples >= 3)):
+    if fusable and (fused_train or plan.recompute or plan.bf16_fused):
         # training: the fused renderer's training twin (one launch per ray chunk: posenc + MLPs + activation save + compositing +
         # sample_pdf/merge) as one autograd node whose backward runs the HIP backward twins (autograd.FusedRenderFn)
-        from ..autograd import fused_render_with_grad
         out = fused_render_with_grad(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
-                                     float(noise_std), rng=rng)
+                                     float(noise_std), rng=rng, plan=plan)
     elif bf16_hc and N_importance > 0 and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
         out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), lean=lean)
     elif bf16_fc and 0 < N_importance <= _FUSED_MAX and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
@@ -219,7 +220,7 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         # general path: the same HIP kernels, un-fused (posenc -> MLP -> compositing -> sample_pdf/merge), for
         # sample counts beyond the fused kernel's LDS scratch and for args.pertubeCord (rendering.py:102-104)
         out = _render_unfused(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
-                              float(noise_std), jitter, int(chunk), train, precision)
+                              float(noise_std), jitter, int(chunk), train, precision, plan)
     else:
         tables = _linspace_tables(N_samples, N_importance, rays.device)
         out = ops.render_rays(coarse.packed_weights(precision), fine.packed_weights(precision) if fine is not None else None, rays,
