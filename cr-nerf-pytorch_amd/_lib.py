@@ -277,6 +277,13 @@ LEAN_COMPOSITE_SIGNATURES = {
     "crnerf_render_coarse_weights_f16": (i32, [ra, vp]),
     "crnerf_render_rays_lean_bf16_fine": (i32, [ra, vp]),
 }
+# One row per symbol of the companion header include/crnerf_lean_x.h (the lean render on the two fp32-accurate split cores: what lean=True runs on
+# under precision "f32x3", "f32h2" and "auto"), bound by the same loader; tests/test_lean_x_host.py holds it to that header's prototypes.
+LEAN_X_SIGNATURES = {
+    "crnerf_render_rays_lean_f32x3": (i32, [ra, vp]),
+    "crnerf_render_rays_lean_f32h2": (i32, [ra, vp]),
+    "crnerf_render_rays_lean_f32x3_repair": (i32, [ra, vp]),
+}
 
 
 class SweepDecodeArgs(ctypes.Structure):
@@ -297,8 +304,8 @@ SWEEP_SIGNATURES = {
     "crnerf_crossray_style_stats_f32": (i32, [vp, i32, i64, i64, pp, vp, vp, vp]),
     "crnerf_crossray_decode_multi_f32": (i32, [ctypes.POINTER(SweepDecodeArgs), vp]),
 }
-# The five tables as one read-only view, in the order load() binds them: every symbol the library must export.
-ALL_SIGNATURES = types.MappingProxyType({**SIGNATURES, **BLENDER_SIGNATURES, **LEAN_SIGNATURES, **LEAN_COMPOSITE_SIGNATURES, **SWEEP_SIGNATURES})
+# The six tables as one read-only view, in the order load() binds them: every symbol the library must export.
+ALL_SIGNATURES = types.MappingProxyType({**SIGNATURES, **BLENDER_SIGNATURES, **LEAN_SIGNATURES, **LEAN_COMPOSITE_SIGNATURES, **LEAN_X_SIGNATURES, **SWEEP_SIGNATURES})
 
 
 _lib = None
@@ -319,7 +326,7 @@ def load():
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in ALL_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_sweep.h
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_lean_x.h / crnerf_sweep.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

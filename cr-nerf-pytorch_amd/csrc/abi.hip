@@ -9,6 +9,7 @@
 #include "../../include/crnerf.h"
 #include "../../include/crnerf_blender.h"
 #include "../../include/crnerf_lean.h"
+#include "../../include/crnerf_lean_x.h"
 #include "../../include/crnerf_sweep.h"
 #include "crossray.h"
 #include "kernels.h"
@@ -435,6 +436,10 @@ int crnerf_render_coarse_weights_f32x3(const crnerf_render_args* a, void* stream
 int crnerf_render_coarse_weights_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::X3_REPAIR); }
 int crnerf_render_coarse_weights_f16(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, COARSE_WEIGHTS, Core::F16_PAIR); }
 int crnerf_render_rays_lean_bf16_fine(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN_BF16_FINE, Core::BF16_PAIR); }
+// include/crnerf_lean_x.h
+int crnerf_render_rays_lean_f32x3(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::X3); }
+int crnerf_render_rays_lean_f32h2(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::H2); }
+int crnerf_render_rays_lean_f32x3_repair(const crnerf_render_args* a, void* stream) { return render_entry(a, stream, LEAN, Core::X3_REPAIR); }
 
 size_t crnerf_packed_mlp_mixed_bytes(void) { return gemm_packed_bytes(); }
 size_t crnerf_mlp_train_mixed_acts_bytes(int64_t n) { return mlp_train_mixed_acts_bytes((long)n); }

@@ -93,8 +93,9 @@ int launch_sample_pdf_merge(const float* z_coarse, const float* weights_coarse, 
 enum class RenderMode {
   Full,            // coarse pass, sample_pdf + merge, fine pass
   FineOnly,        // crnerf_render_rays_bf16_fine: weights_coarse is an INPUT (rendered by another core); sample_pdf + merge + the fine pass only
-  Lean,            // crnerf_render_rays_lean_f32 (render_fused16.hip), _lean_bf16 / _lean_f16 (render_fused_bf16p.hip; include/crnerf_lean.h): trunk-only
-                   // coarse pass; writes feature_fine, depth_fine and (optional) z_fine only
+  Lean,            // crnerf_render_rays_lean_f32 (render_fused16.hip), _lean_bf16 / _lean_f16 (render_fused_bf16p.hip; include/crnerf_lean.h), _lean_f32x3 / _lean_f32h2 /
+                   // _lean_f32x3_repair (render_fused_x3.hip both builds; include/crnerf_lean_x.h): trunk-only coarse pass; writes feature_fine,
+                   // depth_fine and (optional) z_fine only; with `repair` the x3 launcher looks for a NaN in feature_fine[r][0]
   LeanFineOnly,    // crnerf_render_rays_lean_bf16_fine: the fine-only kernel without weights_fine
   CoarseWeights,   // crnerf_render_coarse_weights_* (include/crnerf_lean_composite.h; render_fused_x3.hip both builds, the fp16 pair core): Ni == 0, every
                    // tile walks the trunk, weights_coarse is the only output and carries the range mark (0x7fc00000 in [r][0]); with `repair` the x3
@@ -133,7 +134,7 @@ struct RenderArgs {
   float* noise_fine_out = nullptr;
   // crnerf_render_rays_f32x3_repair: only ray quads whose feature_coarse / feature_fine hold a NaN are rendered (again)
   int repair = 0;
-  // which render this is (RenderMode above); `repair` combines with Full and CoarseWeights
+  // which render this is (RenderMode above); `repair` combines with Full, CoarseWeights and (x3 core) Lean
   RenderMode mode = RenderMode::Full;
   // training twin (crnerf_render_rays_train_f32; all null for inference): saved activations + raw MLP outputs per pass
   void* train_acts_coarse = nullptr;   // crnerf_mlp_train_acts_bytes(R*Nc)

@@ -106,8 +106,21 @@ struct TrainHookX {
 // shorter pass), alpha, the scan and the weights are the full kernel's (composite_weight_tile), no feature or depth sum is formed and nothing but
 // weights_c is stored.  There is no feature_c row to carry a NaN, so the mark a repair launch looks for is the word 0x7fc00000 in weights_c[r][0]:
 // written behind the row by the h2 build for a ray with a tile whose range guard tripped, and for every ray when the pack carries the range flag.
+// LEAN (crnerf_render_rays_lean_f32x3 / _f32h2 / _f32x3_repair, include/crnerf_lean_x.h; Ni > 0, no draws, no hook): the render for a caller that
+// reads the fine image alone.  Pass 0 is the CW body's tile -- trunk walk, composite_weight_tile, the weights into the ray scratch only -- and
+// pass 1 the ordinary tile and composite_tile, so the pipe's stage count alternates per PASS (WeightPipeX stages0 / stages1).  Stored: feature_f,
+// depth_f and (optional) z_fine; weights_c, feature_c, depth_c and weights_f are never touched, not on the repair and pack-flag paths either.
+// The mark: with no coarse row to carry it, a ray whose coarse trunk walk tripped the h2 range guard comes back with its whole feature_f row and
+// its depth_f NaN (decided per wave in front of the one store sequence); the repair prologue tests feature_f[r][0] alone.
+// The mode rides on the hook's type (LeanHookX), so the existing instantiations keep their names.  The lean kernel is built in a unit of its own
+// (render_fused_lean_x3.hip / render_fused_lean_h2.hip: this file under CRNERF_X_LEAN_UNIT, which compiles that kernel and its launch alone): with
+// it in this unit hipcc allocates the registers of the five kernels below differently; without it they compile, instruction for instruction, as they
+// did before the lean kernel existed.
+struct LeanHookX : NoHookX {};
 template <bool RNG, class HOOK, bool CW = false>
 __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const HOOK hook) {
+  constexpr bool LEAN = std::is_same<HOOK, LeanHookX>::value;
+  static_assert(!LEAN || (!RNG && !CW), "the lean render: inference, draws as tensors");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* lds = (lds_char*)smem;
   const int lane = threadIdx.x & 63;
@@ -120,6 +133,7 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
     auto is_nan = [](float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; };
     bool bad;
     if constexpr (CW) bad = rr < a.R && __float_as_uint(a.weights_c[rr * Nc]) == 0x7fc00000u;
+    else if constexpr (LEAN) bad = rr < a.R && is_nan(a.feature_f[rr * FEAT_DIM]);
     else bad = rr < a.R && (is_nan(a.feature_c[rr * FEAT_DIM]) || (Ni > 0 && is_nan(a.feature_f[rr * FEAT_DIM])));
     if (!__syncthreads_or(bad)) return;
   }
@@ -132,6 +146,7 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
       const long rr = ((long)it * gridDim.x + blockIdx.x) * 4 + wave;
       if (rr < a.R && lane == 0) {
         if constexpr (CW) a.weights_c[rr * Nc] = __uint_as_float(0x7fc00000u);
+        else if constexpr (LEAN) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
         else {
           a.feature_c[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
           if (Ni > 0) a.feature_f[rr * FEAT_DIM] = __uint_as_float(0x7fc00000u);
@@ -153,6 +168,7 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
   const int tiles_c = (Nc + 31) >> 5, tiles_f = Ni > 0 ? (Nf + 31) >> 5 : 0;
   WeightPipeX pipe;
   if constexpr (CW) pipe.set_stream_frags(XTRUNK_FRAGS);
+  if constexpr (LEAN) pipe.set_stream_frags(XTRUNK_FRAGS, XSTREAM_FRAGS);   // coarse tiles walk the trunk, fine tiles the whole stream
   pipe.start(lds, a.packed0 + CONST_BYTES, a.packed1 + CONST_BYTES, tiles_c, tiles_c + tiles_f, lane, wave);
   xu32x4 cur[X_AHEAD];
   pipe.prime(cur);
@@ -193,6 +209,74 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
       if (RNG && a.z_coarse_out && ray_ok) a.z_coarse_out[r * Nc + n] = zv;
     }
     wave_lds_fence();
+
+    if constexpr (LEAN) {
+      // a tile's inputs: depths of this lane's sample and the next one, the xyz embedding
+      auto tile_inputs = [&](const lds_float* zsrc, int N, int tile, int& n, bool& valid, float& zn, float& znext, f32x16 (&pe)[3]) {
+        n = tile * 32 + p;
+        valid = n < N;
+        const int nc = valid ? n : N - 1;
+        zn = zsrc[nc];
+        znext = zsrc[nc + 1 < N ? nc + 1 : N - 1];
+        const float x = ox + dx * zn, y = oy + dy * zn, z = oz + dz * zn;   // rendering.py:178 / :188 (separate mul and add)
+        float tmp[48];
+        posenc_regs<XYZ_FREQS, 24>(x, y, z, h, tmp);
+#pragma unroll
+        for (int i = 0; i < 48; ++i) pe[i / 16][i % 16] = tmp[i];
+      };
+      bool tripped;   // wave-uniform: a coarse tile of this ray left fp16's range (h2)
+      {               // pass 0, the CW body's tile: the coarse weights into the ray scratch, nothing into HBM
+        const float* noise_row = a.noise_c ? a.noise_c + r * Nc : nullptr;
+        double t_carry = 1.0;
+        bool trip = false;
+#pragma unroll 1
+        for (int tile = 0; tile < tiles_c; ++tile) {
+          int n; bool valid; float zn, znext, sigma;
+          f32x16 pe[3], feat[2];
+          tile_inputs(scr.zc, Nc, tile, n, valid, zn, znext, pe);
+          mlp_tile_x3<NoSaveX, true>(pipe, 0, pe, dv, feat, sigma, h, cur, tm);
+          trip |= valid && __float_as_uint(sigma) == 0x7fc00000u;
+          const float noise = (noise_row && valid) ? noise_row[n] * a.noise_std : 0.0f;
+          const float w = composite_weight_tile(t_carry, sigma, noise, zn, znext, n == Nc - 1, valid, p);
+          if (valid && h == 0) scr.wc[n] = w;
+          tm.tick(T_COMPOSITE);
+        }
+        tripped = XNP == 2 && __ballot(trip) != 0ull;
+      }
+      wave_lds_fence();
+      sample_pdf_wave(scr, Nc, Ni, a.u ? a.u + r * a.u_stride : nullptr, lane);
+      merge_sort_wave(scr, Nc, Ni, lane);
+      if (a.z_fine && ray_ok)
+        for (int n = lane; n < Nf; n += 64) a.z_fine[r * Nf + n] = scr.zs[n];
+      tm.tick(T_RAYLEVEL);
+      {               // pass 1: the ordinary tile; the compositing state begins its life here
+        const float* noise_row = a.noise_f ? a.noise_f + r * Nf : nullptr;
+        CompositeState st;
+        st.reset();
+#pragma unroll 1
+        for (int tile = 0; tile < tiles_f; ++tile) {
+          int n; bool valid; float zn, znext, sigma;
+          f32x16 pe[3], feat[2];
+          tile_inputs(scr.zs, Nf, tile, n, valid, zn, znext, pe);
+          mlp_tile_x3(pipe, 1, pe, dv, feat, sigma, h, cur, tm);
+          const float noise = (noise_row && valid) ? noise_row[n] * a.noise_std : 0.0f;
+          composite_tile(st, feat, sigma, noise, zn, znext, n == Nf - 1, valid, p);
+          tm.tick(T_COMPOSITE);
+        }
+        composite_finish(st);
+        if (tripped) {   // the mark of the coarse side, in front of the one store sequence
+          const float poison = __uint_as_float(0x7fc00000u);
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) st.facc[t][i] = poison;
+          st.dacc = poison;
+        }
+        if (ray_ok) store_ray_feature(st, a.feature_f + r * FEAT_DIM, a.depth_f + r, p, h);
+      }
+      tm.tick(T_RAYLEVEL);
+      continue;
+    }
 
     // pass 0 = coarse model on zc, pass 1 = fine model on the merged zs; ONE copy of the MLP code
     const int npass = Ni > 0 ? 2 : 1;
@@ -269,6 +353,15 @@ __device__ __forceinline__ void render_rays_x3_body(const RenderParamsX a, const
   hook.publish_range(lds, Nc, Nf, Ni > 0 ? 2 : 1);
 }
 
+int launch_lean_kernel_x3(const RenderParamsX& k, int grid, size_t shmem, hipStream_t stream);   // the unit built with CRNERF_X_LEAN_UNIT
+
+#ifdef CRNERF_X_LEAN_UNIT
+__global__ __launch_bounds__(256, 1) void render_rays_lean_x3_kernel(RenderParamsX a) { render_rays_x3_body<false>(a, LeanHookX()); }
+
+int launch_lean_kernel_x3(const RenderParamsX& k, int grid, size_t shmem, hipStream_t stream) {
+  return launch_kernel(render_rays_lean_x3_kernel, "render_rays_lean_x3_kernel", grid, 256, shmem, stream, k);
+}
+#else
 __global__ __launch_bounds__(256, 1) void render_rays_x3_kernel(RenderParamsX a) { render_rays_x3_body<false>(a, NoHookX()); }
 __global__ __launch_bounds__(256, 1) void render_rays_x3_rng_kernel(RenderParamsX a) { render_rays_x3_body<true>(a, NoHookX()); }
 __global__ __launch_bounds__(256, 1) void render_rays_train_x3_kernel(RenderParamsX a, TrainHookX hook) { render_rays_x3_body<false>(a, hook); }
@@ -294,6 +387,12 @@ int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
     k.feature_c = k.depth_c = k.weights_f = k.feature_f = k.depth_f = k.z_fine = nullptr;
     return launch_kernel(render_coarse_weights_x3_kernel, "render_coarse_weights_x3_kernel", plan.grid, 256, shmem, stream, k);
   }
+  if (a.mode == RenderMode::Lean) {   // crnerf_render_rays_lean_f32x3 / _f32h2 / _f32x3_repair: the fine image only (abi.hip passes the other outputs as null)
+    if (a.Ni == 0) return set_error(-2, "render_rays_lean: N_importance must be > 0");
+    if (rngk || a.train_acts_coarse) return set_error(-3, "render_rays_lean: inference only, random draws come as tensors");
+    k.weights_c = k.feature_c = k.depth_c = k.weights_f = nullptr;
+    return launch_lean_kernel_x3(k, plan.grid, shmem, stream);
+  }
   if (a.train_acts_coarse) {   // training twin (crnerf_render_rays_train_f32x3 / _f32h2; repair: the rays the h2 twin poisoned, saved rows included)
     if (int rc = check_train_state("render_rays_train_f32x3", a)) return rc;
     if ((unsigned long long)a.R * (unsigned)(a.Nc + a.Ni) * 1024ull >= (unsigned long long)SAVEX_OOB)
@@ -307,9 +406,14 @@ int launch_render_rays_x3(const RenderArgs& a, hipStream_t stream) {
   }
   return launch_kernel(rngk ? render_rays_x3_rng_kernel : render_rays_x3_kernel, "render_rays_x3_kernel", plan.grid, 256, shmem, stream, k);
 }
+#endif   // CRNERF_X_LEAN_UNIT
 
 #ifdef CRNERF_TIMING
-#if CRNERF_X_NP == 2
+#if defined(CRNERF_X_LEAN_UNIT) && CRNERF_X_NP == 2
+extern "C" int crnerf_debug_read_timing_lean_h2(unsigned long long* host_out) {
+#elif defined(CRNERF_X_LEAN_UNIT)
+extern "C" int crnerf_debug_read_timing_lean_x3(unsigned long long* host_out) {
+#elif CRNERF_X_NP == 2
 extern "C" int crnerf_debug_read_timing_h2(unsigned long long* host_out) {
 #else
 extern "C" int crnerf_debug_read_timing_x3(unsigned long long* host_out) {

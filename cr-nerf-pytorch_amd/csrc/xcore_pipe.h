@@ -54,7 +54,7 @@ static_assert(X_RING >= 5 && X_PIECES * (X_RING - 3) + 8 <= 63 && LDS_SCRATCH_X 
 constexpr int X_AHEAD = XNP == 2 ? CRNERF_H2_AHEAD : 6;
 static_assert(X_AHEAD % XNP == 0 && X_AHEAD <= X_STAGE_FRAGS, "the queue holds whole piece groups and never reaches past the next stage");
 
-// WeightPipe of mlp_core.h for the split streams: stages_per_pass stages per pass, LDS-DMA as asm.  Protocol as there: stages c and c + 1 may be
+// WeightPipe of mlp_core.h for the split streams: stages0 stages per tile of model 0, stages1 per tile of model 1, LDS-DMA as asm.  Protocol as there: stages c and c + 1 may be
 // read; advance() -- after the last read of stage c has been issued -- waits until this wave's pieces of stage c + 2 have landed (counted
 // vmcnt) and barriers; the slot of stage c - 1 is then refilled with stage c + X_RING - 1 by four issue_piece() calls during stage c + 1.
 struct WeightPipeX {
@@ -62,10 +62,14 @@ struct WeightPipeX {
   const char* base[2];   // scalar: packed streams + this wave's 4 KiB column
   const char* pf_ptr;
   int pf_left, pf_pass, passes0, passes;
-  int stages_per_pass = XSTREAM_FRAGS / X_STAGE_FRAGS;   // stages per pass: forward stream (set_stream_frags() for another)
+  // stages per tile of model 0 (pf_pass < passes0) / of model 1: the forward stream (set_stream_frags() for another).  The lean render walks the
+  // trunk in its coarse tiles and the whole stream in its fine ones, so the count alternates within a launch; the read side does not care (slots
+  // are consumed in fetch order, and the queue's read-ahead across a tile end lands on stage 0 of the next tile whichever form it has).
+  int stages0 = XSTREAM_FRAGS / X_STAGE_FRAGS, stages1 = XSTREAM_FRAGS / X_STAGE_FRAGS;
   uint32_t pf_slot, rd_slot, rd_addr, lane16, lds_ring;
   int wave;   // scalar: this wave's index in the workgroup
-  __device__ __forceinline__ void set_stream_frags(int frags) { stages_per_pass = frags / X_STAGE_FRAGS; }   // before start()
+  __device__ __forceinline__ void set_stream_frags(int frags) { stages0 = stages1 = frags / X_STAGE_FRAGS; }   // before start(); both models
+  __device__ __forceinline__ void set_stream_frags(int frags0, int frags1) { stages0 = frags0 / X_STAGE_FRAGS; stages1 = frags1 / X_STAGE_FRAGS; }
 
   // piece i (0 .. X_PIECES - 1) of the stage being fetched: this wave's fragments X_PIECES * wave + i.  Piece 0 writes M0 (the LDS destination of
   // the wave's column of the slot); pieces 1.. reuse it with their instruction offset, which applies to both sides.  Nothing else in the kernels
@@ -81,8 +85,8 @@ struct WeightPipeX {
       pf_slot = (pf_slot + 1 == X_RING) ? 0u : pf_slot + 1;
       pf_ptr += X_STAGE_BYTES;
       if (--pf_left == 0) {
-        pf_left = stages_per_pass;
         pf_pass = (pf_pass + 1 == passes) ? 0 : pf_pass + 1;
+        pf_left = (pf_pass < passes0) ? stages0 : stages1;   // of the tile the fetch moves to
         pf_ptr = (pf_pass < passes0) ? base[0] : base[1];
       }
     }
@@ -99,7 +103,7 @@ struct WeightPipeX {
     passes0 = passes0_;
     passes = passes_;
     pf_pass = 0;
-    pf_left = stages_per_pass;
+    pf_left = (passes0 > 0) ? stages0 : stages1;
     pf_ptr = (passes0 > 0) ? base[0] : base[1];
     pf_slot = 0;
     rd_slot = 0;

@@ -154,7 +154,10 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     is crnerf_render_coarse_weights_f32h2 / _f16 with crnerf_render_coarse_weights_f32x3_repair behind it -- trunk-only tiles, weights_coarse its
     only output, bit-identical to the ordinary coarse launch's -- and the fine launch crnerf_render_rays_lean_bf16_fine, which writes no weights_fine
     (include/crnerf_lean_composite.h); a ray that leaves fp16's range in the coarse HEAD layers only is no longer re-rendered on x3, and does not need
-    to be: the head does not reach the weights.  Every other case renders as without the flag and drops the other keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
+    to be: the head does not reach the weights.  "f32x3", "f32h2" and "auto" (no pertubeCord, the same sample counts; perturb > 0 is fine, the
+    draws arrive as tensors): ops.render_rays_lean_x -- crnerf_render_rays_lean_f32x3 / _f32h2, under "auto" the h2 entry with
+    crnerf_render_rays_lean_f32x3_repair behind it (include/crnerf_lean_x.h); "f32h2": a ray whose coarse trunk walk left fp16's range has a NaN
+    feature / depth, which "auto" renders again on x3 like every NaN row.  Every other case renders as without the flag and drops the other keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
     args = kwargs['args']
     jitter = bool(getattr(args, 'pertubeCord', False))
     if getattr(args, 'nerf_out_dim', 64) != 64:
@@ -221,6 +224,11 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
         # sample counts beyond the fused kernel's LDS scratch and for args.pertubeCord (rendering.py:102-104)
         out = _render_unfused(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
                               float(noise_std), jitter, int(chunk), train, precision, plan)
+    elif lean and precision in ("f32x3", "f32h2", "auto") and N_samples >= 3:
+        tables = _linspace_tables(N_samples, N_importance, rays.device)
+        out = ops.render_rays_lean_x(coarse.packed_weights(precision), fine.packed_weights(precision), rays, N_samples, N_importance,
+                                     precision=precision, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse, z_steps=tables[0],
+                                     u=u if u is not None else tables[1], noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std))
     else:
         tables = _linspace_tables(N_samples, N_importance, rays.device)
         out = ops.render_rays(coarse.packed_weights(precision), fine.packed_weights(precision) if fine is not None else None, rays,

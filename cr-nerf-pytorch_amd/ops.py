@@ -647,6 +647,38 @@ def render_coarse_weights(packed_coarse, rays, n_samples, precision="auto", use_
                    noise_std, use_disp, int(n_samples), 0)
 
 
+_LEAN_X = {"f32x3": "crnerf_render_rays_lean_f32x3", "f32h2": "crnerf_render_rays_lean_f32h2"}      # include/crnerf_lean_x.h
+
+
+def render_rays_lean_x(packed_coarse, packed_fine, rays, n_samples, n_importance, precision="auto", use_disp=False, view_dir=None, z_coarse=None,
+                       z_steps=None, u=None, noise_coarse=None, noise_fine=None, noise_std=0.0, want_z_fine=False, launcher=False):
+    """The lean render on the fp32-accurate split cores (crnerf_render_rays_lean_f32x3 / _f32h2 / _f32x3_repair, include/crnerf_lean_x.h):
+    {"feature_fine", "depth_fine"[, "z_fine"]}, bit-identical to render_rays(..., precision=...)'s -- the coarse tiles stop behind static_sigma, no
+    coarse feature or depth is composited, and nothing else is allocated or written.  Inference only; random draws come as tensors.
+    precision "f32x3" / "f32h2": that core, packs as for render_rays.  "f32h2" has no feature_coarse row to carry the range guard's NaN: a ray whose
+    coarse trunk walk left fp16's range comes back with its whole feature_fine row and its depth_fine NaN.  "auto" (AutoPacks): the h2 entry, then
+    crnerf_render_rays_lean_f32x3_repair on the same block, which renders the ray quads with a NaN feature_fine[r, 0] again, lean, on the x3 core
+    and leaves at once where there is none; a refused h2 pack: the x3 entry throughout."""
+    name = resolve(precision)
+    if name != "auto" and name not in _LEAN_X:
+        raise ValueError("crnerf_amd: render_rays_lean_x exists for precision='f32x3', 'f32h2' and 'auto' (render_rays(..., lean=True) has the "
+                         "others), got %r" % (name,))
+    Nc, Ni = int(n_samples), int(n_importance)
+    if Ni <= 0:
+        raise ValueError("crnerf_amd: render_rays_lean_x needs n_importance > 0 (it returns the fine pass only)")
+    if not 3 <= Nc <= 256 or Ni > 256:
+        raise ValueError("crnerf_amd: render_rays_lean_x is the fused kernel's: n_samples in [3, 256] and n_importance in [1, 256], got %d + %d" % (Nc, Ni))
+    if packed_coarse is None or packed_fine is None:
+        raise ValueError("crnerf_amd: render_rays_lean_x needs both models' packs")
+    name, packs, repair = _resolve_packs(name, (packed_coarse, packed_fine), None)
+    lib = _lib.load()
+    shapes = [("feature_fine", (64,)), ("depth_fine", ())] + ([("z_fine", (Nc + Ni,))] if want_z_fine else [])
+    checks = [(name, packs[0]), (name, packs[1])] + ([("f32x3", repair[0]), ("f32x3", repair[1])] if repair else [])
+    return _render(lib, _LEAN_X[name], "crnerf_render_rays_lean_f32x3_repair", checks, packs, repair, rays, shapes,
+                   {"view_dir": view_dir, "z_coarse": z_coarse, "z_steps": z_steps, "u": u, "noise_coarse": noise_coarse, "noise_fine": noise_fine},
+                   noise_std, use_disp, Nc, Ni, None, launcher)
+
+
 def render_rays_bf16_fine(packed_fine_bf16, rays, weights_coarse, n_samples, n_importance, use_disp=False, view_dir=None, z_coarse=None, z_steps=None, u=None,
                           noise_fine=None, noise_std=0.0, want_z_fine=False, lean=False):
     """crnerf_render_rays_bf16_fine: sample_pdf + z merge on `weights_coarse` [R,Nc] (rendered by another core, e.g. render_rays(..., n_importance=0,

@@ -48,7 +48,8 @@ CSRC = os.path.join(ROOT, "cr-nerf-pytorch_amd", "csrc")
 # the units whose kernels carry hand-written streams (inline-asm VALU / LDS-DMA / waits next to builtin MFMAs)
 AUDITED_UNITS = ["render_fused_h2.hip", "mlp_forward_h2.hip", "mlp_backward_h2.hip", "render_fused_x3.hip", "mlp_forward_x3.hip",
                  "mlp_backward_x3.hip", "mlp_train16.hip", "render_fused16.hip", "mlp_forward16.hip", "render_fused_bf16p.hip",
-                 "mlp_forward_bf16p.hip", "render_fused_bf16p_f16.hip", "mlp_forward_bf16p_f16.hip"]
+                 "mlp_forward_bf16p.hip", "render_fused_bf16p_f16.hip", "mlp_forward_bf16p_f16.hip", "render_fused_lean_h2.hip",
+                 "render_fused_lean_x3.hip"]
 
 MFMA_PASSES = {  # opcode prefix -> (passes, is_xdl)
     "v_mfma_f32_32x32x16_f16": (8, True), "v_mfma_f32_32x32x16_bf16": (8, True),
