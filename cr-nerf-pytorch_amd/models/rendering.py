@@ -1,13 +1,15 @@
 """render_rays_cross_ray with the reference's signature (models/rendering.py:50-63) on the fused HIP
 renderer.  Callers: train_mask_grid_sample.py:185-197, eval.py:39-52,
 appearance_modification_video.py:82-95 -- all pass the first 11 arguments positionally."""
+from typing import NamedTuple
+
 import torch
 
 from .. import ops
-from ..precision import resolve
+from ..precision import COMPOSITE, resolve
 from .nerf import NeRF_sigma, PosEmbedding
 
-__all__ = ['render_rays_cross_ray']
+__all__ = ['render_rays_cross_ray', 'render_route', 'RenderRoute']
 
 _FUSED_MAX = 256
 
@@ -84,7 +86,7 @@ def _render_unfused(coarse, fine, rays, Nc, Ni, use_disp, view_dir, z_coarse, u,
 _warned_f16_refused = [False]
 
 
-def _render_bf16_composite(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, want_z_fine=False, lean=False, f16_coarse=False):
+def _render_bf16_composite(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise_c, noise_f, noise_std, route, want_z_fine=False):
     """precision="bf16_hc" (inference, perturb = 0): the COARSE pass in fp32 accuracy on the fp16 matrix cores (precision "auto": f32h2 with the
     f32x3 safety net; 25 % of the points), the FINE pass on the bf16 matrix cores.  Why: bf16's end-to-end pixel error on a trained checkpoint is
     sampling sensitivity -- bf16 coarse weights move the fine depths (weights_fine rel-L2 2.8e-2, tests/test_gpu_trained_ckpt.py) -- so with
@@ -92,18 +94,18 @@ def _render_bf16_composite(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise
     Two fused launches (+ the repair kernel that leaves at once): the coarse-only render on the h2 core, then crnerf_render_rays_bf16_fine --
     sample_pdf, merge, embedding, fine MLP and compositing in one kernel on the coarse weights (round 6; rounds 4-5 ran five un-fused calls with
     the [P,120] embeddings and [P,65] raw rows through HBM: 297 ms per 800 x 800 frame).
-    f16_coarse: precision="bf16_fc", the same with the coarse pass on ONE-PIECE FP16 operands -- one MFMA per product like bf16 instead of the h2
+    route.f16_coarse: precision="bf16_fc", the same with the coarse pass on ONE-PIECE FP16 operands -- one MFMA per product like bf16 instead of the h2
     core's three, 11 significand bits instead of bf16's 8: the coarse weights, and with them the fine depths, land ~7x closer to fp32's than bf16's
     do (tests/test_gpu_f16_trained.py) at bf16's cost.  Three launches: the coarse-only crnerf_render_rays_f16, crnerf_render_rays_f32x3_repair over
     its outputs (re-renders the ray quads the fp16 range guard poisoned; leaves at once otherwise -- so the mode returns no NaN that "f32" would
     not), crnerf_render_rays_bf16_fine on those coarse weights.  A coarse model whose weights do not fit fp16 (the pack refuses them) takes
     bf16_hc's coarse pass instead; said once in a warning.
-    lean: the caller reads the fine image alone.  The coarse launch becomes ops.render_coarse_weights (crnerf_render_coarse_weights_f32h2 / _f16 + the
+    route.lean_launch: the caller reads the fine image alone.  The coarse launch becomes ops.render_coarse_weights (crnerf_render_coarse_weights_f32h2 / _f16 + the
     x3 repair: every tile stops behind the sigma head, weights_coarse is all it writes, bit-identical to the ordinary launch's) and the fine launch
     crnerf_render_rays_lean_bf16_fine (no weights_fine); the dict holds feature_fine, depth_fine and (want_z_fine) z_fine."""
     # how the coarse pass is obtained: its precision, its pack and (f16) the x3 pack of the repair behind it
     precision, pk, repair = "auto", None, None
-    if f16_coarse:
+    if route.f16_coarse:
         try:
             precision, pk = "f16", coarse.packed_weights("f16")
         except ops.PackRangeError:
@@ -118,15 +120,56 @@ def _render_bf16_composite(coarse, fine, rays, Nc, Ni, use_disp, view_dir, noise
     else:
         repair = coarse.packed_weights("f32x3")
     kw = dict(use_disp=use_disp, z_steps=z_steps, noise_coarse=noise_c, noise_std=float(noise_std), precision=precision)
-    if lean:
+    if route.lean_launch:
         out = {}
         wc = ops.render_coarse_weights(pk, rays, Nc, repair_x3=repair, **kw)["weights_coarse"]
     else:     # (view_dir: the full launch also composites feature_coarse)
         out = ops.render_rays(pk, None, rays, Nc, 0, view_dir=view_dir, repair_x3=None if repair is None else (repair, None), **kw)
         wc = out["weights_coarse"]
     out.update(ops.render_rays_bf16_fine(fine.packed_weights("bf16"), rays, wc, Nc, Ni, use_disp=use_disp, view_dir=view_dir, z_steps=z_steps, u=u_steps,
-                                         noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine, lean=lean))
+                                         noise_fine=noise_f, noise_std=float(noise_std), want_z_fine=want_z_fine, lean=route.lean_launch))
     return out
+
+
+class RenderRoute(NamedTuple):
+    """Which launch a render_rays_cross_ray call gets -- everything its dispatch reads (render_route)."""
+    path: str            # "train_fused" | "composite" | "unfused" | "lean_x" | "fused": a row of render_rays_cross_ray's table
+    precision: str       # the name the packs and launchers are handed
+    lean: bool           # the caller reads the fine image alone: the result holds nothing else
+    lean_launch: bool    # ... and the launch itself is lean (False under lean: rendered in full, the rest dropped)
+    f16_coarse: bool     # "composite": the coarse pass on one-piece fp16 operands ("bf16_fc")
+    kernel_draws: bool   # jitter / sample_pdf uniforms / density noise are drawn in the kernel (csrc/philox.h), not handed over as tensors
+
+
+def _fits_fused(n_samples, n_importance, short=False):
+    """The fused kernels' sample counts (their LDS scratch; sample_pdf needs three coarse samples).  short: N_samples < 3 is accepted as well."""
+    return (short or n_samples >= 3) and n_samples <= _FUSED_MAX and n_importance <= _FUSED_MAX
+
+
+def render_route(precision, train, plan, jitter, perturb, noise_std, n_samples, n_importance, lean, in_kernel_rng):
+    """The RenderRoute of a call, from plain values alone: precision -- its canonical name (crnerf_amd.precision.resolve); train -- grad mode with
+    trainable models; plan -- autograd.training_plan()'s answer (read only when train); jitter -- args.pertubeCord; in_kernel_rng -- what
+    ops.in_kernel_rng() answers.  Every sample-count rule that is not _fits_fused() as it stands carries its reason."""
+    lean = lean and n_importance > 0        # without a fine pass the flag means nothing
+    if train:                               # grad mode does not read the precision setting (crnerf_amd.set_precision): the plan decides
+        # short: the training twin runs sample_pdf only when there is a fine pass
+        fusable = not jitter and _fits_fused(n_samples, n_importance, short=n_importance == 0)
+        fused_f32 = fusable and plan.family == "f32"
+        if fused_f32 or (fusable and (plan.recompute or plan.bf16_fused)):
+            # only the fp32 family's training kernel draws for itself
+            return RenderRoute("train_fused", "f32", False, False, False, fused_f32 and (perturb > 0 or noise_std != 0) and in_kernel_rng)
+        return RenderRoute("unfused", "f32", False, False, False, False)
+    if precision in COMPOSITE and n_importance > 0 and perturb == 0 and not jitter:
+        # "bf16_hc" does not bound N_importance although its fine launch does -- a defect (ADVICE.md), kept as it is: N_importance > 256 is refused
+        # by ops.render_rays_bf16_fine where "bf16_fc" one line on renders un-fused
+        if _fits_fused(n_samples, 0 if precision == "bf16_hc" else n_importance):
+            return RenderRoute("composite", "bf16", lean, lean, precision == "bf16_fc", False)
+    if precision in COMPOSITE:              # outside their applicability the composite modes take the path plain "bf16" takes
+        precision = "bf16"
+    if jitter or not _fits_fused(n_samples, n_importance, short=True):      # short: the un-fused path is for counts beyond the scratch, not below it
+        return RenderRoute("unfused", precision, lean, False, False, False)
+    lean_launch = lean and _fits_fused(n_samples, n_importance)             # the full entries render N_samples < 3, the lean entries do not
+    return RenderRoute("lean_x" if lean_launch and precision in ("f32x3", "f32h2", "auto") else "fused", precision, lean, lean_launch, False, False)
 
 
 def _check_embedding(emb, n_freqs, what):
@@ -135,29 +178,55 @@ def _check_embedding(emb, n_freqs, what):
                                   "the embedding in registers and cannot call an arbitrary Python callable" % (what, n_freqs - 1, n_freqs))
 
 
+def _results(out, coarse, fine, route, output_random):
+    """The reference's result names (models/rendering.py:140-141,192) for a launch dict; route.lean: the fine image alone."""
+    typ = coarse.typ
+    results = {} if route.lean else {'weights_%s' % typ: out['weights_coarse'], 'feature_%s' % typ: out['feature_coarse'],
+                                     'depth_%s' % typ: out['depth_coarse']}
+    if fine is not None:
+        if not route.lean:
+            results['weights_%s' % fine.typ] = out['weights_fine']
+        results['feature_%s' % fine.typ] = out['feature_fine']
+        if output_random and fine.encode_random:
+            results['feature_fine_random'] = out['feature_fine']         # the SAME tensor object, as in the reference
+        results['depth_%s' % fine.typ] = out['depth_fine']
+    return results
+
+
 def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=False, perturb=0, noise_std=1,
                           N_importance=0, chunk=1024 * 32, white_back=False, test_time=False, **kwargs):
-    """Same contract as the reference: returns weights_/feature_/depth_ for 'coarse' and, when
-    N_importance > 0, 'fine' (+ 'feature_fine_random', the SAME tensor object as 'feature_fine',
-    models/rendering.py:140-141,192).  ts / white_back / test_time / chunk are accepted and, as in the
+    """Same contract as the reference: returns weights_/feature_/depth_ for 'coarse' and, when N_importance > 0, 'fine' (+ 'feature_fine_random', the
+    SAME tensor object as 'feature_fine', models/rendering.py:140-141,192).  ts / white_back / test_time / chunk are accepted and, as in the
     reference's arithmetic, do not influence the result (the MLP is point-wise, so chunking is invisible).
-    One keyword beyond the reference's: precision="f32"|"bf16"|"f32x3"|"f32h2"|"auto"|"bf16_hc"|"bf16_fc"|"f16" (default crnerf_amd.get_precision()) selects the
-    matrix-core arithmetic of NeRF_sigma at inference (include/crnerf.h).  Grad mode trains through the exact-fp32 twins unless
-    the caller opted into mixed precision (autograd.set_training_precision("bf16") / CRNERF_TRAIN_BF16=1: bf16-operand GEMM twins,
-    fp32 accumulation; autograd.set_wgrad_precision("bf16"): weight gradients only) -- neither has a counterpart in the reference.
-    lean=True (another keyword of this mirror; inference only, ValueError in grad mode with trainable models): the caller reads the fine image alone.
-    With N_importance > 0 the result holds exactly feature_<fine.typ>, depth_<fine.typ> and (under its usual condition) feature_fine_random, with
-    the values of the ordinary call.  precision "f32", "bf16" or "f16" (and "bf16_hc" / "bf16_fc" where they fall back to plain "bf16"), no pertubeCord,
-    3 <= N_samples <= 256, N_importance <= 256: crnerf_render_rays_lean_f32 / _lean_bf16 / _lean_f16 -- the coarse pass stops behind the sigma head
-    and nothing of it goes to HBM ("f16": a ray whose coarse pass left fp16's range has a NaN feature / depth instead of the full call's NaN
-    feature_coarse row).  "bf16_hc" / "bf16_fc" on their own two-launch path (perturb = 0, no pertubeCord, the same sample counts): the coarse launch
-    is crnerf_render_coarse_weights_f32h2 / _f16 with crnerf_render_coarse_weights_f32x3_repair behind it -- trunk-only tiles, weights_coarse its
-    only output, bit-identical to the ordinary coarse launch's -- and the fine launch crnerf_render_rays_lean_bf16_fine, which writes no weights_fine
-    (include/crnerf_lean_composite.h); a ray that leaves fp16's range in the coarse HEAD layers only is no longer re-rendered on x3, and does not need
-    to be: the head does not reach the weights.  "f32x3", "f32h2" and "auto" (no pertubeCord, the same sample counts; perturb > 0 is fine, the
-    draws arrive as tensors): ops.render_rays_lean_x -- crnerf_render_rays_lean_f32x3 / _f32h2, under "auto" the h2 entry with
-    crnerf_render_rays_lean_f32x3_repair behind it (include/crnerf_lean_x.h); "f32h2": a ray whose coarse trunk walk left fp16's range has a NaN
-    feature / depth, which "auto" renders again on x3 like every NaN row.  Every other case renders as without the flag and drops the other keys.  N_importance == 0: the flag means nothing, the ordinary result comes back.  Not tied to test_time, which every inference caller sets."""
+    Keywords beyond the reference's: precision (a name of crnerf_amd.precision, default crnerf_amd.get_precision()): the matrix-core arithmetic of
+    NeRF_sigma at inference; view_dir; output_random; rng_ray_offset (below); lean=True: the caller reads the fine image alone -- the result holds
+    exactly feature_<fine.typ>, depth_<fine.typ> and (under its usual condition) feature_fine_random, with the values of the ordinary call; inference
+    only (ValueError in grad mode with trainable models), meaningless with N_importance == 0, not tied to test_time, which every inference caller sets.
+    Grad mode with trainable models reads autograd.training_plan() instead of the precision.
+
+    The launch a call gets -- render_route() decides, first match wins; "counts fit": 3 <= N_samples <= 256 and N_importance <= 256:
+
+    | route       | condition                                             | launch                                        | entries documented in           | a lean call                |
+    |-------------|-------------------------------------------------------|-----------------------------------------------|---------------------------------|----------------------------|
+    | train_fused | grad mode, no pertubeCord, counts fit (N_samples < 3  | autograd.fused_render_with_grad: one autograd | autograd.FusedRenderFn,         | is refused: ValueError     |
+    |             | too when N_importance == 0); plan: f32 family,        | node per ray chunk                            | include/crnerf.h                |                            |
+    |             | recompute or bf16 fused                               |                                               |                                 |                            |
+    | unfused     | grad mode otherwise                                   | _render_unfused on the autograd twins         | autograd.py                     | is refused: ValueError     |
+    | composite   | "bf16_hc" / "bf16_fc", N_importance > 0, perturb == 0,| _render_bf16_composite: ops.render_rays       | include/crnerf.h,               | ops.render_coarse_weights, |
+    |             | no pertubeCord, counts fit ("bf16_hc": N_importance   | (coarse only), ops.render_rays_bf16_fine      | include/crnerf_lean_composite.h | the fine launch lean       |
+    |             | not bounded, ADVICE.md)                               |                                               |                                 |                            |
+    | unfused     | pertubeCord, N_samples > 256 or N_importance > 256    | _render_unfused on ops.mlp_forward            | include/crnerf.h                | renders in full, drops     |
+    | lean_x      | lean, "f32x3" / "f32h2" / "auto", N_samples >= 3      | ops.render_rays_lean_x                        | include/crnerf_lean_x.h         | is what this row is for    |
+    | fused       | everything else ("bf16_hc" / "bf16_fc" as "bf16")     | ops.render_rays                               | include/crnerf.h,               | lean=True; N_samples < 3:  |
+    |             |                                                       |                                               | include/crnerf_lean.h           | renders in full, drops     |
+
+    What an entry does with NaN rows and fp16's range guard is said where the entry is: the docstrings of ops.render_rays, ops.render_rays_lean_x,
+    ops.render_coarse_weights, ops.render_rays_bf16_fine and _render_bf16_composite, and the headers above.
+    Random inputs (perturb > 0: stratified coarse depths and sample_pdf's uniforms; noise_std != 0: density noise) are torch draws handed on as tensors,
+    except where the route says kernel_draws (train_fused on the f32 plan with ops.in_kernel_rng()): then the only draw is the Philox seed, from torch's
+    CPU generator, so torch.manual_seed() governs the run either way.  rng_ray_offset: the index of rays[0] in the caller's whole batch -- the kernel's
+    draws are keyed on (seed, GLOBAL ray, sample), so a batch rendered in ray chunks or sharded over ranks (pipeline.TrainingSystem) draws what one
+    call over all of it would."""
     args = kwargs['args']
     jitter = bool(getattr(args, 'pertubeCord', False))
     if getattr(args, 'nerf_out_dim', 64) != 64:
@@ -173,85 +242,45 @@ def render_rays_cross_ray(models, embeddings, rays, ts, N_samples=64, use_disp=F
     lean = bool(kwargs.get('lean', False))
     if lean and train:
         raise ValueError("crnerf_amd: lean=True is an inference render; call it under torch.no_grad() (or with frozen models)")
-    lean = lean and N_importance > 0
     precision = kwargs.get('precision', None)
     if precision is None:
         from .. import get_precision
         precision = get_precision()
-    name = "f32" if train else resolve(precision, composite=True)      # grad mode does not read the setting (crnerf_amd.set_precision)
-    bf16_hc, bf16_fc = name == "bf16_hc", name == "bf16_fc"
-    # outside their applicability (below) the composite modes take the path plain "bf16" takes
-    # ("f16": both passes on fp16 operands through the fused kernel, NaN rows where a point leaves fp16's range; the un-fused path has no repair either)
-    precision = "bf16" if (bf16_hc or bf16_fc) else name
+    from ..autograd import fused_render_with_grad, training_plan
+    plan = training_plan() if train else None      # the training settings, asked once: this call's nodes run as it says, forward and backward
+    route = render_route("f32" if train else resolve(precision, composite=True), train, plan, jitter, perturb, noise_std, N_samples, N_importance, lean,
+                         train and ops.in_kernel_rng())      # (asked in grad mode only: no inference launch draws for itself)
 
     rays = rays.to(torch.float32).contiguous()
     R = rays.shape[0]
     view_dir = kwargs.get('view_dir', None)
-    z_coarse = u = noise_c = noise_f = None
-    from ..autograd import fused_render_with_grad, training_plan
-    plan = training_plan() if train else None      # the training settings, asked once: this call's nodes run as it says, forward and backward
-    fusable = train and not jitter and N_samples <= _FUSED_MAX and N_importance <= _FUSED_MAX and (N_importance == 0 or N_samples >= 3)
-    fused_train = fusable and plan.family == "f32"
-    rng = None
-    if fused_train and (perturb > 0 or noise_std != 0) and ops.in_kernel_rng():
-        # the fused fp32 training kernel draws the jitter / sample_pdf uniforms / density noise itself (csrc/philox.h): no [R,N] random
-        # tensors, no launches for them.  The seed comes from torch's CPU generator, so torch.manual_seed() governs the run.
-        # rng_ray_offset (kwarg of this mirror only): the index of rays[0] in the caller's whole batch -- the draws are keyed on (seed, GLOBAL ray,
-        # sample), so a batch rendered in ray chunks or sharded over ranks (pipeline.TrainingSystem) draws what one call over all of it would
+    noise_std = float(noise_std)
+    rng = z_coarse = u = noise_c = noise_f = None
+    if route.kernel_draws:
         rng = {"seed": int(torch.randint(0, 2 ** 62, (1,), device="cpu")), "perturb": float(perturb), "jitter": perturb > 0, "u": perturb > 0,
                "noise": noise_std != 0, "ray_offset": int(kwargs.get("rng_ray_offset", 0))}
-    if rng is None and perturb > 0:
-        z_coarse = _coarse_depths(rays, N_samples, use_disp, perturb)
-        if N_importance > 0:
-            u = torch.rand(R, N_importance, device=rays.device)
-    if noise_std != 0 and rng is None:
-        noise_c = torch.randn(R, N_samples, device=rays.device)
-        if N_importance > 0:
-            noise_f = torch.randn(R, N_samples + N_importance, device=rays.device)
-
-    if fusable and (fused_train or plan.recompute or plan.bf16_fused):
-        # training: the fused renderer's training twin (one launch per ray chunk: posenc + MLPs + activation save + compositing +
-        # sample_pdf/merge) as one autograd node whose backward runs the HIP backward twins (autograd.FusedRenderFn)
-        out = fused_render_with_grad(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
-                                     float(noise_std), rng=rng, plan=plan)
-    elif bf16_hc and N_importance > 0 and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
-        out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), lean=lean)
-    elif bf16_fc and 0 < N_importance <= _FUSED_MAX and perturb == 0 and not jitter and 3 <= N_samples <= _FUSED_MAX:
-        out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, float(noise_std), lean=lean,
-                                     f16_coarse=True)
-    elif train or N_samples > _FUSED_MAX or N_importance > _FUSED_MAX or jitter:
-        # general path: the same HIP kernels, un-fused (posenc -> MLP -> compositing -> sample_pdf/merge), for
-        # sample counts beyond the fused kernel's LDS scratch and for args.pertubeCord (rendering.py:102-104)
-        out = _render_unfused(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f,
-                              float(noise_std), jitter, int(chunk), train, precision, plan)
-    elif lean and precision in ("f32x3", "f32h2", "auto") and N_samples >= 3:
-        tables = _linspace_tables(N_samples, N_importance, rays.device)
-        out = ops.render_rays_lean_x(coarse.packed_weights(precision), fine.packed_weights(precision), rays, N_samples, N_importance,
-                                     precision=precision, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse, z_steps=tables[0],
-                                     u=u if u is not None else tables[1], noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std))
     else:
-        tables = _linspace_tables(N_samples, N_importance, rays.device)
-        out = ops.render_rays(coarse.packed_weights(precision), fine.packed_weights(precision) if fine is not None else None, rays,
-                              N_samples, N_importance, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse,
-                              z_steps=tables[0], u=u if u is not None else tables[1],
-                              noise_coarse=noise_c, noise_fine=noise_f, noise_std=float(noise_std), precision=precision,
-                              lean=lean and precision in ("f32", "bf16", "f16") and N_samples >= 3)
+        if perturb > 0:
+            z_coarse = _coarse_depths(rays, N_samples, use_disp, perturb)
+            if N_importance > 0:
+                u = torch.rand(R, N_importance, device=rays.device)
+        if noise_std != 0:
+            noise_c = torch.randn(R, N_samples, device=rays.device)
+            if N_importance > 0:
+                noise_f = torch.randn(R, N_samples + N_importance, device=rays.device)
 
-    if lean:    # the lean kernel wrote nothing else; the other paths rendered as usual and their other tensors are dropped here
-        typ_f = fine.typ
-        results = {'feature_%s' % typ_f: out['feature_fine']}
-        if kwargs.get('output_random', True) and fine.encode_random:
-            results['feature_fine_random'] = out['feature_fine']
-        results['depth_%s' % typ_f] = out['depth_fine']
-        return results
-    typ_c = coarse.typ
-    results = {'weights_%s' % typ_c: out['weights_coarse'], 'feature_%s' % typ_c: out['feature_coarse'],
-               'depth_%s' % typ_c: out['depth_coarse']}
-    if N_importance > 0:
-        typ_f = fine.typ
-        results['weights_%s' % typ_f] = out['weights_fine']
-        results['feature_%s' % typ_f] = out['feature_fine']
-        if kwargs.get('output_random', True) and fine.encode_random:
-            results['feature_fine_random'] = out['feature_fine']
-        results['depth_%s' % typ_f] = out['depth_fine']
-    return results
+    if route.path == "train_fused":
+        out = fused_render_with_grad(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f, noise_std, rng=rng,
+                                     plan=plan)
+    elif route.path == "composite":
+        out = _render_bf16_composite(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, noise_c, noise_f, noise_std, route)
+    elif route.path == "unfused":
+        out = _render_unfused(coarse, fine, rays, N_samples, N_importance, use_disp, view_dir, z_coarse, u, noise_c, noise_f, noise_std, jitter,
+                              int(chunk), train, route.precision, plan)
+    else:
+        z_steps, u_steps = _linspace_tables(N_samples, N_importance, rays.device)
+        render, flag = (ops.render_rays_lean_x, {}) if route.path == "lean_x" else (ops.render_rays, {"lean": route.lean_launch})
+        out = render(coarse.packed_weights(route.precision), fine.packed_weights(route.precision) if fine is not None else None, rays, N_samples,
+                     N_importance, precision=route.precision, use_disp=use_disp, view_dir=view_dir, z_coarse=z_coarse, z_steps=z_steps,
+                     u=u if u is not None else u_steps, noise_coarse=noise_c, noise_fine=noise_f, noise_std=noise_std, **flag)
+    return _results(out, coarse, fine, route, kwargs.get('output_random', True))

@@ -114,7 +114,7 @@ def render_frame(models, embeddings, enc_a, style_img, H, W, K, c2w, hparams_, n
     a_emb: a precomputed enc_a(style_img) -- the reference encodes the style image ONCE per video (:216-222), so frame loops
     pass it in instead of re-running the encoder per frame.
     lean=True: render_rays_cross_ray(..., lean=True) -- only what the fine image needs is computed and returned; same pixels
-    (every precision has its lean launches: "f32", "bf16", "f16", "bf16_hc", "bf16_fc" and, through ops.render_rays_lean_x, "f32x3", "f32h2", "auto")."""
+    (every precision has its lean launches; which one a call gets is a row of the table in render_rays_cross_ray's docstring)."""
     if a_emb is None:
         a_emb = enc_a(style_img)
     rays = generate_rays(H, W, K, c2w, near, far, device=style_img.device)

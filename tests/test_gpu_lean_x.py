@@ -234,3 +234,33 @@ def test_mirror_takes_the_lean_entries_and_returns_the_full_values(scene, precis
     assert bool(torch.isfinite(full["feature_fine"]).all())
     for k in LEAN_KEYS:
         assert torch.equal(lean[k], full[k]), k
+
+
+@torch.no_grad()
+@pytest.mark.parametrize("lean", [False, True])
+@pytest.mark.parametrize("precision", ["f32", "auto"])
+def test_mirror_hands_on_the_draws_it_makes(scene, precision, lean):
+    """The draws the mirror makes on the device -- _coarse_depths, u, noise_c, noise_f, in that order -- are the tensors its launch gets: drawn again
+    from the same seed and handed to the entry the route names, they give the same bits.  Six rays: two ray quads, the second partial."""
+    from crnerf_amd.models import rendering
+    args, models, emb = scene
+    R, nc, ni = 6, 5, 4
+    rays = K.C(K.synth.rays(R, seed=5, H=2, W=3))
+    torch.manual_seed(0)
+    got = rendering.render_rays_cross_ray(models, emb, rays, None, nc, False, 1, 1, ni, 4096, False, test_time=True, args=args, precision=precision, lean=lean)
+    torch.manual_seed(0)
+    z = rendering._coarse_depths(rays, nc, False, 1)
+    u = torch.rand(R, ni, device=rays.device)
+    noise_c = torch.randn(R, nc, device=rays.device)
+    noise_f = torch.randn(R, nc + ni, device=rays.device)
+    launch = dict(precision=precision, z_coarse=z, z_steps=torch.linspace(0, 1, nc, device=rays.device), u=u, noise_coarse=noise_c, noise_fine=noise_f,
+                  noise_std=1.0)
+    packs = [models[k].packed_weights(precision) for k in ("coarse", "fine")]
+    if lean and precision == "auto":
+        want = ops.render_rays_lean_x(*packs, rays, nc, ni, **launch)
+    else:
+        want = ops.render_rays(*packs, rays, nc, ni, lean=lean, **launch)
+    torch.cuda.synchronize()
+    assert list(got) == (LEAN_KEYS if lean else FULL_KEYS) and bool(torch.isfinite(got["feature_fine"]).all())
+    for k in got:
+        assert torch.equal(got[k], want["feature_fine" if k == "feature_fine_random" else k]), k
