@@ -306,6 +306,15 @@ SWEEP_SIGNATURES = {
 }
 # The six tables as one read-only view, in the order load() binds them: every symbol the library must export.
 ALL_SIGNATURES = types.MappingProxyType({**SIGNATURES, **BLENDER_SIGNATURES, **LEAN_SIGNATURES, **LEAN_COMPOSITE_SIGNATURES, **LEAN_X_SIGNATURES, **SWEEP_SIGNATURES})
+# One row per symbol of the companion header include/crnerf_geometry.h (the density query: sigma at points or on a grid, trunk-only walk).  A table
+# of its own that load() binds in a second loop and that is NOT folded into ALL_SIGNATURES: the size of that view is pinned by the tests of the
+# rounds that wrote it.  tests/test_geometry_host.py holds this one to its header's prototypes.
+GEOMETRY_SIGNATURES = {
+    "crnerf_sigma_points_f32": (i32, [vp, vp, vp, i64, vp]),
+    "crnerf_sigma_points_bf16": (i32, [vp, vp, vp, i64, vp]),
+    "crnerf_sigma_grid_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "crnerf_sigma_grid_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+}
 
 
 _lib = None
@@ -327,6 +336,10 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in ALL_SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_lean_x.h / crnerf_sweep.h
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in GEOMETRY_SIGNATURES.items():
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_geometry.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

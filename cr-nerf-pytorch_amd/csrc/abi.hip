@@ -8,6 +8,7 @@
 #include <string.h>
 #include "../../include/crnerf.h"
 #include "../../include/crnerf_blender.h"
+#include "../../include/crnerf_geometry.h"
 #include "../../include/crnerf_lean.h"
 #include "../../include/crnerf_lean_x.h"
 #include "../../include/crnerf_sweep.h"
@@ -155,6 +156,27 @@ static int forward_entry(const char* who, const void* packed, const float* x, fl
   REQUIRE(packed, "packed"); REQUIRE(x, "x"); REQUIRE(out, "out");
   if (n < 0) return fail(CRNERF_ERR_SHAPE, who, "negative n");
   return launch((long)n);
+}
+
+// every crnerf_sigma_points_* / crnerf_sigma_grid_* (include/crnerf_geometry.h): the kernels index points with 32 bits
+static const int64_t SIGMA_MAX_POINTS = 0x7fffffffLL;
+template <class Launch>
+static int sigma_points_entry(const void* packed, const float* xyz, float* sigma, int64_t n, Launch launch) {
+  if (n < 0) return fail(CRNERF_ERR_SHAPE, "sigma_points", "negative n");
+  if (n == 0) return 0;
+  REQUIRE(packed, "packed"); REQUIRE(xyz, "xyz"); REQUIRE(sigma, "sigma");
+  if (n > SIGMA_MAX_POINTS) return fail(CRNERF_ERR_SHAPE, "sigma_points", "more than 2^31 - 1 points in one call (split the list)");
+  return launch((long)n);
+}
+template <class Launch>
+static int sigma_grid_entry(const void* packed, const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma,
+                            Launch launch) {
+  if (nx < 0 || ny < 0 || nz < 0) return fail(CRNERF_ERR_SHAPE, "sigma_grid", "negative axis length");
+  if (nx == 0 || ny == 0 || nz == 0) return 0;
+  REQUIRE(packed, "packed"); REQUIRE(xs, "xs"); REQUIRE(ys, "ys"); REQUIRE(zs, "zs"); REQUIRE(sigma, "sigma");
+  // (nx * ny < 2^62, and the quotient test keeps the triple product out of 64-bit overflow)
+  if ((int64_t)nx * ny > SIGMA_MAX_POINTS / nz) return fail(CRNERF_ERR_SHAPE, "sigma_grid", "more than 2^31 - 1 points in one call (slabs of a grid are grids)");
+  return launch();
 }
 
 // the 22 decoder tensors in kernel order (CRNERF_DECODER_TENSORS); a backward entry leaves workspace, rgb and plane_stride null
@@ -574,6 +596,22 @@ int crnerf_pack_mlp_weights_bf16(const float* const* tensors, void* packed, void
 
 int crnerf_mlp_forward_bf16(const void* packed, const float* x, float* out, int64_t n, int sigma_only, void* stream) {
   return forward_entry("mlp_forward_bf16", packed, x, out, n, [&](long P) { return launch_mlp_forward_bf16p(packed, x, out, P, sigma_only, (hipStream_t)stream); });
+}
+
+// include/crnerf_geometry.h: the density query.  A launcher sees a point count in [1, 2^31 - 1] and no NULL pointer.
+int crnerf_sigma_points_f32(const void* packed, const float* xyz, float* sigma, int64_t n, void* stream) {
+  return sigma_points_entry(packed, xyz, sigma, n, [&](long P) { return launch_sigma_points16(packed, xyz, sigma, P, (hipStream_t)stream); });
+}
+int crnerf_sigma_points_bf16(const void* packed, const float* xyz, float* sigma, int64_t n, void* stream) {
+  return sigma_points_entry(packed, xyz, sigma, n, [&](long P) { return launch_sigma_points_bf16p(packed, xyz, sigma, P, (hipStream_t)stream); });
+}
+int crnerf_sigma_grid_f32(const void* packed, const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma,
+                          void* stream) {
+  return sigma_grid_entry(packed, xs, ys, zs, nx, ny, nz, sigma, [&] { return launch_sigma_grid16(packed, xs, ys, zs, nx, ny, nz, sigma, (hipStream_t)stream); });
+}
+int crnerf_sigma_grid_bf16(const void* packed, const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma,
+                           void* stream) {
+  return sigma_grid_entry(packed, xs, ys, zs, nx, ny, nz, sigma, [&] { return launch_sigma_grid_bf16p(packed, xs, ys, zs, nx, ny, nz, sigma, (hipStream_t)stream); });
 }
 
 size_t crnerf_packed_mlp_f16_bytes(void) { return PACKEDB_BYTES; }

@@ -169,6 +169,12 @@ int launch_render_rays_bf16p(const RenderArgs& a, hipStream_t stream);   // one 
 int launch_mlp_forward_f16p(const void* packed, const float* x, float* out, long P, int sigma_only, hipStream_t stream);
 int launch_render_rays_f16p(const RenderArgs& a, hipStream_t stream);
 int launch_rng_fill(float* out, long R, int n, unsigned long long seed, int stream_id, long ray_offset, hipStream_t stream);
+// density query (include/crnerf_geometry.h; sigma_query16.hip, sigma_query_bf16p.hip): sigma[n] at xyz[n][3], or at the nx * ny * nz nodes of a grid
+// given by its axes, x fastest.  The point count is in [1, 2^31 - 1]: abi.hip has checked
+int launch_sigma_points16(const void* packed, const float* xyz, float* sigma, long n, hipStream_t stream);
+int launch_sigma_grid16(const void* packed, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float* sigma, hipStream_t stream);
+int launch_sigma_points_bf16p(const void* packed, const float* xyz, float* sigma, long n, hipStream_t stream);
+int launch_sigma_grid_bf16p(const void* packed, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float* sigma, hipStream_t stream);
 
 
 size_t content_backward_workspace_floats(long HW);

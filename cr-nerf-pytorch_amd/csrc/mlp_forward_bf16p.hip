@@ -77,7 +77,9 @@ __global__ __launch_bounds__(512, 2) void CRNERF_P_MLP_KERNEL(const char* __rest
     asm volatile("" : "+v"(hg));   // keep the half-dependent column selects inside the loop (else hoisted and spilled)
     u32x4 pe[KS_XYZ], dv[KS_DIR];
     gather_embedded_p<XYZ_FREQS, KS_XYZ>(row, hg, valid, pe);
-    gather_embedded_p<DIR_FREQS, KS_DIR>(row + XYZ_DIM, hg, valid && !sigma_only, dv);
+    // sigma_only: x rows are 93 wide and hold no direction part.  The gather loads unconditionally and selects afterwards, so it is pointed at the
+    // row's own first columns then (all discarded): at row + XYZ_DIM the loads of the LAST point ran up to 108 bytes past the end of x
+    gather_embedded_p<DIR_FREQS, KS_DIR>(sigma_only ? row : row + XYZ_DIM, hg, valid && !sigma_only, dv);
 #pragma unroll
     for (int s = 0; s < KS_DIR; ++s) *(__attribute__((address_space(3))) u32x4*)(dirbuf + 32 * s) = dv[s];
     f32x16 feat[2];

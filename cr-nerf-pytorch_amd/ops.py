@@ -420,6 +420,68 @@ def mlp_forward(packed, x, sigma_only=False, precision="f32"):
     return out
 
 
+_SIGMA_QUERY = {"f32": ("crnerf_sigma_points_f32", "crnerf_sigma_grid_f32"), "bf16": ("crnerf_sigma_points_bf16", "crnerf_sigma_grid_bf16")}   # include/crnerf_geometry.h
+
+
+def _sigma_query_core(precision, what):
+    try:
+        name = resolve(precision)
+    except ValueError:
+        name = None
+    if name not in _SIGMA_QUERY:
+        raise ValueError("crnerf_amd: %s runs under precision 'f32' or 'bf16', got %r (the other cores have no density query)" % (what, precision))
+    return name
+
+
+def _sigma_input(t, name, what, points=False, on_device=True):
+    """A float32, contiguous device tensor of the right rank, as it is: nothing is converted or copied.  on_device=False: the rank alone."""
+    if not torch.is_tensor(t):
+        raise TypeError("crnerf_amd: %s: %s must be a tensor" % (what, name))
+    if points and (t.dim() != 2 or t.shape[1] != 3):
+        raise ValueError("crnerf_amd: %s expects %s as [n,3], got %s" % (what, name, tuple(t.shape)))
+    if not points and t.dim() != 1:
+        raise ValueError("crnerf_amd: %s expects the axis %s as [n], got %s" % (what, name, tuple(t.shape)))
+    return _lib.dev_ptr(t, name) if on_device else None
+
+
+def sigma_points(packed, xyz, precision="f32"):
+    """sigma [n] of the model behind `packed` (pack_mlp_weights(..., precision)) at xyz [n,3]: one launch that reads the coordinates, embeds them in
+    registers and walks the weight stream up to the sigma head (include/crnerf_geometry.h).  precision "f32": bit-identical to
+    mlp_forward(packed, posenc(xyz, 15), sigma_only=True)[:, 0]; "bf16": the bf16 matrix cores with the fused renderer's embedding.
+    Domain: |coordinate| < 64 (not checked here: crnerf_amd.geometry checks what it is handed on the host)."""
+    name = _sigma_query_core(precision, "sigma_points")
+    xp = _sigma_input(xyz, "xyz", "sigma_points", points=True)
+    lib = _lib.load()
+    _check_pack(lib, name, packed)
+    out = torch.empty(xyz.shape[0], dtype=torch.float32, device=xyz.device)
+    fn = _SIGMA_QUERY[name][0]
+    _lib.check(getattr(lib, fn)(ctypes.c_void_p(packed.data_ptr()), xp, _lib.dev_ptr(out), xyz.shape[0], _lib.stream_ptr()), fn)
+    return out
+
+
+def sigma_grid(packed, xs, ys, zs, precision="f32", out=None):
+    """sigma [nz, ny, nx] at the nodes (xs[ix], ys[iy], zs[iz]) of the grid the three axis tensors span (any values: non-uniform grids and slabs of
+    a larger grid are grids) -- sigma_points without the point list: 4 bytes per point leave, the axes are all that is read.  out=: a contiguous
+    float32 [nz, ny, nx] tensor on the axes' device to write into (a slab of a larger volume, say); it is returned.  At most 2^31 - 1 points a call."""
+    name = _sigma_query_core(precision, "sigma_grid")
+    for t, n in ((xs, "xs"), (ys, "ys"), (zs, "zs")):      # every shape before any device
+        _sigma_input(t, n, "sigma_grid", on_device=False)
+    ptrs = [_sigma_input(t, n, "sigma_grid") for t, n in ((xs, "xs"), (ys, "ys"), (zs, "zs"))]
+    shape = (zs.shape[0], ys.shape[0], xs.shape[0])
+    if shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:      # (the library refuses it too; an axis beyond int32 would not reach it intact)
+        raise ValueError("crnerf_amd: sigma_grid: %d x %d x %d is more than 2^31 - 1 points in one call (slabs of a grid are grids)" % shape[::-1])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=xs.device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != shape:
+        raise ValueError("crnerf_amd: sigma_grid: out must be [nz, ny, nx] = %s, got %s" % (shape, tuple(out.shape) if torch.is_tensor(out) else type(out)))
+    op = _lib.dev_ptr(out, "out")
+    lib = _lib.load()
+    _check_pack(lib, name, packed)
+    fn = _SIGMA_QUERY[name][1]
+    _lib.check(getattr(lib, fn)(ctypes.c_void_p(packed.data_ptr()), *ptrs, shape[2], shape[1], shape[0], op, _lib.stream_ptr()), fn)
+    return out
+
+
 def composite(raw, z, noise=None, noise_std=0.0):
     lib = _lib.load()
     raw, z = _f32c(raw, "raw"), _f32c(z, "z")
