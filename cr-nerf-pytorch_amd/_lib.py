@@ -315,6 +315,13 @@ GEOMETRY_SIGNATURES = {
     "crnerf_sigma_grid_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "crnerf_sigma_grid_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
 }
+# One row per symbol of the companion header include/crnerf_mesh.h (the iso-surface of a density grid: count, then emit).  A table of its own for
+# the same reason, bound in a third loop; tests/test_mesh_host.py holds it to its header's prototypes.
+MESH_SIGNATURES = {
+    "crnerf_mesh_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32]),
+    "crnerf_mesh_count_f32": (i32, [vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
+    "crnerf_mesh_emit_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, i64, i64, vp, vp, vp, vp]),
+}
 
 
 _lib = None
@@ -340,6 +347,10 @@ def load():
             fn.argtypes = args
         for name, (res, args) in GEOMETRY_SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_geometry.h
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in MESH_SIGNATURES.items():
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_mesh.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

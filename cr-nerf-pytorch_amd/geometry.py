@@ -1,18 +1,25 @@
 """Where is the geometry?  The density of a trained NeRF_sigma at points that do not come from rays: a point list, or the nodes of a grid --
-what mesh extraction (scipy / skimage / PyMCubes take the grid as it is), occupancy visualisation and point-cloud export start from.
+what mesh extraction, occupancy visualisation and point-cloud export start from -- and the surface itself, extracted on the device.
 
     sigma_points(model, xyz)                      [n]           sigma at xyz [n,3]
     sigma_grid(model, xs, ys, zs)                 [nz, ny, nx]  sigma at (xs[ix], ys[iy], zs[iz]); the axes need not be uniform
-    density_grid(model, lo, hi, resolution)       a DensityGrid: sigma on torch.linspace axes, and .occupied(threshold) -> [m,3] point cloud
+    density_grid(model, lo, hi, resolution)       a DensityGrid: sigma on torch.linspace axes, .occupied(threshold) -> [m,3] point cloud and
+                                                  .mesh(threshold) -> a Mesh (vertices [V,3], faces [F,3] int32, normals [V,3]; .save_ply(path))
+    extract_mesh(model, lo, hi, resolution, threshold)      density_grid(...).mesh(threshold)
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
+The mesh (include/crnerf_mesh.h): marching tetrahedra on the Kuhn split, watertight by construction, shared vertices, faces oriented out of the
+dense region, the same bytes on every run; count, one read-back of the two totals, emit.
 Inference only; GPU tensors only: like every op of the package there is no CPU fallback.
 
 Domain: |coordinate| < 64.  Below it the kernels' embedding is the routine the stand-alone posenc uses (which switches to ocml's sincosf there);
 the fused routine degrades beyond 200.  sigma_grid and density_grid refuse an axis or a bound outside the domain (the axes are small: the check
 reads them back); sigma_points does not check its points.
 """
+import math
+import struct
+
 import torch
 
 from . import ops
@@ -33,6 +40,59 @@ class DensityGrid:
         iz, iy, ix = torch.nonzero(self.sigma > threshold, as_tuple=True)
         return torch.stack((self.xs[ix], self.ys[iy], self.zs[iz]), dim=1)
 
+    @torch.no_grad()
+    def mesh(self, threshold, normals=True):
+        """The surface sigma == threshold as a Mesh: the nodes with sigma > threshold are inside and the faces look away from them.  The axes must be
+        strictly increasing and the threshold a number (ValueError otherwise; the axes are small: the check reads them back)."""
+        threshold = float(threshold)
+        if math.isnan(threshold):
+            raise ValueError("crnerf_amd.geometry: mesh: the threshold is NaN")
+        for t, n in ((self.xs, "xs"), (self.ys, "ys"), (self.zs, "zs")):
+            _check_increasing(t, n)
+        return Mesh(*ops.mesh_grid(self.sigma, self.xs, self.ys, self.zs, threshold, normals=normals))
+
+
+class Mesh:
+    """An indexed triangle mesh: vertices [V,3] float32, faces [F,3] int32 (vertex ids, counter-clockwise seen from outside the dense region),
+    normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None."""
+    __slots__ = ("vertices", "faces", "normals")
+
+    def __init__(self, vertices, faces, normals=None):
+        self.vertices, self.faces, self.normals = vertices, faces, normals
+
+    def save_ply(self, path):
+        """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals) per vertex, `uchar int` vertex_indices per face.  Copies to
+        the host itself; needs no third-party package."""
+        v = self.vertices.detach().to("cpu", torch.float32)
+        f = self.faces.detach().to("cpu", torch.int32)
+        if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError("crnerf_amd.geometry: save_ply expects vertices [V,3] and faces [F,3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+        props = ["x", "y", "z"]
+        if self.normals is not None:
+            n = self.normals.detach().to("cpu", torch.float32)
+            if tuple(n.shape) != tuple(v.shape):
+                raise ValueError("crnerf_amd.geometry: save_ply: normals %s do not match vertices %s" % (tuple(n.shape), tuple(v.shape)))
+            v = torch.cat((v, n), dim=1)
+            props += ["nx", "ny", "nz"]
+        header = "".join(["ply\nformat binary_little_endian 1.0\ncomment crnerf_amd.geometry\nelement vertex %d\n" % v.shape[0]]
+                         + ["property float %s\n" % p for p in props]
+                         + ["element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]])
+        rows = torch.empty(f.shape[0], 13, dtype=torch.uint8)      # one count byte, three little-endian int32
+        rows[:, 0] = 3
+        rows[:, 1:] = _little_endian(f.contiguous()).view(torch.uint8).reshape(-1, 12)
+        with open(path, "wb") as out:
+            out.write(header.encode("ascii"))
+            out.write(_little_endian(v.contiguous()).numpy().tobytes())
+            out.write(rows.numpy().tobytes())
+
+
+_HOST_IS_LITTLE = struct.pack("=H", 1) == struct.pack("<H", 1)
+
+
+def _little_endian(t):
+    """The tensor with its 4-byte elements in little-endian byte order (as it is on a little-endian host)."""
+    return t if _HOST_IS_LITTLE else t.view(torch.uint8).reshape(-1, 4).flip(1).reshape(-1).view(t.dtype).reshape(t.shape)
+
 
 def _check_axis(t, name):
     """Rank, then domain -- wherever the axis lives: the refusal needs no device."""
@@ -41,6 +101,13 @@ def _check_axis(t, name):
         worst = float(t.abs().max())
         if not worst < DOMAIN:          # (a NaN is refused too)
             raise ValueError("crnerf_amd.geometry: the axis %s reaches |v| = %g; the density query is defined for |v| < %g" % (name, worst, DOMAIN))
+
+
+def _check_increasing(t, name):
+    """The orientation of the faces, and t in [0, 1] meaning `between the nodes`, rest on axes that rise."""
+    ops._sigma_input(t, name, "mesh", on_device=False)
+    if t.numel() > 1 and not bool((t[1:] > t[:-1]).all()):      # (a NaN is refused too)
+        raise ValueError("crnerf_amd.geometry: mesh: the axis %s is not strictly increasing" % name)
 
 
 @torch.no_grad()
@@ -81,3 +148,11 @@ def density_grid(model, lo, hi, resolution, precision="f32"):
     dev = pack.device
     xs, ys, zs = (torch.linspace(lo[a], hi[a], n[a], dtype=torch.float32, device=dev) for a in range(3))
     return DensityGrid(ops.sigma_grid(pack, xs, ys, zs, precision=precision), xs, ys, zs)
+
+
+@torch.no_grad()
+def extract_mesh(model, lo, hi, resolution, threshold, precision="f32"):
+    """density_grid(model, lo, hi, resolution, precision).mesh(threshold): the surface of the box's density as a Mesh."""
+    if math.isnan(float(threshold)):      # before the grid is paid for
+        raise ValueError("crnerf_amd.geometry: mesh: the threshold is NaN")
+    return density_grid(model, lo, hi, resolution, precision=precision).mesh(threshold)

@@ -482,6 +482,47 @@ def sigma_grid(packed, xs, ys, zs, precision="f32", out=None):
     return out
 
 
+def mesh_grid(sigma, xs, ys, zs, threshold, normals=True):
+    """The iso-surface sigma == threshold of a density grid as an indexed triangle mesh, extracted on the device (include/crnerf_mesh.h states every
+    rule: marching tetrahedra on the Kuhn split, inside = sigma > threshold, one shared vertex per active edge, faces oriented out of the dense
+    region, content and order deterministic).  sigma [nz, ny, nx] and the axes xs [nx], ys [ny], zs [nz]: float32, contiguous, on the device, as
+    they are.  Returns (vertices [V,3] float32, faces [F,3] int32, normals [V,3] float32 or None).
+    Count, ONE read-back of the two totals (the only synchronisation), allocate, emit.  The axes are taken to be strictly increasing -- that is what
+    the orientation promise rests on -- and this is NOT checked here: crnerf_amd.geometry checks what it is handed."""
+    if not torch.is_tensor(sigma):
+        raise TypeError("crnerf_amd: mesh_grid: sigma must be a tensor")
+    if sigma.dim() != 3:
+        raise ValueError("crnerf_amd: mesh_grid expects sigma as [nz, ny, nx], got %s" % (tuple(sigma.shape),))
+    for t, n in ((xs, "xs"), (ys, "ys"), (zs, "zs")):      # every shape before any device
+        _sigma_input(t, n, "mesh_grid", on_device=False)
+    shape = (zs.shape[0], ys.shape[0], xs.shape[0])
+    if tuple(sigma.shape) != shape:
+        raise ValueError("crnerf_amd: mesh_grid: sigma must be [nz, ny, nx] = %s for these axes, got %s" % (shape, tuple(sigma.shape)))
+    if shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:
+        raise ValueError("crnerf_amd: mesh_grid: %d x %d x %d is more than 2^31 - 1 nodes in one call" % shape[::-1])
+    threshold = float(threshold)
+    sp = _lib.dev_ptr(sigma, "sigma")
+    ptrs = [_sigma_input(t, n, "mesh_grid") for t, n in ((xs, "xs"), (ys, "ys"), (zs, "zs"))]
+    lib = _lib.load()
+    dims = (shape[2], shape[1], shape[0])
+    dev = sigma.device
+    workspace = torch.empty(max(int(lib.crnerf_mesh_workspace_bytes(*dims)), 8), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    wp, st = ctypes.c_void_p(workspace.data_ptr()), _lib.stream_ptr()
+    _lib.check(lib.crnerf_mesh_count_f32(sp, *dims, threshold, wp, ctypes.c_void_p(counts.data_ptr()), st), "crnerf_mesh_count_f32")
+    V, F = counts.tolist()
+    if V > 2 ** 31 - 1 or F > 2 ** 31 - 1:
+        raise ValueError("crnerf_amd: mesh_grid: %d vertices and %d faces do not fit int32 indices; extract slabs of the grid" % (V, F))
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    nrm = torch.empty(V, 3, dtype=torch.float32, device=dev) if normals else None
+    if V or F:
+        _lib.check(lib.crnerf_mesh_emit_f32(sp, *ptrs, *dims, threshold, wp, V, F, ctypes.c_void_p(vertices.data_ptr()),
+                                            ctypes.c_void_p(nrm.data_ptr()) if normals else None, ctypes.c_void_p(faces.data_ptr()), st),
+                   "crnerf_mesh_emit_f32")
+    return vertices, faces, nrm
+
+
 def composite(raw, z, noise=None, noise_std=0.0):
     lib = _lib.load()
     raw, z = _f32c(raw, "raw"), _f32c(z, "z")
