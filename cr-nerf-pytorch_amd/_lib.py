@@ -323,6 +323,16 @@ MESH_SIGNATURES = {
     "crnerf_mesh_emit_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, i64, i64, vp, vp, vp, vp]),
 }
 
+# One row per symbol of the companion header include/crnerf_mesh_parts.h (the connected parts of an indexed mesh: label, sizes, select).  A table
+# of its own for the same reason, bound in a fourth loop; tests/test_mesh_parts_host.py holds it to its header's prototypes.
+MESH_PARTS_SIGNATURES = {
+    "crnerf_mesh_parts_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
+    "crnerf_mesh_parts_label_i32": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
+    "crnerf_mesh_parts_sizes_i32": (i32, [vp, vp, i64, i64, i64, vp, vp, vp]),
+    "crnerf_mesh_parts_select_count": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp]),
+    "crnerf_mesh_parts_select_emit_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp]),
+}
+
 
 _lib = None
 _lock = threading.Lock()
@@ -351,6 +361,10 @@ def load():
             fn.argtypes = args
         for name, (res, args) in MESH_SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_mesh.h
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in MESH_PARTS_SIGNATURES.items():
+            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_mesh_parts.h
             fn.restype = res
             fn.argtypes = args
         _lib = lib

@@ -5,12 +5,17 @@ what mesh extraction, occupancy visualisation and point-cloud export start from 
     sigma_grid(model, xs, ys, zs)                 [nz, ny, nx]  sigma at (xs[ix], ys[iy], zs[iz]); the axes need not be uniform
     density_grid(model, lo, hi, resolution)       a DensityGrid: sigma on torch.linspace axes, .occupied(threshold) -> [m,3] point cloud and
                                                   .mesh(threshold) -> a Mesh (vertices [V,3], faces [F,3] int32, normals [V,3]; .save_ply(path))
-    extract_mesh(model, lo, hi, resolution, threshold)      density_grid(...).mesh(threshold)
+    extract_mesh(model, lo, hi, resolution, threshold)      density_grid(...).mesh(threshold); keep_largest=True: its .largest()
+    Mesh.parts()                                  a MeshParts: count, vertex_part [V], face_part [F], n_vertices [K], n_faces [K]
+    Mesh.largest(n=1) / .drop_small(min_faces) / .select(keep)      a new Mesh without the floaters: whole parts removed, rows and order kept
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
 The mesh (include/crnerf_mesh.h): marching tetrahedra on the Kuhn split, watertight by construction, shared vertices, faces oriented out of the
 dense region, the same bytes on every run; count, one read-back of the two totals, emit.
+The parts (include/crnerf_mesh_parts.h): connected components by shared vertex, labelled by a lock-free union-find on the device, ids ascending
+in the part's smallest vertex id; a filtered mesh is the original minus whole parts -- rows copied byte for byte, order kept, ids renumbered --
+and again the same bytes on every run.  One read-back for the labels (K), one for a selection (V', F').
 Inference only; GPU tensors only: like every op of the package there is no CPU fallback.
 
 Domain: |coordinate| < 64.  Below it the kernels' embedding is the routine the stand-alone posenc uses (which switches to ocml's sincosf there);
@@ -60,6 +65,67 @@ class Mesh:
     def __init__(self, vertices, faces, normals=None):
         self.vertices, self.faces, self.normals = vertices, faces, normals
 
+    @torch.no_grad()
+    def parts(self):
+        """The connected parts of the mesh as a MeshParts (include/crnerf_mesh_parts.h: parts by shared vertex, ids ascending in the part's
+        smallest vertex id).  Labelled and measured on the device; one read-back, of the number of parts."""
+        return MeshParts(*ops.mesh_parts(self.faces, self.vertices.shape[0]))
+
+    @torch.no_grad()
+    def select(self, keep, parts=None):
+        """A new Mesh of the parts `keep` names: a bool / uint8 [K] tensor, or a sequence of part ids.  Kept rows are the original rows, in their
+        original order, ids renumbered; normals=None stays None.  parts=: the MeshParts of this mesh, when the caller has it already.  A wrong
+        length, a wrong dtype or an id outside [0, K): ValueError."""
+        if torch.is_tensor(keep):
+            if keep.dtype not in (torch.bool, torch.uint8):      # before any device work
+                raise ValueError("crnerf_amd.geometry: select: keep must be a bool or uint8 tensor, got %s" % keep.dtype)
+            if keep.dim() != 1:
+                raise ValueError("crnerf_amd.geometry: select: keep must be [K], got %s" % (tuple(keep.shape),))
+            ids = None
+        else:
+            try:
+                ids = [int(i) for i in keep]
+                exact = all(i == k for i, k in zip(ids, keep))
+            except (TypeError, ValueError):
+                ids, exact = None, False
+            if not exact:
+                raise ValueError("crnerf_amd.geometry: select: keep must be a bool / uint8 [K] tensor or a sequence of part ids")
+            if any(i < 0 for i in ids):
+                raise ValueError("crnerf_amd.geometry: select: the part id %d is negative" % min(ids))
+        parts = _parts_of(self, parts)
+        K = parts.count
+        if ids is None:
+            if keep.shape[0] != K:
+                raise ValueError("crnerf_amd.geometry: select: keep has %d entries for %d parts" % (keep.shape[0], K))
+            keep = keep.to(self.faces.device).contiguous()
+        else:
+            if ids and max(ids) >= K:
+                raise ValueError("crnerf_amd.geometry: select: the part id %d is outside [0, %d)" % (max(ids), K))
+            keep = torch.zeros(K, dtype=torch.uint8, device=self.faces.device)
+            if ids:
+                keep[torch.tensor(ids, dtype=torch.int64, device=keep.device)] = 1
+        return Mesh(*_select(self, parts, keep))
+
+    @torch.no_grad()
+    def largest(self, n=1, parts=None):
+        """A new Mesh of the n parts with the most faces (ties go to the smaller part id); the rows stay in their original order.  Ranked on the
+        device."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("crnerf_amd.geometry: largest: n must not be negative, got %d" % n)
+        parts = _parts_of(self, parts)
+        keep = torch.zeros(parts.count, dtype=torch.uint8, device=self.faces.device)
+        if parts.count and n:
+            order = torch.sort(parts.n_faces, descending=True, stable=True).indices      # stable: equal sizes stay in id order
+            keep[order[:n]] = 1
+        return Mesh(*_select(self, parts, keep))
+
+    @torch.no_grad()
+    def drop_small(self, min_faces, parts=None):
+        """A new Mesh of the parts with at least min_faces faces."""
+        parts = _parts_of(self, parts)
+        return Mesh(*_select(self, parts, (parts.n_faces >= int(min_faces)).to(torch.uint8)))
+
     def save_ply(self, path):
         """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals) per vertex, `uchar int` vertex_indices per face.  Copies to
         the host itself; needs no third-party package."""
@@ -86,7 +152,36 @@ class Mesh:
             out.write(rows.numpy().tobytes())
 
 
-_HOST_IS_LITTLE = struct.pack("=H", 1) == struct.pack("<H", 1)
+class MeshParts:
+    """The connected parts of a Mesh: count K, vertex_part [V] int32, face_part [F] int32 (-1 for a face with an id outside [0, V)), and the sizes
+    n_vertices [K], n_faces [K] int32 (device tensors).  Part ids ascend in the smallest vertex id of the part."""
+    __slots__ = ("vertex_part", "face_part", "n_vertices", "n_faces")
+
+    def __init__(self, vertex_part, face_part, n_vertices, n_faces):
+        self.vertex_part, self.face_part, self.n_vertices, self.n_faces = vertex_part, face_part, n_vertices, n_faces
+
+    @property
+    def count(self):
+        return int(self.n_faces.shape[0])
+
+
+def _parts_of(mesh, parts):
+    """The caller's MeshParts, held to the mesh; None: the mesh is labelled now."""
+    if parts is None:
+        return mesh.parts()
+    if not isinstance(parts, MeshParts):
+        raise ValueError("crnerf_amd.geometry: parts must be the MeshParts of this mesh (Mesh.parts())")
+    if parts.vertex_part.shape[0] != mesh.vertices.shape[0] or parts.face_part.shape[0] != mesh.faces.shape[0]:
+        raise ValueError("crnerf_amd.geometry: parts labels %d vertices and %d faces, the mesh has %d and %d"
+                         % (parts.vertex_part.shape[0], parts.face_part.shape[0], mesh.vertices.shape[0], mesh.faces.shape[0]))
+    return parts
+
+
+def _select(mesh, parts, keep):
+    return ops.mesh_select(mesh.vertices, mesh.faces, mesh.normals, parts.vertex_part, parts.face_part, keep)
+
+
+_HOST_IS_LITTLE =struct.pack("=H", 1) == struct.pack("<H", 1)
 
 
 def _little_endian(t):
@@ -151,8 +246,10 @@ def density_grid(model, lo, hi, resolution, precision="f32"):
 
 
 @torch.no_grad()
-def extract_mesh(model, lo, hi, resolution, threshold, precision="f32"):
-    """density_grid(model, lo, hi, resolution, precision).mesh(threshold): the surface of the box's density as a Mesh."""
+def extract_mesh(model, lo, hi, resolution, threshold, precision="f32", keep_largest=False):
+    """density_grid(model, lo, hi, resolution, precision).mesh(threshold): the surface of the box's density as a Mesh.  keep_largest=True: its
+    .largest(1) -- the part with the most faces, the floaters of a trained density gone."""
     if math.isnan(float(threshold)):      # before the grid is paid for
         raise ValueError("crnerf_amd.geometry: mesh: the threshold is NaN")
-    return density_grid(model, lo, hi, resolution, precision=precision).mesh(threshold)
+    mesh = density_grid(model, lo, hi, resolution, precision=precision).mesh(threshold)
+    return mesh.largest(1) if keep_largest else mesh

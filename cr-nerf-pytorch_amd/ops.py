@@ -523,6 +523,94 @@ def mesh_grid(sigma, xs, ys, zs, threshold, normals=True):
     return vertices, faces, nrm
 
 
+def _parts_input(t, name, what, dtype, cols=None, rows=None, on_device=True):
+    """An indexed-mesh tensor of the right rank, dtype and row count, contiguous and on the device, as it is.  on_device=False: shape and dtype
+    alone -- those refusals need no device."""
+    if not torch.is_tensor(t):
+        raise TypeError("crnerf_amd: %s: %s must be a tensor" % (what, name))
+    if (t.dim() != 1) if cols is None else (t.dim() != 2 or t.shape[1] != cols):
+        raise ValueError("crnerf_amd: %s expects %s as %s, got %s" % (what, name, "[n]" if cols is None else "[n,%d]" % cols, tuple(t.shape)))
+    if rows is not None and t.shape[0] != rows:
+        raise ValueError("crnerf_amd: %s: %s must have %d rows, got %d" % (what, name, rows, t.shape[0]))
+    if t.dtype != dtype:
+        raise TypeError("crnerf_amd: %s must be %s, got %s" % (name, dtype, t.dtype))
+    return _lib.dev_ptr(t, name, dtype) if on_device else None
+
+
+def _parts_workspace(lib, V, F, dev):
+    return torch.empty(max(int(lib.crnerf_mesh_parts_workspace_bytes(V, F)), 16), dtype=torch.uint8, device=dev)
+
+
+def mesh_parts(faces, n_vertices):
+    """The connected parts of an indexed triangle list, labelled on the device (include/crnerf_mesh_parts.h states every rule: parts by shared
+    vertex over the valid faces, ids 0..K-1 ascending in the part's smallest vertex id, content deterministic).  faces [F,3]: int32, contiguous, on
+    the device, as it is; n_vertices: V.  Returns (vertex_part [V] int32, face_part [F] int32 -- -1 for a face with an id outside [0, V) --,
+    part_vertices [K] int32, part_faces [K] int32).  Label, ONE read-back of K (the only synchronisation), allocate, sizes."""
+    V = int(n_vertices)
+    if V < 0 or V > 2 ** 31 - 1:
+        raise ValueError("crnerf_amd: mesh_parts: n_vertices must lie in [0, 2^31 - 1], got %d" % V)
+    fp = _parts_input(faces, "faces", "mesh_parts", torch.int32, cols=3)
+    F, dev = faces.shape[0], faces.device
+    lib = _lib.load()
+    vertex_part = torch.empty(V, dtype=torch.int32, device=dev)
+    face_part = torch.full((F,), -1, dtype=torch.int32, device=dev) if V == 0 else torch.empty(F, dtype=torch.int32, device=dev)
+    K = 0
+    st = _lib.stream_ptr()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    if V:
+        workspace = _parts_workspace(lib, V, F, dev)
+        counts = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.crnerf_mesh_parts_label_i32(fp, V, F, p(workspace), p(vertex_part), p(face_part), p(counts), st), "crnerf_mesh_parts_label_i32")
+        K = int(counts.item())
+    part_vertices = torch.empty(K, dtype=torch.int32, device=dev)
+    part_faces = torch.empty(K, dtype=torch.int32, device=dev)
+    if K:
+        _lib.check(lib.crnerf_mesh_parts_sizes_i32(p(vertex_part), p(face_part), V, F, K, p(part_vertices), p(part_faces), st), "crnerf_mesh_parts_sizes_i32")
+    return vertex_part, face_part, part_vertices, part_faces
+
+
+def mesh_select(vertices, faces, normals, vertex_part, face_part, keep):
+    """The mesh minus the parts keep[] does not name (include/crnerf_mesh_parts.h, Selection): kept rows copied byte for byte in their original
+    order, ids renumbered by rank.  vertices [V,3] float32, faces [F,3] int32, normals [V,3] float32 or None, vertex_part [V] / face_part [F]
+    int32 (what mesh_parts returned), keep [K] uint8 or bool: contiguous, on the device, as they are.  Returns (vertices', faces', normals' or
+    None).  Count, ONE read-back of V' and F' (the only synchronisation), allocate, emit."""
+    what = "mesh_select"
+    vp_ = np_ = fp = vpp = fpp = None
+    for on_device in (False, True):      # every shape and dtype before any device
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        V = vertices.shape[0]
+        fp = _parts_input(faces, "faces", what, torch.int32, cols=3, on_device=on_device)
+        F = faces.shape[0]
+        np_ = None if normals is None else _parts_input(normals, "normals", what, torch.float32, cols=3, rows=V, on_device=on_device)
+        if not torch.is_tensor(keep) or keep.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("crnerf_amd: mesh_select: keep must be a uint8 or bool tensor")
+        if keep.dim() != 1:
+            raise ValueError("crnerf_amd: mesh_select expects keep as [K], got %s" % (tuple(keep.shape),))
+        K = keep.shape[0]
+        if K > V:
+            raise ValueError("crnerf_amd: mesh_select: keep names %d parts, more than the %d vertices" % (K, V))
+        vpp = _parts_input(vertex_part, "vertex_part", what, torch.int32, rows=V, on_device=on_device)
+        fpp = _parts_input(face_part, "face_part", what, torch.int32, rows=F, on_device=on_device)
+    kp = _lib.dev_ptr(keep, "keep", keep.dtype)      # (a bool tensor is one byte an element, 0 or 1)
+    dev = vertices.device
+    lib = _lib.load()
+    st = _lib.stream_ptr()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    Vk = Fk = 0
+    if V and K:
+        workspace = _parts_workspace(lib, V, F, dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.crnerf_mesh_parts_select_count(vpp, fpp, V, F, K, kp, p(workspace), p(counts), st), "crnerf_mesh_parts_select_count")
+        Vk, Fk = counts.tolist()
+    out_v = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+    out_n = None if normals is None else torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    if Vk or Fk:
+        _lib.check(lib.crnerf_mesh_parts_select_emit_f32(vp_, np_, fp, vpp, fpp, V, F, K, kp, p(workspace), Vk, Fk, p(out_v),
+                                                         None if out_n is None else p(out_n), p(out_f), st), "crnerf_mesh_parts_select_emit_f32")
+    return out_v, out_f, out_n
+
+
 def composite(raw, z, noise=None, noise_std=0.0):
     lib = _lib.load()
     raw, z = _f32c(raw, "raw"), _f32c(z, "z")
