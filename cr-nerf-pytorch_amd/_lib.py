@@ -1,12 +1,13 @@
-"""ctypes binding of libcrnerf_hip.so (the C ABI declared in include/crnerf.h).
+"""ctypes binding of libcrnerf_hip.so (the C ABI declared in the headers of include/).
 
 The library is the product: if it is missing or fails to load, every call raises -- there is no
 eager/CPU fallback behind these functions.
 """
+import collections.abc
 import ctypes
+import itertools
 import os
 import threading
-import types
 
 import torch
 
@@ -120,14 +121,29 @@ class ConvGeom(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("cin", "cout", "H", "W", "k", "stride", "pad", "dil", "depthwise")]
 
 
-# One row per symbol of include/crnerf.h: name -> (restype, argtypes).  This table IS the export list (EXPORTS below): build() checks the library
-# against it, load() binds it, tests/test_host.py holds it to the header's prototypes.  One spelling per C type, so that equal prototypes read equal.
+class SweepDecodeArgs(ctypes.Structure):
+    """struct crnerf_sweep_decode_args (include/crnerf_sweep.h)."""
+    _fields_ = [
+        ("content", _c_fp), ("HW", ctypes.c_int64), ("stats", _c_fp), ("style_HW", ctypes.c_int64),
+        ("S", ctypes.c_int32), ("out_kind", ctypes.c_int32),
+        ("weights", ctypes.POINTER(ctypes.c_void_p)), ("workspace", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("style_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64),
+    ]
+
+
+SWEEP_MAX_STYLES, SWEEP_STATS_FLOATS = 16, 1088          # CRNERF_SWEEP_MAX_STYLES, CRNERF_SWEEP_STATS_FLOATS
+SWEEP_OUT_F32, SWEEP_OUT_U8 = 0, 1                       # CRNERF_SWEEP_OUT_*
+
+
+# The ABI registry: one table per header of include/, in binding order; each table holds one row per prototype, name -> (restype, argtypes).
+# Everything that needs the ABI reads it here: load() binds it, build() checks the library's exports against it, tests/test_host.py holds every
+# table to its header parameter by parameter.  One spelling per C type, so that equal prototypes read equal.  A new header costs one entry.
 i64, i32, u32, u64, f32, f64 = ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_double      # i32: int / int32_t
 usz, cstr, vp = ctypes.c_size_t, ctypes.c_char_p, ctypes.c_void_p
 pp = ctypes.POINTER(ctypes.c_void_p)                     # a host array of pointers (every `T* const*`)
 hf = ctypes.POINTER(ctypes.c_float)                      # a host float array (`*_host`)
 ra = ctypes.POINTER(RenderArgs)
-SIGNATURES = {
+HEADER_SIGNATURES = {"crnerf.h": {
     "crnerf_abi_version": (i32, []),
     "crnerf_last_error": (cstr, []),
     "crnerf_packed_mlp_bytes": (usz, []),
@@ -235,8 +251,8 @@ SIGNATURES = {
     "crnerf_cgnet_forward_train_f32": (i32, [vp, i32, i32, i32, pp, pp, pp, pp, f32, f32, vp, vp, vp]),
     "crnerf_cgnet_backward_f32": (i32, [vp, i32, i32, i32, pp, vp, vp, vp, vp, pp, vp]),
     "crnerf_peer_window_bytes": (usz, []),
-    "crnerf_peer_window_create": (i32, [pp, ctypes.c_char_p]),
-    "crnerf_peer_window_open": (i32, [ctypes.c_char_p, pp]),
+    "crnerf_peer_window_create": (i32, [pp, cstr]),
+    "crnerf_peer_window_open": (i32, [cstr, pp]),
     "crnerf_peer_window_close": (i32, [vp]),
     "crnerf_peer_window_destroy": (i32, [vp]),
     "crnerf_peer_window_status": (i32, [vp, ctypes.POINTER(i32)]),
@@ -252,86 +268,71 @@ SIGNATURES = {
     "crnerf_lanczos_resize_u8": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
     "crnerf_scene_bounds_workspace_bytes": (usz, [i32, i32]),
     "crnerf_scene_bounds_f64": (i32, [vp, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp]),
-}
-EXPORTS = list(SIGNATURES)
-# One row per symbol of the companion header include/crnerf_blender.h (the Blender dataset path), in the same spelling and bound by the
-# same loader; tests/test_blender_host.py holds it to that header's prototypes.  Folding the headers moves these rows to the end of SIGNATURES.
-BLENDER_SIGNATURES = {
+}, "crnerf_blender.h": {                # the Blender dataset path
     "crnerf_rgba_prepare_workspace_bytes": (usz, [i32, i32, i32, i32]),
     "crnerf_rgba_prepare_u8": (i32, [ctypes.POINTER(RgbaPrepareArgs), vp]),
     "crnerf_grid_sample_batch_round_f32": (i32, [ctypes.POINTER(BatchArgs), vp]),
     "crnerf_generate_rays_fmanorm_f32": (i32, [hf, hf, i32, i32, f32, f32, vp, vp]),
-}
-# One row per symbol of the companion header include/crnerf_lean.h (the lean render on the pair core's two builds), bound by the same loader;
-# tests/test_lean_pair_host.py holds it to that header's prototypes.
-LEAN_SIGNATURES = {
+}, "crnerf_lean.h": {                   # the lean render on the pair core's two builds
     "crnerf_render_rays_lean_bf16": (i32, [ra, vp]),
     "crnerf_render_rays_lean_f16": (i32, [ra, vp]),
-}
-# One row per symbol of include/crnerf_lean_composite.h (the coarse-weights renders and the lean fine launch of the composite precisions; the header
-# crnerf_lean.h includes), bound by the same loader; tests/test_lean_composite_host.py holds it to that header's prototypes.
-LEAN_COMPOSITE_SIGNATURES = {
+}, "crnerf_lean_composite.h": {         # the coarse-weights renders and the lean fine launch of the composite precisions
     "crnerf_render_coarse_weights_f32h2": (i32, [ra, vp]),
     "crnerf_render_coarse_weights_f32x3": (i32, [ra, vp]),
     "crnerf_render_coarse_weights_f32x3_repair": (i32, [ra, vp]),
     "crnerf_render_coarse_weights_f16": (i32, [ra, vp]),
     "crnerf_render_rays_lean_bf16_fine": (i32, [ra, vp]),
-}
-# One row per symbol of the companion header include/crnerf_lean_x.h (the lean render on the two fp32-accurate split cores: what lean=True runs on
-# under precision "f32x3", "f32h2" and "auto"), bound by the same loader; tests/test_lean_x_host.py holds it to that header's prototypes.
-LEAN_X_SIGNATURES = {
+}, "crnerf_lean_x.h": {                 # the lean render on the two fp32-accurate split cores
     "crnerf_render_rays_lean_f32x3": (i32, [ra, vp]),
     "crnerf_render_rays_lean_f32h2": (i32, [ra, vp]),
     "crnerf_render_rays_lean_f32x3_repair": (i32, [ra, vp]),
-}
-
-
-class SweepDecodeArgs(ctypes.Structure):
-    """struct crnerf_sweep_decode_args (include/crnerf_sweep.h)."""
-    _fields_ = [
-        ("content", _c_fp), ("HW", ctypes.c_int64), ("stats", _c_fp), ("style_HW", ctypes.c_int64),
-        ("S", ctypes.c_int32), ("out_kind", ctypes.c_int32),
-        ("weights", ctypes.POINTER(ctypes.c_void_p)), ("workspace", ctypes.c_void_p), ("out", ctypes.c_void_p),
-        ("style_stride", ctypes.c_int64), ("plane_stride", ctypes.c_int64),
-    ]
-
-
-SWEEP_MAX_STYLES, SWEEP_STATS_FLOATS = 16, 1088          # CRNERF_SWEEP_MAX_STYLES, CRNERF_SWEEP_STATS_FLOATS
-SWEEP_OUT_F32, SWEEP_OUT_U8 = 0, 1                       # CRNERF_SWEEP_OUT_*
-# One row per symbol of the companion header include/crnerf_sweep.h (the appearance sweep: S styles' statistics once, one content grid decoded
-# under all of them), bound by the same loader; tests/test_sweep_host.py holds it to that header's prototypes.
-SWEEP_SIGNATURES = {
+}, "crnerf_sweep.h": {                  # the appearance sweep: S styles' statistics once, one content grid decoded under all of them
     "crnerf_crossray_style_stats_f32": (i32, [vp, i32, i64, i64, pp, vp, vp, vp]),
     "crnerf_crossray_decode_multi_f32": (i32, [ctypes.POINTER(SweepDecodeArgs), vp]),
-}
-# The six tables as one read-only view, in the order load() binds them: every symbol the library must export.
-ALL_SIGNATURES = types.MappingProxyType({**SIGNATURES, **BLENDER_SIGNATURES, **LEAN_SIGNATURES, **LEAN_COMPOSITE_SIGNATURES, **LEAN_X_SIGNATURES, **SWEEP_SIGNATURES})
-# One row per symbol of the companion header include/crnerf_geometry.h (the density query: sigma at points or on a grid, trunk-only walk).  A table
-# of its own that load() binds in a second loop and that is NOT folded into ALL_SIGNATURES: the size of that view is pinned by the tests of the
-# rounds that wrote it.  tests/test_geometry_host.py holds this one to its header's prototypes.
-GEOMETRY_SIGNATURES = {
+}, "crnerf_geometry.h": {               # the density query: sigma at points or on a grid, trunk-only walk
     "crnerf_sigma_points_f32": (i32, [vp, vp, vp, i64, vp]),
     "crnerf_sigma_points_bf16": (i32, [vp, vp, vp, i64, vp]),
     "crnerf_sigma_grid_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "crnerf_sigma_grid_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
-}
-# One row per symbol of the companion header include/crnerf_mesh.h (the iso-surface of a density grid: count, then emit).  A table of its own for
-# the same reason, bound in a third loop; tests/test_mesh_host.py holds it to its header's prototypes.
-MESH_SIGNATURES = {
-    "crnerf_mesh_workspace_bytes": (ctypes.c_size_t, [i32, i32, i32]),
-    "crnerf_mesh_count_f32": (i32, [vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
-    "crnerf_mesh_emit_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, ctypes.c_float, vp, i64, i64, vp, vp, vp, vp]),
-}
-
-# One row per symbol of the companion header include/crnerf_mesh_parts.h (the connected parts of an indexed mesh: label, sizes, select).  A table
-# of its own for the same reason, bound in a fourth loop; tests/test_mesh_parts_host.py holds it to its header's prototypes.
-MESH_PARTS_SIGNATURES = {
-    "crnerf_mesh_parts_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
+}, "crnerf_mesh.h": {                   # the iso-surface of a density grid: count, then emit
+    "crnerf_mesh_workspace_bytes": (usz, [i32, i32, i32]),
+    "crnerf_mesh_count_f32": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
+    "crnerf_mesh_emit_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, vp, i64, i64, vp, vp, vp, vp]),
+}, "crnerf_mesh_parts.h": {             # the connected parts of an indexed mesh: label, sizes, select
+    "crnerf_mesh_parts_workspace_bytes": (usz, [i64, i64]),
     "crnerf_mesh_parts_label_i32": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
     "crnerf_mesh_parts_sizes_i32": (i32, [vp, vp, i64, i64, i64, vp, vp, vp]),
     "crnerf_mesh_parts_select_count": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp]),
     "crnerf_mesh_parts_select_emit_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp]),
-}
+}}
+
+
+class _AllSignatures(collections.abc.Mapping):
+    """Every row of HEADER_SIGNATURES as one read-only mapping, in binding order.  It reads the registry on every access, so the two cannot
+    fall out of step."""
+
+    def __getitem__(self, name):
+        return HEADER_SIGNATURES[header_of(name)][name]
+
+    def __iter__(self):
+        return itertools.chain.from_iterable(HEADER_SIGNATURES.values())
+
+    def __len__(self):
+        return sum(len(table) for table in HEADER_SIGNATURES.values())
+
+
+def header_of(name):
+    """The header whose table holds `name`; KeyError if none does."""
+    for header, table in HEADER_SIGNATURES.items():
+        if name in table:
+            return header
+    raise KeyError(name)
+
+
+ALL_SIGNATURES = _AllSignatures()
+EXPORTS = list(ALL_SIGNATURES)          # every symbol the library must export
+if len(set(EXPORTS)) != len(EXPORTS):
+    raise ImportError("crnerf_amd._lib: declared by more than one header: %s" % sorted({n for n in EXPORTS if EXPORTS.count(n) > 1}))
 
 
 _lib = None
@@ -352,19 +353,11 @@ def load():
                 "(or __graft_entry__.build()); there is no fallback path." % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in ALL_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf.h / crnerf_blender.h / crnerf_lean.h (+ _composite) / crnerf_lean_x.h / crnerf_sweep.h
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in GEOMETRY_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_geometry.h
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in MESH_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_mesh.h
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in MESH_PARTS_SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError here = the library does not match include/crnerf_mesh_parts.h
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise AttributeError("crnerf_amd: %s does not export %s, which include/%s declares: the library does not match that header"
+                                     % (LIB_PATH, name, header_of(name))) from None
             fn.restype = res
             fn.argtypes = args
         _lib = lib

@@ -1,7 +1,7 @@
 """CPU-only side of the Blender dataset path: the numpy restatement of tests/_blender_cases.py against Pillow's and the
 reference's recorded outputs (tests/golden/g19_blender.npz) and against Pillow live, the conditions those outputs must meet for the GPU
 tests to mean something, perturbation_params against the reference's add_perturbation, include/crnerf_blender.h against
-_lib.BLENDER_SIGNATURES, and every refusal of the entry points (no device is touched).  Every comparison is exact."""
+its table of _lib.HEADER_SIGNATURES, and every refusal of the entry points (no device is touched).  Every comparison is exact."""
 import ctypes
 import math
 import os
@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import _abi
 import _blender_cases as B
 from crnerf_amd import _lib
 from crnerf_amd.datasets import blender
@@ -100,32 +101,17 @@ def test_intrinsics():
     assert K.dtype == np.float64 and np.array_equal(K, np.array([[focal, 0, 20.0], [0, focal, 20.0], [0, 0, 1]]))
 
 
-def header_prototypes():
-    """{symbol: (return type, number of parameters)} of every prototype of include/crnerf_blender.h."""
-    text = open(os.path.join(ROOT, "include", "crnerf_blender.h")).read()
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(crnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
-    return {name: ("".join(ret.split()), 0 if params.strip() == "void" else params.count(",") + 1) for ret, name, params in protos}
-
-
 def test_companion_header_declares_what_the_binding_expects():
-    protos = header_prototypes()
-    assert sorted(protos) == sorted(_lib.BLENDER_SIGNATURES) and len(protos) == 4
-    assert not set(protos) & set(_lib.SIGNATURES)
-    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t}
-    for name, (ret, n_params) in protos.items():
-        restype, argtypes = _lib.BLENDER_SIGNATURES[name]
-        assert len(argtypes) == n_params, "%s: %d argtypes for %d parameters" % (name, len(argtypes), n_params)
-        assert restype is restypes[ret], "%s returns %s, the table says %s" % (name, ret, restype)
-    text = open(os.path.join(ROOT, "include", "crnerf_blender.h")).read()
+    _abi.check_header("crnerf_blender.h")
+    protos = _abi.prototypes("crnerf_blender.h")
+    assert len(protos) == 4 and not set(protos) & set(_lib.HEADER_SIGNATURES["crnerf.h"])
+    text = _abi.header_text("crnerf_blender.h")
     for name, value in (("TILE_H", _lib.RGBA_TILE_H), ("TILE_W", _lib.RGBA_TILE_W), ("VBLOCK", _lib.RGBA_VBLOCK), ("MAX_RECTS", _lib.RGBA_MAX_RECTS)):
         assert re.search(r"#define CRNERF_RGBA_%s %d\b" % (name, value), text), name
     for name, value in _lib.RGBA_OUT.items():
         assert re.search(r"#define CRNERF_RGBA_OUT_%s %d\b" % (name.upper(), value), text), name
     # the struct's fields, in order
-    body = re.search(r"typedef struct \{(.*?)\} crnerf_rgba_prepare_args;", text, flags=re.S).group(1)
-    fields = [f for decl in body.split(";") for f in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
-    assert fields == [f[0] for f in _lib.RgbaPrepareArgs._fields_]
+    assert [f for _, f, _ in _abi.struct_fields("crnerf_rgba_prepare_args")] == [f[0] for f in _lib.RgbaPrepareArgs._fields_]
 
 
 def ksize(a, b):

@@ -1,46 +1,40 @@
 """Host-side checks of the density query (include/crnerf_geometry.h, crnerf_amd.geometry; no GPU needed): the header against
-_lib.GEOMETRY_SIGNATURES, the exports, every refusal of the four entries -- each call below is refused, or is a no-op, on the host before any device
-work, so the pointers are never followed -- and the refusals of the Python layer that fire before a device tensor is needed."""
+its table of _lib.HEADER_SIGNATURES, the exports, every refusal of the four entries -- each call below is refused, or is a no-op, on the host before
+any device work, so the pointers are never followed -- and the refusals of the Python layer that fire before a device tensor is needed."""
 import ctypes
 import importlib.util
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
+from _abi import bound as _fn, header_text as _header, last_error as _last_error
 from crnerf_amd import _lib, geometry, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POINTS = ["crnerf_sigma_points_f32", "crnerf_sigma_points_bf16"]
 GRID = ["crnerf_sigma_grid_f32", "crnerf_sigma_grid_bf16"]
+TABLE = _lib.HEADER_SIGNATURES["crnerf_geometry.h"]
 P = 4096          # a non-NULL pointer that is never followed
 BIG = 2 ** 31 - 1
 
 
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
-
-
 def test_header_declares_the_four_entries_and_matches_the_signature_table():
-    text = re.sub(r"/\*.*?\*/", "", _header("crnerf_geometry.h"), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (m.group(1).strip(), 0 if params in ("", "void") else params.count(",") + 1)
-    assert sorted(protos) == sorted(_lib.GEOMETRY_SIGNATURES) == sorted(POINTS + GRID)
-    for name, (ret, nparams) in protos.items():
-        restype, argtypes = _lib.GEOMETRY_SIGNATURES[name]
+    _abi.check_header("crnerf_geometry.h")
+    protos = _abi.prototypes("crnerf_geometry.h")
+    assert list(protos) == list(TABLE) == POINTS + GRID
+    for name, (ret, params) in protos.items():
+        restype, argtypes = TABLE[name]
         assert ret == "int" and restype is ctypes.c_int32, name
-        assert nparams == len(argtypes) == (5 if name in POINTS else 9), name
+        assert len(params) == len(argtypes) == (5 if name in POINTS else 9), name
         assert argtypes[-1] is ctypes.c_void_p, name                        # stream
     for name in POINTS:
-        assert _lib.GEOMETRY_SIGNATURES[name][1][3] is ctypes.c_int64       # n
+        assert TABLE[name][1][3] is ctypes.c_int64       # n
     for name in GRID:
-        assert _lib.GEOMETRY_SIGNATURES[name][1][4:7] == [ctypes.c_int32] * 3     # nx, ny, nz
-    # a table of its own, NOT folded into what the older tests count; crnerf.h does not know the entries
-    assert not set(_lib.GEOMETRY_SIGNATURES) & set(_lib.ALL_SIGNATURES)
+        assert TABLE[name][1][4:7] == [ctypes.c_int32] * 3     # nx, ny, nz
+    # in no other header's table (tests/test_host.py: pairwise disjoint, 152 rows in all); crnerf.h does not know the entries
+    assert not set(TABLE) & set().union(*(t for h, t in _lib.HEADER_SIGNATURES.items() if h != "crnerf_geometry.h"))
     assert "crnerf_sigma_" not in _header("crnerf.h")
 
 
@@ -52,33 +46,11 @@ def test_build_and_audit_know_the_new_units_and_the_header():
         return mod
     build = load("crnerf_build_for_geometry", os.path.join(ROOT, "cr-nerf-pytorch_amd", "build.py"))
     audit = load("crnerf_isa_audit_for_geometry", os.path.join(ROOT, "tools", "isa_audit.py"))
-    assert "../../include/crnerf_geometry.h" in build.HEADERS
+    assert all("../../include/" + header in build.HEADERS for header in _lib.HEADER_SIGNATURES)
     for unit in ("sigma_query16.hip", "sigma_query_bf16p.hip"):
         assert unit in build.SOURCES and unit in audit.AUDITED_UNITS
     assert build.PER_FILE_FLAGS["sigma_query_bf16p.hip"] == build.PER_FILE_FLAGS["mlp_forward_bf16p.hip"]      # its sibling's flags
     assert "sigma_query16.hip" not in build.PER_FILE_FLAGS and "mlp_forward16.hip" not in build.PER_FILE_FLAGS
-
-
-def _fn(name):
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.GEOMETRY_SIGNATURES[name]
-    return fn
-
-
-def _last_error():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib.crnerf_last_error()
-
-
-def test_the_loader_binds_the_table():
-    lib = _lib.load()
-    for name, (res, args) in _lib.GEOMETRY_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
 
 
 @pytest.mark.parametrize("name", POINTS)

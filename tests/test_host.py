@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _abi
 import crnerf_amd
 import crnerf_amd.synth as synth
 from crnerf_amd import _lib, ops
@@ -20,30 +21,54 @@ class Args:
     nerf_out_dim, img_wh, pertubeCord = 64, [40, 24], False
 
 
-def header_symbols():
-    text = open(os.path.join(ROOT, "include", "crnerf.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+def header_symbols(name="crnerf.h"):
+    text = re.sub(r"/\*.*?\*/", "", _abi.header_text(name), flags=re.S)
     return sorted(set(re.findall(r"\b(crnerf_[a-z0-9_]+)\s*\(", text)))
 
 
-def header_prototypes():
-    """{symbol: (return type, number of parameters)} of every prototype of include/crnerf.h."""
-    text = open(os.path.join(ROOT, "include", "crnerf.h")).read()
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(crnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
-    return {name: ("".join(ret.split()), 0 if params.strip() == "void" else params.count(",") + 1) for ret, name, params in protos}
+@pytest.mark.parametrize("header", list(_lib.HEADER_SIGNATURES))
+def test_every_header_matches_its_registry_table(header):
+    """The registry against include/: one table per header, each held to its prototypes parameter by parameter (_abi.check_header), no symbol in two
+    tables, and the counts -- a new entry has to be counted here on purpose."""
+    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(_lib.HEADER_SIGNATURES)
+    _abi.check_header(header)
+    assert header_symbols(header) == sorted(_lib.HEADER_SIGNATURES[header])          # nothing that looks like an entry escaped the prototype parser
+    for other, table in _lib.HEADER_SIGNATURES.items():
+        assert other == header or not set(table) & set(_lib.HEADER_SIGNATURES[header]), other
+    assert len(_lib.HEADER_SIGNATURES["crnerf.h"]) == 124 and len(_lib.ALL_SIGNATURES) == 152
+    assert _lib.EXPORTS == list(_lib.ALL_SIGNATURES) == [s for table in _lib.HEADER_SIGNATURES.values() for s in table]
+    assert set(_abi.EXCEPTIONS) <= {(s, re.search(r"\w+$", decl).group()) for h in _lib.HEADER_SIGNATURES
+                                    for s, (_, params) in _abi.prototypes(h).items() for decl in params}      # no exception outlives its parameter
 
 
-def test_header_declares_what_the_binding_expects():
-    assert header_symbols() == sorted(_lib.EXPORTS)
-    # the signature table row by row: as many argtypes as the prototype has parameters, and its return type
-    protos = header_prototypes()
-    assert sorted(protos) == sorted(_lib.SIGNATURES) and len(protos) == 124
-    restypes = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "constchar*": ctypes.c_char_p}
-    for name, (ret, n_params) in protos.items():
-        restype, argtypes = _lib.SIGNATURES[name]
-        assert len(argtypes) == n_params, "%s: %d argtypes for %d parameters" % (name, len(argtypes), n_params)
-        assert restype is restypes[ret], "%s returns %s, the table says %s" % (name, ret, restype)
+def test_every_struct_matches_its_typedef():
+    """Every ctypes.Structure of _lib against the `typedef struct ... crnerf_X;` its docstring names: the field names in order, and every field's
+    type by the rule of the prototypes (a scalar by its width, an array of pointers, any other pointer; `T* f[n]` an array of n pointers)."""
+    found = _abi.structs()
+    assert len(found) == 9 and found["crnerf_render_args"] is _lib.RenderArgs and found["crnerf_sweep_decode_args"] is _lib.SweepDecodeArgs
+    for c_name, cls in found.items():
+        fields = _abi.struct_fields(c_name)
+        assert [f for _, f, _ in fields] == [f for f, _ in cls._fields_], c_name
+        for (c_type, field, n), (_, ct) in zip(fields, cls._fields_):
+            want = _abi.expected_ctype(c_type)
+            assert (ct is want) if n is None else (ct._type_ is want and ct._length_ == n), (c_name, field)
+
+
+def test_load_binds_every_row():
+    lib = _lib.load()
+    for name, (res, args) in _lib.ALL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_build_checks_the_library_against_every_header():
+    """__graft_entry__.build()'s missing-symbol check covers the whole registry: a handle that lacks one symbol of each header has all nine reported."""
+    import types
+    import __graft_entry__ as entry
+    held_back = [next(iter(table)) for table in _lib.HEADER_SIGNATURES.values()]
+    fake = types.SimpleNamespace(**{s: None for s in _lib.ALL_SIGNATURES if s not in held_back})
+    assert entry.missing_symbols(fake) == held_back and len(held_back) == 9
+    assert entry.missing_symbols(ctypes.CDLL(_lib.LIB_PATH)) == []
 
 
 def test_library_exports_every_declared_symbol():
@@ -78,14 +103,6 @@ def test_library_exports_every_declared_symbol():
     lib.crnerf_last_error.restype = ctypes.c_char_p
     assert b"NULL" in lib.crnerf_last_error()
     assert lib.crnerf_posenc_f32(None, None, 0, 15, None) == 0      # empty input is a no-op
-
-
-def test_render_args_struct_matches_header_field_order():
-    text = open(os.path.join(ROOT, "include", "crnerf.h")).read()
-    body = text[text.index("typedef struct crnerf_render_args {"):text.index("} crnerf_render_args;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"\b([a-z_0-9]+)\s*;", body)
-    assert fields == [f[0] for f in _lib.RenderArgs._fields_]
 
 
 def test_nerf_sigma_mirrors_reference_module():

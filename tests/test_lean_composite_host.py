@@ -1,51 +1,34 @@
 """Host-side checks of the launches behind lean=True in the composite precisions (include/crnerf_lean_composite.h, which crnerf_lean.h includes;
-no GPU needed): the header against _lib.LEAN_COMPOSITE_SIGNATURES, the exports, and every refusal -- each call below is refused, or is a no-op, on
-the host before any device work, so the pointers in the argument blocks are never followed."""
+no GPU needed): the header against its table of _lib.HEADER_SIGNATURES, the exports, and every refusal -- each call below is refused, or is a
+no-op, on the host before any device work, so the pointers in the argument blocks are never followed."""
 import ctypes
-import os
-import re
 
 import pytest
 
+import _abi
+from _abi import header_text as _header, last_error as _last_error
 from crnerf_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COARSE = ["crnerf_render_coarse_weights_f32h2", "crnerf_render_coarse_weights_f32x3", "crnerf_render_coarse_weights_f32x3_repair",
           "crnerf_render_coarse_weights_f16"]
 FINE = "crnerf_render_rays_lean_bf16_fine"
 SYMBOLS = COARSE + [FINE]
-
-
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
+TABLE = _lib.HEADER_SIGNATURES["crnerf_lean_composite.h"]
 
 
 def test_header_declares_the_five_entries_and_matches_the_signature_table():
-    text = re.sub(r"/\*.*?\*/", "", _header("crnerf_lean_composite.h"), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (m.group(1).strip(), 0 if params in ("", "void") else params.count(",") + 1)
-    assert sorted(protos) == sorted(_lib.LEAN_COMPOSITE_SIGNATURES) == sorted(SYMBOLS)
-    for name, (ret, nparams) in protos.items():
-        restype, argtypes = _lib.LEAN_COMPOSITE_SIGNATURES[name]
+    _abi.check_header("crnerf_lean_composite.h")
+    protos = _abi.prototypes("crnerf_lean_composite.h")
+    assert list(protos) == list(TABLE) == SYMBOLS
+    for name, (ret, params) in protos.items():
+        restype, argtypes = TABLE[name]
         assert ret == "int" and restype is ctypes.c_int32, name
-        assert nparams == len(argtypes) == 2, name
+        assert len(params) == len(argtypes) == 2, name
         assert argtypes[0] is ctypes.POINTER(_lib.RenderArgs) and argtypes[1] is ctypes.c_void_p, name
     # reachable through crnerf_lean.h, whose own two prototypes and crnerf.h stay as they are
     assert '#include "crnerf_lean_composite.h"' in _header("crnerf_lean.h")
-    assert not set(SYMBOLS) & (set(_lib.SIGNATURES) | set(_lib.LEAN_SIGNATURES))
+    assert not set(SYMBOLS) & (set(_lib.HEADER_SIGNATURES["crnerf.h"]) | set(_lib.HEADER_SIGNATURES["crnerf_lean.h"]))
     assert "crnerf_render_coarse_weights" not in _header("crnerf.h")
-
-
-def _fn(name):
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.LEAN_COMPOSITE_SIGNATURES[name]
-    return fn
 
 
 def _args(ni, **over):
@@ -58,15 +41,9 @@ def _args(ni, **over):
     return a
 
 
-def _last_error():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib.crnerf_last_error()
-
-
 @pytest.mark.parametrize("name", SYMBOLS)
 def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(name):
-    fn = _fn(name)
+    fn = _abi.bound(name)
     ni = 128 if name == FINE else 0
     assert fn(None, None) == -1                                               # CRNERF_ERR_NULL
     assert fn(ctypes.byref(_lib.RenderArgs()), None) == 0                     # n_rays == 0: a no-op
@@ -84,9 +61,7 @@ def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(n
         assert fn(ctypes.byref(_args(128)), None) == -2                       # a coarse-weights entry renders the coarse pass alone
         assert fn(ctypes.byref(_args(ni, n_samples=1)), None) == -2
         assert fn(ctypes.byref(_args(ni, packed_coarse=None)), None) == -1
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_abi_version.restype = ctypes.c_int
-    assert lib.crnerf_abi_version() == 2
+    assert _abi.bound("crnerf_abi_version")() == 2
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f32", "bf16_hc", "nonsense"])

@@ -1,52 +1,37 @@
 """Host-side checks of the lean render on the fp32-accurate split cores (include/crnerf_lean_x.h; no GPU needed): the header against
-_lib.LEAN_X_SIGNATURES, the exports, every refusal of the three entries -- each call below is refused, or is a no-op, on the host before any device
+its table of _lib.HEADER_SIGNATURES, the exports, every refusal of the three entries -- each call below is refused, or is a no-op, on the host before any device
 work, so the pointers in the argument blocks are never followed -- every refusal of ops.render_rays_lean_x that fires before a device tensor is
 needed, and ops.render_rays(lean=True), which keeps refusing these precisions."""
 import ctypes
 import json
 import os
-import re
 
 import pytest
 import torch
 
+import _abi
+from _abi import header_text as _header, last_error as _last_error
 from crnerf_amd import _lib, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["crnerf_render_rays_lean_f32x3", "crnerf_render_rays_lean_f32h2", "crnerf_render_rays_lean_f32x3_repair"]
-
-
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
+TABLE = _lib.HEADER_SIGNATURES["crnerf_lean_x.h"]
 
 
 def test_header_declares_the_three_entries_and_matches_the_signature_table():
-    text = re.sub(r"/\*.*?\*/", "", _header("crnerf_lean_x.h"), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (m.group(1).strip(), 0 if params in ("", "void") else params.count(",") + 1)
-    assert sorted(protos) == sorted(_lib.LEAN_X_SIGNATURES) == sorted(SYMBOLS)
-    for name, (ret, nparams) in protos.items():
-        restype, argtypes = _lib.LEAN_X_SIGNATURES[name]
+    _abi.check_header("crnerf_lean_x.h")
+    protos = _abi.prototypes("crnerf_lean_x.h")
+    assert list(protos) == list(TABLE) == SYMBOLS
+    for name, (ret, params) in protos.items():
+        restype, argtypes = TABLE[name]
         assert ret == "int" and restype is ctypes.c_int32, name
-        assert nparams == len(argtypes) == 2, name
+        assert len(params) == len(argtypes) == 2, name
         assert argtypes[0] is ctypes.POINTER(_lib.RenderArgs) and argtypes[1] is ctypes.c_void_p, name
-    # a table of its own, folded into what the loader binds; crnerf.h does not know the entries
-    others = set(_lib.SIGNATURES) | set(_lib.LEAN_SIGNATURES) | set(_lib.LEAN_COMPOSITE_SIGNATURES) | set(_lib.BLENDER_SIGNATURES) | set(_lib.SWEEP_SIGNATURES)
+    # in no other header's table (tests/test_host.py: the tables are pairwise disjoint and 152 rows in all), bound by the loader; crnerf.h does not
+    # know the entries
+    others = set().union(*(t for h, t in _lib.HEADER_SIGNATURES.items() if h != "crnerf_lean_x.h"))
     assert not set(SYMBOLS) & others and set(SYMBOLS) <= set(_lib.ALL_SIGNATURES)
-    assert len(_lib.ALL_SIGNATURES) == len(others) + 3
     assert "crnerf_render_rays_lean_f32x3" not in _header("crnerf.h") and "crnerf_render_rays_lean_f32h2" not in _header("crnerf.h")
-
-
-def _fn(name):
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.LEAN_X_SIGNATURES[name]
-    return fn
 
 
 def _args(**over):
@@ -59,15 +44,9 @@ def _args(**over):
     return a
 
 
-def _last_error():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib.crnerf_last_error()
-
-
 @pytest.mark.parametrize("name", SYMBOLS)
 def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(name):
-    fn = _fn(name)
+    fn = _abi.bound(name)
     assert fn(None, None) == -1                                               # CRNERF_ERR_NULL
     assert fn(ctypes.byref(_lib.RenderArgs()), None) == 0                     # n_rays == 0: a no-op
     assert fn(ctypes.byref(_args(n_rays=-1)), None) == -2                     # CRNERF_ERR_SHAPE
@@ -81,9 +60,7 @@ def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(n
     for over in (dict(rng_flags=1), dict(z_coarse_out=4096), dict(noise_coarse_out=4096), dict(noise_fine_out=4096)):
         assert fn(ctypes.byref(_args(**over)), None) == -3, over              # CRNERF_ERR_CONFIG: no draws in the lean kernels
         assert _last_error().startswith(b"render_rays_lean: no in-kernel random draws")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_abi_version.restype = ctypes.c_int
-    assert lib.crnerf_abi_version() == 2
+    assert _abi.bound("crnerf_abi_version")() == 2
 
 
 # ---------------------------------------------------------------- ops.render_rays_lean_x

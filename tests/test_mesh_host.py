@@ -1,11 +1,9 @@
 """Host-side checks of the mesh extraction (include/crnerf_mesh.h, crnerf_amd.geometry.Mesh; no GPU needed): the header against
-_lib.MESH_SIGNATURES, the exports, every refusal of the entries -- each call below is refused, or is a no-op, on the host before any device work, so
-the pointers are never followed --, the PLY writer on CPU tensors, the axis and threshold refusals of the geometry layer, and the NumPy restatement
-the GPU tests compare with (tests/_mesh_cases.py) held to the topology a closed surface must have."""
-import ctypes
+its table of _lib.HEADER_SIGNATURES, the exports, every refusal of the entries -- each call below is refused, or is a no-op, on the host before any
+device work, so the pointers are never followed --, the PLY writer on CPU tensors, the axis and threshold refusals of the geometry layer, and the
+NumPy restatement the GPU tests compare with (tests/_mesh_cases.py) held to the topology a closed surface must have."""
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,38 +11,24 @@ import torch
 
 from crnerf_amd import _lib, geometry, ops
 
+import _abi
+from _abi import bound as _fn, header_text as _header, last_error as _last_error
 import _mesh_cases as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 4096          # a non-NULL, 16-byte aligned pointer that is never followed
 BIG = 2 ** 31 - 1
 COUNT, EMIT, BYTES = "crnerf_mesh_count_f32", "crnerf_mesh_emit_f32", "crnerf_mesh_workspace_bytes"
-
-
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
+TABLE = _lib.HEADER_SIGNATURES["crnerf_mesh.h"]
 
 
 def test_header_declares_the_three_entries_and_matches_the_signature_table():
-    text = re.sub(r"/\*.*?\*/", "", _header("crnerf_mesh.h"), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = [p.strip() for p in m.group(3).split(",")]
-        protos[m.group(2)] = (m.group(1).strip(), params)
-    assert sorted(protos) == sorted(_lib.MESH_SIGNATURES) == sorted([COUNT, EMIT, BYTES])
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int": ctypes.c_int32}
-    for name, (ret, params) in protos.items():
-        restype, argtypes = _lib.MESH_SIGNATURES[name]
-        assert ctype[ret] is restype, name
-        assert len(params) == len(argtypes), name
-        for p, a in zip(params, argtypes):
-            want = ctypes.c_void_p if "*" in p else ctype[p.split()[0]]
-            assert a is want, (name, p)
+    _abi.check_header("crnerf_mesh.h")                  # every return type and every parameter, by C type
+    protos = _abi.prototypes("crnerf_mesh.h")
+    assert list(protos) == list(TABLE) == [BYTES, COUNT, EMIT]
     assert len(protos[BYTES][1]) == 3 and len(protos[COUNT][1]) == 8 and len(protos[EMIT][1]) == 15
-    # a table of its own, NOT folded into what the older tests count; the older headers do not know the entries
-    assert not set(_lib.MESH_SIGNATURES) & set(_lib.ALL_SIGNATURES)
-    assert not set(_lib.MESH_SIGNATURES) & set(_lib.GEOMETRY_SIGNATURES)
+    # in no other header's table (tests/test_host.py: pairwise disjoint, 152 rows in all); the older headers do not know the entries
+    assert not set(TABLE) & set().union(*(t for h, t in _lib.HEADER_SIGNATURES.items() if h != "crnerf_mesh.h"))
     assert "crnerf_mesh_" not in _header("crnerf.h") and "crnerf_mesh_" not in _header("crnerf_geometry.h")
 
 
@@ -59,31 +43,9 @@ def test_build_knows_the_unit_and_the_header():
     spec = importlib.util.spec_from_file_location("crnerf_build_for_mesh", os.path.join(ROOT, "cr-nerf-pytorch_amd", "build.py"))
     build = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build)
-    assert "mesh.hip" in build.SOURCES and "../../include/crnerf_mesh.h" in build.HEADERS
+    assert "mesh.hip" in build.SOURCES and all("../../include/" + header in build.HEADERS for header in _lib.HEADER_SIGNATURES)
     assert "-fhonor-nans" in build.PER_FILE_FLAGS["mesh.hip"]          # the inside test and the t fallback are NaN comparisons
     assert "-ffp-contract=off" in build.FLAGS                          # the interpolation: a multiply and an add
-
-
-def _fn(name):
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.MESH_SIGNATURES[name]
-    return fn
-
-
-def _last_error():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib.crnerf_last_error()
-
-
-def test_the_loader_binds_the_table():
-    lib = _lib.load()
-    for name, (res, args) in _lib.MESH_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
 
 
 NEGATIVE = ((-1, 4, 4), (4, -1, 4), (4, 4, -1), (-1, 0, 4), (-2 ** 31, 2, 2))

@@ -1,11 +1,10 @@
 """Host-side checks of the mesh parts (include/crnerf_mesh_parts.h, ops.mesh_parts / mesh_select, crnerf_amd.geometry.Mesh.parts / select / largest /
-drop_small; no GPU needed): the header against _lib.MESH_PARTS_SIGNATURES, the exports, every refusal and every no-op of the entries -- each call
-below is refused, or does nothing, on the host before any device work, so the pointers are never followed --, the ValueErrors of the geometry
-layer, and the NumPy restatement the GPU tests compare with (tests/_mesh_parts_cases.py) held to hand cases and to scipy's connected components."""
-import ctypes
+drop_small; no GPU needed): the header against its table of _lib.HEADER_SIGNATURES, the exports, every refusal and every no-op of the entries --
+each call below is refused, or does nothing, on the host before any device work, so the pointers are never followed --, the ValueErrors of the
+geometry layer, and the NumPy restatement the GPU tests compare with (tests/_mesh_parts_cases.py) held to hand cases and to scipy's connected
+components."""
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,8 @@ import torch
 
 from crnerf_amd import _lib, geometry, ops
 
+import _abi
+from _abi import bound as _fn, header_text as _header, last_error as _last_error
 import _mesh_cases as M
 import _mesh_parts_cases as C
 
@@ -22,30 +23,16 @@ BIG = 2 ** 31 - 1
 BYTES, LABEL, SIZES = "crnerf_mesh_parts_workspace_bytes", "crnerf_mesh_parts_label_i32", "crnerf_mesh_parts_sizes_i32"
 COUNT, EMIT = "crnerf_mesh_parts_select_count", "crnerf_mesh_parts_select_emit_f32"
 SHAPE, NULL, CONFIG = -2, -1, -3          # CRNERF_ERR_*
-
-
-def _header(name):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
+TABLE = _lib.HEADER_SIGNATURES["crnerf_mesh_parts.h"]
 
 
 def test_header_declares_the_five_entries_and_matches_the_signature_table():
-    text = re.sub(r"/\*.*?\*/", "", _header("crnerf_mesh_parts.h"), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        protos[m.group(2)] = (m.group(1).strip(), [p.strip() for p in m.group(3).split(",")])
-    assert sorted(protos) == sorted(_lib.MESH_PARTS_SIGNATURES) == sorted([BYTES, LABEL, SIZES, COUNT, EMIT])
-    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int": ctypes.c_int32}
-    for name, (ret, params) in protos.items():
-        restype, argtypes = _lib.MESH_PARTS_SIGNATURES[name]
-        assert ctype[ret] is restype, name
-        assert len(params) == len(argtypes), name
-        for p, a in zip(params, argtypes):
-            assert a is (ctypes.c_void_p if "*" in p else ctype[p.split()[0]]), (name, p)
+    _abi.check_header("crnerf_mesh_parts.h")            # every return type and every parameter, by C type
+    protos = _abi.prototypes("crnerf_mesh_parts.h")
+    assert list(protos) == list(TABLE) == [BYTES, LABEL, SIZES, COUNT, EMIT]
     assert [len(protos[n][1]) for n in (BYTES, LABEL, SIZES, COUNT, EMIT)] == [2, 8, 8, 9, 16]
-    # a table of its own, NOT folded into what the older tests count; the older headers do not know the entries
-    for other in (_lib.ALL_SIGNATURES, _lib.GEOMETRY_SIGNATURES, _lib.MESH_SIGNATURES):
-        assert not set(_lib.MESH_PARTS_SIGNATURES) & set(other)
+    # in no other header's table (tests/test_host.py: pairwise disjoint, 152 rows in all); the older headers do not know the entries
+    assert not set(TABLE) & set().union(*(t for h, t in _lib.HEADER_SIGNATURES.items() if h != "crnerf_mesh_parts.h"))
     for older in ("crnerf.h", "crnerf_geometry.h", "crnerf_mesh.h"):
         assert "crnerf_mesh_parts_" not in _header(older)
 
@@ -62,31 +49,9 @@ def test_build_and_entry_know_the_unit_and_the_header():
     spec = importlib.util.spec_from_file_location("crnerf_build_for_mesh_parts", os.path.join(ROOT, "cr-nerf-pytorch_amd", "build.py"))
     build = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build)
-    assert "mesh_parts.hip" in build.SOURCES and "../../include/crnerf_mesh_parts.h" in build.HEADERS
-    with open(os.path.join(ROOT, "__graft_entry__.py")) as f:
-        assert "MESH_PARTS_SIGNATURES" in f.read()          # the missing-symbol check counts the new table
-
-
-def _fn(name):
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.MESH_PARTS_SIGNATURES[name]
-    return fn
-
-
-def _last_error():
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib.crnerf_last_error()
-
-
-def test_the_exports_are_present_and_the_loader_binds_the_table():
-    lib = _lib.load()
-    for name, (res, args) in _lib.MESH_PARTS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert "mesh_parts.hip" in build.SOURCES and all("../../include/" + header in build.HEADERS for header in _lib.HEADER_SIGNATURES)
+    import __graft_entry__ as entry                         # the missing-symbol check covers this header's table
+    assert set(entry.missing_symbols(object())) >= set(TABLE)
 
 
 NEGATIVE = ((-1, 4), (4, -1), (-1, -1), (-2 ** 63, 0))

@@ -1,87 +1,51 @@
 """Host-side checks of the appearance sweep, crnerf_crossray_style_stats_f32 / crnerf_crossray_decode_multi_f32 (include/crnerf_sweep.h; no GPU
-needed): the header against _lib.SWEEP_SIGNATURES, the exports, every refusal of the two entry points (each call is refused, or is a no-op, on
+needed): the header against its table of _lib.HEADER_SIGNATURES, the exports, every refusal of the two entry points (each call is refused, or is a no-op, on
 the host: no pointer is followed) and the Python layer's ValueErrors, raised before the library is loaded."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
+import _abi
 from crnerf_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["crnerf_crossray_decode_multi_f32", "crnerf_crossray_style_stats_f32"]
+TABLE = _lib.HEADER_SIGNATURES["crnerf_sweep.h"]
 P = 4096          # a non-NULL "pointer" that is never followed
 
 
-def _header():
-    with open(os.path.join(ROOT, "include", "crnerf_sweep.h")) as f:
-        return f.read()
-
-
-def _prototypes():
-    """{symbol: (return type, number of parameters)} of every prototype of include/crnerf_sweep.h."""
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"^\s*([A-Za-z_][\w\s\*]*?)\b(crnerf_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = m.group(3).strip()
-        protos[m.group(2)] = (m.group(1).strip(), 0 if params in ("", "void") else params.count(",") + 1)
-    return protos
-
-
 def test_companion_header_matches_the_signature_table():
-    protos = _prototypes()
-    assert sorted(protos) == sorted(_lib.SWEEP_SIGNATURES) == SYMBOLS
-    for name, (ret, nparams) in protos.items():
-        restype, argtypes = _lib.SWEEP_SIGNATURES[name]
+    _abi.check_header("crnerf_sweep.h")
+    protos = _abi.prototypes("crnerf_sweep.h")
+    assert sorted(protos) == sorted(TABLE) == SYMBOLS
+    for name, (ret, params) in protos.items():
+        restype, argtypes = TABLE[name]
         assert ret == "int" and restype is ctypes.c_int32, name
-        assert nparams == len(argtypes), name
-    assert len(_lib.SWEEP_SIGNATURES["crnerf_crossray_style_stats_f32"][1]) == 8
-    assert _lib.SWEEP_SIGNATURES["crnerf_crossray_decode_multi_f32"][1] == [ctypes.POINTER(_lib.SweepDecodeArgs), ctypes.c_void_p]
+        assert len(params) == len(argtypes), name
+    assert len(TABLE["crnerf_crossray_style_stats_f32"][1]) == 8
+    assert TABLE["crnerf_crossray_decode_multi_f32"][1] == [ctypes.POINTER(_lib.SweepDecodeArgs), ctypes.c_void_p]
     # disjoint from crnerf.h and its table, which stay as they are
-    assert not set(SYMBOLS) & set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 124
-    with open(os.path.join(ROOT, "include", "crnerf.h")) as f:
-        text = f.read()
-    assert not any(s in text for s in SYMBOLS)
+    assert not set(SYMBOLS) & set(_lib.HEADER_SIGNATURES["crnerf.h"]) and len(_lib.HEADER_SIGNATURES["crnerf.h"]) == 124
+    assert not any(s in _abi.header_text("crnerf.h") for s in SYMBOLS)
 
 
 def test_header_constants_and_struct_match_the_binding():
-    text = _header()
-    consts = dict(re.findall(r"#define (CRNERF_SWEEP_\w+) (\d+)", text))
+    consts = dict(re.findall(r"#define (CRNERF_SWEEP_\w+) (\d+)", _abi.header_text("crnerf_sweep.h")))
     assert int(consts["CRNERF_SWEEP_MAX_STYLES"]) == _lib.SWEEP_MAX_STYLES == 16
     assert int(consts["CRNERF_SWEEP_STATS_FLOATS"]) == _lib.SWEEP_STATS_FLOATS == 64 + 1024
     assert (int(consts["CRNERF_SWEEP_OUT_F32"]), int(consts["CRNERF_SWEEP_OUT_U8"])) == (_lib.SWEEP_OUT_F32, _lib.SWEEP_OUT_U8) == (0, 1)
-    body = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct crnerf_sweep_decode_args \{(.*?)\}", text, flags=re.S).group(1), flags=re.S)
-    fields = [re.search(r"(\w+)\s*$", d).group(1) for d in body.split(";") if d.strip()]
-    assert fields == [n for n, _ in _lib.SweepDecodeArgs._fields_]
-    ctype = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}
-    for decl, (name, ct) in zip([d for d in body.split(";") if d.strip()], _lib.SweepDecodeArgs._fields_):
-        base = decl.split()[0] if "*" not in decl else None
-        assert (ctype[base] is ct) if base else ct in (ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)), name
+    fields = _abi.struct_fields("crnerf_sweep_decode_args")
+    assert [f for _, f, _ in fields] == [n for n, _ in _lib.SweepDecodeArgs._fields_]
+    for (c_type, _, n), (name, ct) in zip(fields, _lib.SweepDecodeArgs._fields_):
+        assert n is None and ct is _abi.expected_ctype(c_type), name
     assert _lib.SWEEP_MAX_STYLES * 196 * 4 == 12544          # the LDS the folded maps take: 12.25 KiB
 
 
-def _lib_handle():
-    assert os.path.exists(_lib.LIB_PATH), "libcrnerf_hip.so missing: run __graft_entry__.build()"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.crnerf_last_error.restype = ctypes.c_char_p
-    return lib
-
-
-def _fn(lib, name):
-    assert hasattr(lib, name), "%s is not exported" % name
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = _lib.SWEEP_SIGNATURES[name]
-    return fn
-
-
 def test_built_library_exports_the_entries():
-    lib = _lib_handle()
     for name in SYMBOLS:
-        _fn(lib, name)
-    lib.crnerf_abi_version.restype = ctypes.c_int
-    assert lib.crnerf_abi_version() == 2
+        _abi.bound(name)
+    assert _abi.bound("crnerf_abi_version")() == 2
 
 
 def _weights(hole=None):
@@ -92,8 +56,7 @@ def _weights(hole=None):
 
 
 def test_style_stats_refusals():
-    lib = _lib_handle()
-    fn = _fn(lib, "crnerf_crossray_style_stats_f32")
+    fn = _abi.bound("crnerf_crossray_style_stats_f32")
     w = _weights()
     ok = dict(styles=P, S=2, HWs=1024, content_HW=4096, weights=w, workspace=P, stats=P)
 
@@ -103,10 +66,10 @@ def test_style_stats_refusals():
     assert call(S=0) == 0 and call(S=0, styles=None, weights=None, workspace=None, stats=None) == 0        # no-op
     for field in ("styles", "weights", "workspace", "stats"):
         assert call(**{field: None}) == -1
-        assert field.encode() in lib.crnerf_last_error()
-    assert call(weights=_weights(hole=7)) == -1 and b"weight" in lib.crnerf_last_error()
+        assert field.encode() in _abi.last_error()
+    assert call(weights=_weights(hole=7)) == -1 and b"weight" in _abi.last_error()
     assert call(S=-1) == -2 and call(HWs=-1) == -2 and call(content_HW=-1) == -2
-    assert call(S=17) == -2 and b"CRNERF_SWEEP_MAX_STYLES" in lib.crnerf_last_error()
+    assert call(S=17) == -2 and b"CRNERF_SWEEP_MAX_STYLES" in _abi.last_error()
     assert call(HWs=0) == -2 and call(content_HW=0) == -2
 
 
@@ -121,20 +84,19 @@ def _args(**over):
 
 
 def test_decode_multi_refusals():
-    lib = _lib_handle()
-    fn = _fn(lib, "crnerf_crossray_decode_multi_f32")
+    fn = _abi.bound("crnerf_crossray_decode_multi_f32")
     call = lambda **over: fn(ctypes.byref(_args(**over)), None)      # noqa: E731
-    assert fn(None, None) == -1 and b"args" in lib.crnerf_last_error()
+    assert fn(None, None) == -1 and b"args" in _abi.last_error()
     assert call(S=0) == 0 and call(HW=0) == 0                                                   # no-ops
     assert call(S=0, content=None, stats=None, workspace=None, out=None) == 0
     for field in ("content", "stats", "weights", "workspace", "out"):
         assert call(**{field: None}) == -1
-        assert field.encode() in lib.crnerf_last_error()
+        assert field.encode() in _abi.last_error()
     hole = _weights(hole=21)
-    assert call(weights=ctypes.cast(hole, ctypes.POINTER(ctypes.c_void_p))) == -1 and b"weight" in lib.crnerf_last_error()
-    assert call(S=17) == -2 and b"CRNERF_SWEEP_MAX_STYLES" in lib.crnerf_last_error()
+    assert call(weights=ctypes.cast(hole, ctypes.POINTER(ctypes.c_void_p))) == -1 and b"weight" in _abi.last_error()
+    assert call(S=17) == -2 and b"CRNERF_SWEEP_MAX_STYLES" in _abi.last_error()
     assert call(S=-1) == -2 and call(HW=-1) == -2 and call(style_HW=-1) == -2 and call(style_HW=0) == -2
-    assert call(out_kind=2) == -3 and call(out_kind=-1) == -3 and b"out_kind" in lib.crnerf_last_error()
+    assert call(out_kind=2) == -3 and call(out_kind=-1) == -3 and b"out_kind" in _abi.last_error()
     assert call(plane_stride=99) == -2                       # planes overlap
     assert call(style_stride=299) == -2                      # float images overlap: 2 * 100 + 100
     assert call(out_kind=1, style_stride=299) == -2          # uint8 frames overlap: 3 * 100

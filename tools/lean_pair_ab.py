@@ -1,7 +1,7 @@
 """Kernel time of the lean inference render on the pair core (crnerf_render_rays_lean_bf16 / _f16) against the full one (crnerf_render_rays_bf16 /
 _f16), one GPU.
 
-    python tools/lean_pair_ab.py [--steps 40] [--warmup 10] [--frame] [--parent-lib PATH] [--out FILE]
+    python tools/lean_pair_ab.py [--steps 40] [--warmup 10] [--frame] [--out FILE]
 
 Bare ABI launches on fixed buffers (ops.render_rays(..., launcher=True): nothing but the C call on the host side), INTERLEAVED F L F' L F L ... so
 that all series see the same clocks; one pair of HIP events around every launch, the first `warmup` rounds discarded; medians reported.  The full
@@ -11,13 +11,10 @@ Next to the measured ratio the tool prints what the MFMA count predicts: a pass 
 and a coarse tile's trunk is 992 of its 1,208 fragments, so the lean kernel issues (992 Sc + 1208 Sf) / (1208 (Sc + Sf)) of the full kernel's MFMAs
 with Sc = ceil(Nc / 64) and Sf = ceil((Nc + Ni) / 64): 0.928 and 0.940.  A count, not a model of the clock: the part is power-governed.
 --frame: additionally one 800 x 800 pipeline.render_frame at 256+256, precision "bf16", in 32,768-ray chunks, full against lean, interleaved; each
-with its torch.cuda.max_memory_allocated (reported, not promised: the Python layer drops the per-chunk tensors either way).
---parent-lib PATH: a libcrnerf_hip.so built from the parent commit.  The full kernel alone is then timed in child processes that alternate between
-that library and this tree's (P N P N), to show that the full kernel did not move.  --full-only is that child's mode."""
+with its torch.cuda.max_memory_allocated (reported, not promised: the Python layer drops the per-chunk tensors either way)."""
 import argparse
 import os
 import statistics
-import subprocess
 import sys
 
 import numpy as np
@@ -53,13 +50,8 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frame", action="store_true")
-    ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--full-only", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from crnerf_amd import _lib
-    if a.full_only:          # a parent library has no lean entry points to bind
-        _lib.LEAN_SIGNATURES.clear()
     import crnerf_amd.synth as synth
     from crnerf_amd import ops
 
@@ -69,9 +61,8 @@ def main():
     def say(s):
         lines.append(s)
         print(s, flush=True)
-    if not a.full_only:
-        say("device: %s; %d timed rounds after %d discarded; a round is F L F' L (full, lean, full again, lean), events around every launch"
-            % (torch.cuda.get_device_name(0), a.steps, a.warmup))
+    say("device: %s; %d timed rounds after %d discarded; a round is F L F' L (full, lean, full again, lean), events around every launch"
+        % (torch.cuda.get_device_name(0), a.steps, a.warmup))
     st = [synth.mlp_state(s, 3.0, 1.0) for s in (1, 2)]
     with torch.no_grad():
         for prec in ("bf16", "f16"):
@@ -80,11 +71,6 @@ def main():
                 rays = torch.from_numpy(synth.rays(R, seed=0)).to(dev)
                 kw = dict(z_steps=torch.linspace(0, 1, nc, device=dev), u=torch.linspace(0, 1, ni, device=dev), launcher=True, precision=prec)
                 full, out_f = ops.render_rays(pc, pf, rays, nc, ni, **kw)
-                if a.full_only:
-                    t = [timed(full) for _ in range(a.warmup + 2 * a.steps)][a.warmup:]
-                    say("%s %5d x (%d+%d): full median %.1f us (min %.1f, max %.1f) over %d launches  [%s]"
-                        % (prec, R, nc, ni, med(t), min(t), max(t), len(t), os.environ.get("CRNERF_LIB_PATH", "this tree's library")))
-                    continue
                 lean, out_l = ops.render_rays(pc, pf, rays, nc, ni, lean=True, **kw)
                 t = {"F": [], "F'": [], "L": []}
                 for i in range(a.warmup + a.steps):
@@ -102,7 +88,7 @@ def main():
                        (q[1] - q[0]) / mf, same))
                 del lean, out_l
             del full, out_f
-        if a.frame and not a.full_only:
+        if a.frame:
             from crnerf_amd import pipeline
 
             class HP:
@@ -139,21 +125,6 @@ def main():
                 "lean %s ms; medians %.1f / %.1f, lean/full %.3f; peak memory above the models full %.3f GB, lean %.3f GB; same image: %s"
                 % (["%.1f" % v for v in ms[False]], ["%.1f" % v for v in ms[True]], med(ms[False]), med(ms[True]), med(ms[True]) / med(ms[False]),
                    peak[False] / 1e9, peak[True] / 1e9, torch.equal(imgs[False], imgs[True])))
-    if a.parent_lib and not a.full_only:
-        say("the full kernel alone, child processes alternating between the parent commit's library (P) and this tree's (N):")
-        for lib in (a.parent_lib, None, a.parent_lib, None):
-            env = dict(os.environ)
-            env.pop("CRNERF_LIB_PATH", None)
-            if lib:
-                env["CRNERF_LIB_PATH"] = os.path.abspath(lib)
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full-only", "--steps", str(a.steps), "--warmup", str(a.warmup)],
-                               env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-            if r.returncode != 0:
-                say("  child failed (%d): %s" % (r.returncode, r.stdout[-400:]))
-                break
-            for ln in r.stdout.splitlines():
-                if "full median" in ln:
-                    say("  %s %s" % ("P" if lib else "N", ln))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
