@@ -334,6 +334,17 @@ EXPORTS = list(ALL_SIGNATURES)          # every symbol the library must export
 if len(set(EXPORTS)) != len(EXPORTS):
     raise ImportError("crnerf_amd._lib: declared by more than one header: %s" % sorted({n for n in EXPORTS if EXPORTS.count(n) > 1}))
 
+# Staged entries: headers that still live beside the sources (csrc/), one table per header in the registry's form.  load() binds them behind the
+# registry loop; they are not counted by ALL_SIGNATURES / EXPORTS or by build()'s missing-symbol check until the header moves into include/ and
+# its table into HEADER_SIGNATURES (tests/test_host.py pins those counts and is edited by that step).
+STAGED_SIGNATURES = {"crnerf_point_features.h": {     # the point-feature query: 64 rgb features (and sigma) at points with a view direction, full walk
+    "crnerf_feature_points_f32": (i32, [vp, vp, vp, vp, vp, i64, vp]),
+    "crnerf_feature_points_bf16": (i32, [vp, vp, vp, vp, vp, i64, vp]),
+}}
+_staged = [n for table in STAGED_SIGNATURES.values() for n in table]
+if len(set(_staged)) != len(_staged) or set(_staged) & set(EXPORTS):
+    raise ImportError("crnerf_amd._lib: a staged entry is declared twice: %s" % sorted(n for n in _staged if _staged.count(n) > 1 or n in EXPORTS))
+
 
 _lib = None
 _lock = threading.Lock()
@@ -360,6 +371,15 @@ def load():
                                      % (LIB_PATH, name, header_of(name))) from None
             fn.restype = res
             fn.argtypes = args
+        for header, table in STAGED_SIGNATURES.items():
+            for name, (res, args) in table.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    raise AttributeError("crnerf_amd: %s does not export %s, which csrc/%s declares: the library does not match that header"
+                                         % (LIB_PATH, name, header)) from None
+                fn.restype = res
+                fn.argtypes = args
         _lib = lib
     return _lib
 

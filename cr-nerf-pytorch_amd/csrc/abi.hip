@@ -12,6 +12,7 @@
 #include "../../include/crnerf_lean.h"
 #include "../../include/crnerf_lean_x.h"
 #include "../../include/crnerf_sweep.h"
+#include "crnerf_point_features.h"
 #include "crossray.h"
 #include "kernels.h"
 #include "layout.h"
@@ -166,6 +167,15 @@ static int sigma_points_entry(const void* packed, const float* xyz, float* sigma
   if (n == 0) return 0;
   REQUIRE(packed, "packed"); REQUIRE(xyz, "xyz"); REQUIRE(sigma, "sigma");
   if (n > SIGMA_MAX_POINTS) return fail(CRNERF_ERR_SHAPE, "sigma_points", "more than 2^31 - 1 points in one call (split the list)");
+  return launch((long)n);
+}
+// every crnerf_feature_points_* (crnerf_point_features.h): the density query's rules, with a direction per point; sigma may be NULL
+template <class Launch>
+static int feature_points_entry(const void* packed, const float* xyz, const float* dirs, float* feature, int64_t n, Launch launch) {
+  if (n < 0) return fail(CRNERF_ERR_SHAPE, "feature_points", "negative n");
+  if (n == 0) return 0;
+  REQUIRE(packed, "packed"); REQUIRE(xyz, "xyz"); REQUIRE(dirs, "dirs"); REQUIRE(feature, "feature");
+  if (n > SIGMA_MAX_POINTS) return fail(CRNERF_ERR_SHAPE, "feature_points", "more than 2^31 - 1 points in one call (split the list)");
   return launch((long)n);
 }
 template <class Launch>
@@ -612,6 +622,14 @@ int crnerf_sigma_grid_f32(const void* packed, const float* xs, const float* ys, 
 int crnerf_sigma_grid_bf16(const void* packed, const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz, float* sigma,
                            void* stream) {
   return sigma_grid_entry(packed, xs, ys, zs, nx, ny, nz, sigma, [&] { return launch_sigma_grid_bf16p(packed, xs, ys, zs, nx, ny, nz, sigma, (hipStream_t)stream); });
+}
+
+// crnerf_point_features.h (staged beside the sources): the point-feature query.  A launcher sees a point count in [1, 2^31 - 1] and no NULL but sigma.
+int crnerf_feature_points_f32(const void* packed, const float* xyz, const float* dirs, float* feature, float* sigma, int64_t n, void* stream) {
+  return feature_points_entry(packed, xyz, dirs, feature, n, [&](long P) { return launch_feature_points16(packed, xyz, dirs, feature, sigma, P, (hipStream_t)stream); });
+}
+int crnerf_feature_points_bf16(const void* packed, const float* xyz, const float* dirs, float* feature, float* sigma, int64_t n, void* stream) {
+  return feature_points_entry(packed, xyz, dirs, feature, n, [&](long P) { return launch_feature_points_bf16p(packed, xyz, dirs, feature, sigma, P, (hipStream_t)stream); });
 }
 
 size_t crnerf_packed_mlp_f16_bytes(void) { return PACKEDB_BYTES; }

@@ -175,6 +175,10 @@ int launch_sigma_points16(const void* packed, const float* xyz, float* sigma, lo
 int launch_sigma_grid16(const void* packed, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float* sigma, hipStream_t stream);
 int launch_sigma_points_bf16p(const void* packed, const float* xyz, float* sigma, long n, hipStream_t stream);
 int launch_sigma_grid_bf16p(const void* packed, const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, float* sigma, hipStream_t stream);
+// point-feature query (crnerf_point_features.h; feature_query16.hip, feature_query_bf16p.hip): feature[n][64] (and sigma[n] unless NULL) at xyz[n][3]
+// seen from dirs[n][3], one full walk per tile.  The point count is in [1, 2^31 - 1] and only sigma may be NULL: abi.hip has checked
+int launch_feature_points16(const void* packed, const float* xyz, const float* dirs, float* feature, float* sigma, long n, hipStream_t stream);
+int launch_feature_points_bf16p(const void* packed, const float* xyz, const float* dirs, float* feature, float* sigma, long n, hipStream_t stream);
 
 
 size_t content_backward_workspace_floats(long HW);

@@ -8,6 +8,9 @@ what mesh extraction, occupancy visualisation and point-cloud export start from 
     extract_mesh(model, lo, hi, resolution, threshold)      density_grid(...).mesh(threshold); keep_largest=True: its .largest()
     Mesh.parts()                                  a MeshParts: count, vertex_part [V], face_part [F], n_vertices [K], n_faces [K]
     Mesh.largest(n=1) / .drop_small(min_faces) / .select(keep)      a new Mesh without the floaters: whole parts removed, rows and order kept
+    feature_points(model, xyz, dirs)              ([n,64], [n]) the 64 rgb features and sigma at xyz seen from dirs [n,3]; one launch, full walk
+    point_colors(model, decoder, style, xyz, dirs)          [n,3] in [0,1]: the features decoded by the cross-ray decoder under one appearance
+    Mesh.colorize(model, decoder, style, dirs=None)         a new Mesh with colors [V,3] (dirs None: -normals); save_ply writes red green blue
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
@@ -59,11 +62,23 @@ class DensityGrid:
 
 class Mesh:
     """An indexed triangle mesh: vertices [V,3] float32, faces [F,3] int32 (vertex ids, counter-clockwise seen from outside the dense region),
-    normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None."""
-    __slots__ = ("vertices", "faces", "normals")
+    normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None, colors [V,3] float32 in [0,1] (colorize) or None."""
+    __slots__ = ("vertices", "faces", "normals", "colors")
 
-    def __init__(self, vertices, faces, normals=None):
-        self.vertices, self.faces, self.normals = vertices, faces, normals
+    def __init__(self, vertices, faces, normals=None, colors=None):
+        self.vertices, self.faces, self.normals, self.colors = vertices, faces, normals, colors
+
+    @torch.no_grad()
+    def colorize(self, model, decoder, style_feature, dirs=None, precision="f32"):
+        """A new Mesh with colors [V,3] float32 in [0,1]: point_colors at the vertices (same vertices, faces and normals, not copied).
+        dirs [V,3]: the view direction per vertex; None: -normals, the viewer looking straight at the surface (a mesh without normals: ValueError).
+        A zero normal (the density gradient vanishes) gives a zero direction, which is defined: the embedding of (0, 0, 0).  The colours depend
+        on the set of vertices decoded together (point_colors): colorize after removing floaters, not before, if they are to be the clean mesh's."""
+        if dirs is None:
+            if self.normals is None:
+                raise ValueError("crnerf_amd.geometry: colorize: the mesh has no normals to look along; pass dirs [V,3]")
+            dirs = -self.normals
+        return Mesh(self.vertices, self.faces, self.normals, point_colors(model, decoder, style_feature, self.vertices, dirs, precision=precision))
 
     @torch.no_grad()
     def parts(self):
@@ -127,8 +142,8 @@ class Mesh:
         return Mesh(*_select(self, parts, (parts.n_faces >= int(min_faces)).to(torch.uint8)))
 
     def save_ply(self, path):
-        """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals) per vertex, `uchar int` vertex_indices per face.  Copies to
-        the host itself; needs no third-party package."""
+        """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals, then uchar red green blue when it has colors:
+        (c.clamp(0, 1) * 255) truncated) per vertex, `uchar int` vertex_indices per face.  Copies to the host itself; needs no third-party package."""
         v = self.vertices.detach().to("cpu", torch.float32)
         f = self.faces.detach().to("cpu", torch.int32)
         if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
@@ -140,15 +155,24 @@ class Mesh:
                 raise ValueError("crnerf_amd.geometry: save_ply: normals %s do not match vertices %s" % (tuple(n.shape), tuple(v.shape)))
             v = torch.cat((v, n), dim=1)
             props += ["nx", "ny", "nz"]
+        vrows = _little_endian(v.contiguous())
+        uprops = []
+        if self.colors is not None:
+            c = self.colors.detach().to("cpu", torch.float32)
+            if tuple(c.shape) != (v.shape[0], 3):
+                raise ValueError("crnerf_amd.geometry: save_ply: colors %s do not match %d vertices" % (tuple(c.shape), v.shape[0]))
+            # the video path's rule (video.render_video): clamp to [0,1], times 255, truncated
+            vrows = torch.cat((vrows.view(torch.uint8).reshape(v.shape[0], 4 * len(props)), (c.clamp(0, 1) * 255).to(torch.uint8)), dim=1)
+            uprops = ["red", "green", "blue"]
         header = "".join(["ply\nformat binary_little_endian 1.0\ncomment crnerf_amd.geometry\nelement vertex %d\n" % v.shape[0]]
-                         + ["property float %s\n" % p for p in props]
+                         + ["property float %s\n" % p for p in props] + ["property uchar %s\n" % p for p in uprops]
                          + ["element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]])
         rows = torch.empty(f.shape[0], 13, dtype=torch.uint8)      # one count byte, three little-endian int32
         rows[:, 0] = 3
         rows[:, 1:] = _little_endian(f.contiguous()).view(torch.uint8).reshape(-1, 12)
         with open(path, "wb") as out:
             out.write(header.encode("ascii"))
-            out.write(_little_endian(v.contiguous()).numpy().tobytes())
+            out.write(vrows.numpy().tobytes())
             out.write(rows.numpy().tobytes())
 
 
@@ -178,7 +202,10 @@ def _parts_of(mesh, parts):
 
 
 def _select(mesh, parts, keep):
-    return ops.mesh_select(mesh.vertices, mesh.faces, mesh.normals, parts.vertex_part, parts.face_part, keep)
+    v, f, n = ops.mesh_select(mesh.vertices, mesh.faces, mesh.normals, parts.vertex_part, parts.face_part, keep)
+    # the colours of the kept vertices: a vertex stays when its part does, rows in their original order (include/crnerf_mesh_parts.h, Selection)
+    c = None if mesh.colors is None else mesh.colors[keep.bool()[parts.vertex_part.long()]]
+    return v, f, n, c
 
 
 _HOST_IS_LITTLE =struct.pack("=H", 1) == struct.pack("<H", 1)
@@ -211,6 +238,44 @@ def sigma_points(model, xyz, precision="f32"):
     name = ops._sigma_query_core(precision, "sigma_points")
     ops._sigma_input(xyz, "xyz", "sigma_points", points=True)
     return ops.sigma_points(model.packed_weights(name), xyz, precision=precision)
+
+
+@torch.no_grad()
+def feature_points(model, xyz, dirs, precision="f32"):
+    """(feature [n,64], sigma [n]) at xyz [n,3] seen from dirs [n,3] (float32, contiguous, on the GPU): ops.feature_points on the model's pack.
+    Domain |coordinate| < 64, points and directions: documented, not checked."""
+    name = ops._sigma_query_core(precision, "feature_points")
+    _check_point_features(xyz, dirs, "feature_points")
+    return ops.feature_points(model.packed_weights(name), xyz, dirs, precision=precision)
+
+
+@torch.no_grad()
+def point_colors(model, decoder, style_feature, xyz, dirs, precision="f32"):
+    """colours [n,3] float32 in [0,1] of the points xyz [n,3] seen from dirs [n,3], in the appearance of style_feature: the model's 64 rgb features
+    at the points (one launch, ops.feature_points) decoded by the cross-ray decoder exactly as a rendered image's feature grid is --
+    ops.crossray_decode(feature, style, decoder.decoder_tensors()), transposed and clamped.  decoder: models["decoder"], a style_net;
+    style_feature: enc_a(style_img), [1,64,h,w].
+    The colours depend on the SET of points decoded together: the decoder's cross-ray statistics (mean and Gram) run over the content it is
+    handed, just as a pixel's colour depends on its image in this model.  Decode a mesh's vertices, or a cloud, in one call -- a chunked call
+    gives every chunk its own statistics.  n == 0: [0,3], the decoder is not called.  A coloured point cloud: point_colors(..., g.occupied(t), dirs)."""
+    name = ops._sigma_query_core(precision, "point_colors")
+    _check_point_features(xyz, dirs, "point_colors")
+    if xyz.shape[0] == 0:
+        return torch.empty(0, 3, dtype=torch.float32, device=xyz.device)
+    from .models.linearStyleTransfer import _pixel_major
+    style_pm, _ = _pixel_major(style_feature)
+    feature, _ = ops.feature_points(model.packed_weights(name), xyz, dirs, precision=precision, want_sigma=False)
+    return ops.crossray_decode(feature, style_pm, decoder.decoder_tensors()).t().clamp(0.0, 1.0).contiguous()
+
+
+def _check_point_features(xyz, dirs, what):
+    """float32, contiguous, on the device, a direction per point: before the model is asked for its pack."""
+    for t, n in ((xyz, "xyz"), (dirs, "dirs")):
+        ops._sigma_input(t, n, what, points=True, on_device=False)
+    if xyz.shape[0] != dirs.shape[0]:
+        raise ValueError("crnerf_amd: %s: xyz has %d rows and dirs has %d; a direction per point" % (what, xyz.shape[0], dirs.shape[0]))
+    for t, n in ((xyz, "xyz"), (dirs, "dirs")):
+        ops._sigma_input(t, n, what, points=True)
 
 
 @torch.no_grad()

@@ -459,6 +459,35 @@ def sigma_points(packed, xyz, precision="f32"):
     return out
 
 
+_FEATURE_QUERY = {"f32": "crnerf_feature_points_f32", "bf16": "crnerf_feature_points_bf16"}   # csrc/crnerf_point_features.h (staged)
+
+
+def feature_points(packed, xyz, dirs, precision="f32", want_sigma=True):
+    """(feature [n,64], sigma [n] or None) of the model behind `packed` (pack_mlp_weights(..., precision)) at xyz [n,3] seen from dirs [n,3]: one
+    launch that reads the point and its direction, builds both embeddings in registers and walks the whole weight stream
+    (csrc/crnerf_point_features.h).  feature rows are pixel-major: what crossray_decode reads in place.  precision "f32": bit-identical to
+    mlp_forward(packed, cat(posenc(xyz, 15), posenc(dirs, 4)))[:, :64] and [:, 64]; "bf16": the bf16 matrix cores with the fused renderer's
+    embeddings.  want_sigma=False: sigma is not stored and None is returned for it.  dirs are taken as given (not normalised).
+    Domain: |coordinate| < 64, for points and directions (not checked)."""
+    what = "feature_points"
+    name = _sigma_query_core(precision, what)
+    for t, n in ((xyz, "xyz"), (dirs, "dirs")):      # every shape before any device
+        _sigma_input(t, n, what, points=True, on_device=False)
+    if xyz.shape[0] != dirs.shape[0]:
+        raise ValueError("crnerf_amd: feature_points: xyz has %d rows and dirs has %d; a direction per point" % (xyz.shape[0], dirs.shape[0]))
+    xp, dp = _sigma_input(xyz, "xyz", what, points=True), _sigma_input(dirs, "dirs", what, points=True)      # (both on the current device)
+    n = xyz.shape[0]
+    feature = torch.empty(n, 64, dtype=torch.float32, device=xyz.device)
+    sigma = torch.empty(n, dtype=torch.float32, device=xyz.device) if want_sigma else None
+    if n == 0:
+        return feature, sigma
+    lib = _lib.load()
+    _check_pack(lib, name, packed)
+    fn = _FEATURE_QUERY[name]
+    _lib.check(getattr(lib, fn)(ctypes.c_void_p(packed.data_ptr()), xp, dp, _lib.dev_ptr(feature), _lib.dev_ptr(sigma), n, _lib.stream_ptr()), fn)
+    return feature, sigma
+
+
 def sigma_grid(packed, xs, ys, zs, precision="f32", out=None):
     """sigma [nz, ny, nx] at the nodes (xs[ix], ys[iy], zs[iz]) of the grid the three axis tensors span (any values: non-uniform grids and slabs of
     a larger grid are grids) -- sigma_points without the point list: 4 bytes per point leave, the axes are all that is read.  out=: a contiguous

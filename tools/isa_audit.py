@@ -49,7 +49,7 @@ CSRC = os.path.join(ROOT, "cr-nerf-pytorch_amd", "csrc")
 AUDITED_UNITS = ["render_fused_h2.hip", "mlp_forward_h2.hip", "mlp_backward_h2.hip", "render_fused_x3.hip", "mlp_forward_x3.hip",
                  "mlp_backward_x3.hip", "mlp_train16.hip", "render_fused16.hip", "mlp_forward16.hip", "render_fused_bf16p.hip",
                  "mlp_forward_bf16p.hip", "render_fused_bf16p_f16.hip", "mlp_forward_bf16p_f16.hip", "render_fused_lean_h2.hip",
-                 "render_fused_lean_x3.hip", "sigma_query16.hip", "sigma_query_bf16p.hip"]
+                 "render_fused_lean_x3.hip", "sigma_query16.hip", "sigma_query_bf16p.hip", "feature_query16.hip", "feature_query_bf16p.hip"]
 
 MFMA_PASSES = {  # opcode prefix -> (passes, is_xdl)
     "v_mfma_f32_32x32x16_f16": (8, True), "v_mfma_f32_32x32x16_bf16": (8, True),
