@@ -341,7 +341,14 @@ STAGED_SIGNATURES = {"crnerf_point_features.h": {     # the point-feature query:
     "crnerf_feature_points_f32": (i32, [vp, vp, vp, vp, vp, i64, vp]),
     "crnerf_feature_points_bf16": (i32, [vp, vp, vp, vp, vp, i64, vp]),
 }}
-_staged = [n for table in STAGED_SIGNATURES.values() for n in table]
+# A second staged mapping of the same form (tests/test_point_features_host.py pins the first to its one header): the mesh track's staged headers.
+STAGED_MESH_SIGNATURES = {"crnerf_mesh_simplify.h": {   # mesh simplification by vertex clustering: count, then emit; the grid as nine scalars
+    "crnerf_mesh_cluster_workspace_bytes": (usz, [i64, i64, i64]),
+    "crnerf_mesh_cluster_count_f32": (i32, [vp, vp, i64, i64, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, vp]),
+    "crnerf_mesh_cluster_emit_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
+}}
+STAGED_MAPPINGS = (STAGED_SIGNATURES, STAGED_MESH_SIGNATURES)      # what load() binds behind the registry, in this order
+_staged = [n for mapping in STAGED_MAPPINGS for table in mapping.values() for n in table]
 if len(set(_staged)) != len(_staged) or set(_staged) & set(EXPORTS):
     raise ImportError("crnerf_amd._lib: a staged entry is declared twice: %s" % sorted(n for n in _staged if _staged.count(n) > 1 or n in EXPORTS))
 
@@ -371,7 +378,7 @@ def load():
                                      % (LIB_PATH, name, header_of(name))) from None
             fn.restype = res
             fn.argtypes = args
-        for header, table in STAGED_SIGNATURES.items():
+        for header, table in itertools.chain.from_iterable(mapping.items() for mapping in STAGED_MAPPINGS):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(lib, name)

@@ -11,6 +11,8 @@ what mesh extraction, occupancy visualisation and point-cloud export start from 
     feature_points(model, xyz, dirs)              ([n,64], [n]) the 64 rgb features and sigma at xyz seen from dirs [n,3]; one launch, full walk
     point_colors(model, decoder, style, xyz, dirs)          [n,3] in [0,1]: the features decoded by the cross-ray decoder under one appearance
     Mesh.colorize(model, decoder, style, dirs=None)         a new Mesh with colors [V,3] (dirs None: -normals); save_ply writes red green blue
+    Mesh.simplify(cell, lo=None, hi=None)         a new Mesh with one vertex per occupied cell of a grid of `cell`-sized cells (vertex clustering);
+                                                  extract_mesh(..., simplify_cell=c) ends with it
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
@@ -19,6 +21,10 @@ dense region, the same bytes on every run; count, one read-back of the two total
 The parts (include/crnerf_mesh_parts.h): connected components by shared vertex, labelled by a lock-free union-find on the device, ids ascending
 in the part's smallest vertex id; a filtered mesh is the original minus whole parts -- rows copied byte for byte, order kept, ids renumbered --
 and again the same bytes on every run.  One read-back for the labels (K), one for a selection (V', F').
+Simplification (csrc/crnerf_mesh_simplify.h): the mesh above follows the sampling grid, about six triangles per surface cell; vertex clustering
+makes it follow a cell size of the caller's -- one vertex per occupied cell at the members' mean (exact integer sums: the same bytes on every
+run), collapsed and duplicate faces dropped, normals and colours averaged.  Count, one read-back (V', F'), emit.  The order of a pipeline:
+floaters first, then simplify, then colorize (or colorize first: the colours are averaged).
 Inference only; GPU tensors only: like every op of the package there is no CPU fallback.
 
 Domain: |coordinate| < 64.  Below it the kernels' embedding is the routine the stand-alone posenc uses (which switches to ocml's sincosf there);
@@ -62,7 +68,9 @@ class DensityGrid:
 
 class Mesh:
     """An indexed triangle mesh: vertices [V,3] float32, faces [F,3] int32 (vertex ids, counter-clockwise seen from outside the dense region),
-    normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None, colors [V,3] float32 in [0,1] (colorize) or None."""
+    normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None, colors [V,3] float32 in [0,1] (colorize) or None.
+    Every method returns a new Mesh and leaves this one as it is.  Order of a pipeline: floaters first (largest / drop_small / select), then
+    simplify, then colorize -- or colorize before simplify, which averages the colours it is handed."""
     __slots__ = ("vertices", "faces", "normals", "colors")
 
     def __init__(self, vertices, faces, normals=None, colors=None):
@@ -141,6 +149,53 @@ class Mesh:
         parts = _parts_of(self, parts)
         return Mesh(*_select(self, parts, (parts.n_faces >= int(min_faces)).to(torch.uint8)))
 
+    @torch.no_grad()
+    def simplify(self, cell, lo=None, hi=None):
+        """A new Mesh simplified by vertex clustering (csrc/crnerf_mesh_simplify.h states every rule): the box [lo, hi] is cut into cells of size
+        `cell` -- a positive float, or (cx, cy, cz) --, n_a = max(1, ceil((hi_a - lo_a) / cell_a)) of them on axis a, and the vertices of a cell
+        become one vertex at their mean.  A face whose corners fall into fewer than three cells is dropped; of the faces over the same three cells
+        the first stays; the kept faces keep their order and orientation.  Normals and colours are carried when present -- the normalised mean and
+        the mean of the members' --, None stays None.  lo / hi: 3-sequences; None: the vertices' bounding box (one extra read-back, of six floats);
+        a vertex outside the box belongs to the nearest border cell.  An empty mesh gives an empty mesh, without a read-back.
+        Order: floaters first (largest / drop_small: a small cell can merge a floater into the surface it hovers over), then simplify, then
+        colorize -- or colorize first and let simplify average the colours.  A cell that no kept face uses leaves an unused vertex: drop_small(1)
+        removes those.  ValueError: a cell that is not finite and > 0, a bound that is not finite, hi < lo, more than 2^20 cells on an axis or
+        more than 2^31 - 1 in all."""
+        what = "crnerf_amd.geometry: simplify"
+        try:
+            cells = [float(cell)] * 3 if not hasattr(cell, "__len__") else [float(c) for c in cell]
+        except (TypeError, ValueError):
+            cells = []
+        if len(cells) != 3:
+            raise ValueError("%s: cell must be a positive float or a 3-sequence of them, got %r" % (what, cell))
+        if not all(math.isfinite(c) and c > 0.0 for c in cells):
+            raise ValueError("%s: cell must be finite and > 0, got %r" % (what, cell))
+        bounds = []
+        for name, b in (("lo", lo), ("hi", hi)):
+            if b is not None:
+                try:
+                    b = [float(x) for x in b]
+                except (TypeError, ValueError):
+                    b = []
+                if len(b) != 3 or not all(math.isfinite(x) for x in b):
+                    raise ValueError("%s: %s must be a 3-sequence of finite floats" % (what, name))
+            bounds.append(b)
+        lo, hi = bounds
+        if lo is not None and hi is not None:      # before the device is needed
+            n = _cluster_cells(lo, hi, cells, what)
+        if self.vertices.shape[0] == 0:
+            empty = self.vertices.new_empty((0, 3))
+            return Mesh(empty, self.faces.new_empty((0, 3)), None if self.normals is None else empty.clone(),
+                        None if self.colors is None else empty.clone())
+        if lo is None or hi is None:
+            box = torch.stack((self.vertices.min(dim=0).values, self.vertices.max(dim=0).values)).tolist()
+            lo, hi = box[0] if lo is None else lo, box[1] if hi is None else hi
+            if not all(math.isfinite(x) for x in lo + hi):
+                raise ValueError("%s: the vertices' bounding box is not finite; pass lo and hi" % what)
+            n = _cluster_cells(lo, hi, cells, what)
+        v, f, nrm, col, _ = ops.mesh_cluster(self.vertices, self.faces, lo, cells, n, normals=self.normals, colors=self.colors)
+        return Mesh(v, f, nrm, col)
+
     def save_ply(self, path):
         """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals, then uchar red green blue when it has colors:
         (c.clamp(0, 1) * 255) truncated) per vertex, `uchar int` vertex_indices per face.  Copies to the host itself; needs no third-party package."""
@@ -199,6 +254,22 @@ def _parts_of(mesh, parts):
         raise ValueError("crnerf_amd.geometry: parts labels %d vertices and %d faces, the mesh has %d and %d"
                          % (parts.vertex_part.shape[0], parts.face_part.shape[0], mesh.vertices.shape[0], mesh.faces.shape[0]))
     return parts
+
+
+def _cluster_cells(lo, hi, cell, what):
+    """n_a = max(1, ceil((hi_a - lo_a) / cell_a)) in Python floats, held to what the clustering grid may be."""
+    for a in range(3):
+        if hi[a] < lo[a]:
+            raise ValueError("%s: hi must not lie below lo, got lo = %r and hi = %r" % (what, lo, hi))
+    n = []
+    for a in range(3):
+        q = (hi[a] - lo[a]) / cell[a]
+        if not q <= 2 ** 20:      # (an infinite quotient too)
+            raise ValueError("%s: cell = %r cuts the box into more than 2^20 cells on an axis" % (what, cell))
+        n.append(max(1, math.ceil(q)))
+    if n[0] * n[1] * n[2] > 2 ** 31 - 1:
+        raise ValueError("%s: cell = %r cuts the box into %d x %d x %d cells, more than 2^31 - 1 in all" % (what, cell, n[0], n[1], n[2]))
+    return n
 
 
 def _select(mesh, parts, keep):
@@ -311,10 +382,15 @@ def density_grid(model, lo, hi, resolution, precision="f32"):
 
 
 @torch.no_grad()
-def extract_mesh(model, lo, hi, resolution, threshold, precision="f32", keep_largest=False):
+def extract_mesh(model, lo, hi, resolution, threshold, precision="f32", keep_largest=False, simplify_cell=None):
     """density_grid(model, lo, hi, resolution, precision).mesh(threshold): the surface of the box's density as a Mesh.  keep_largest=True: its
-    .largest(1) -- the part with the most faces, the floaters of a trained density gone."""
+    .largest(1) -- the part with the most faces, the floaters of a trained density gone.  simplify_cell=c: then its .simplify(c), in that order
+    -- extract, largest when asked, simplify (over the bounding box of what is left); None: the mesh as it is."""
     if math.isnan(float(threshold)):      # before the grid is paid for
         raise ValueError("crnerf_amd.geometry: mesh: the threshold is NaN")
+    if simplify_cell is not None:
+        Mesh(torch.empty(0, 3), torch.empty(0, 3, dtype=torch.int32)).simplify(simplify_cell)      # a bad cell: refused before the grid is paid for
     mesh = density_grid(model, lo, hi, resolution, precision=precision).mesh(threshold)
-    return mesh.largest(1) if keep_largest else mesh
+    if keep_largest:
+        mesh = mesh.largest(1)
+    return mesh if simplify_cell is None else mesh.simplify(simplify_cell)

@@ -2,6 +2,7 @@
 current stream.  Every function here runs on the GPU or raises."""
 import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -638,6 +639,71 @@ def mesh_select(vertices, faces, normals, vertex_part, face_part, keep):
         _lib.check(lib.crnerf_mesh_parts_select_emit_f32(vp_, np_, fp, vpp, fpp, V, F, K, kp, p(workspace), Vk, Fk, p(out_v),
                                                          None if out_n is None else p(out_n), p(out_f), st), "crnerf_mesh_parts_select_emit_f32")
     return out_v, out_f, out_n
+
+
+def _cluster_grid(lo, cell, n, what):
+    """(lo, cell as float32-rounded floats, n as ints) of a clustering grid, held to what the library accepts: no device is needed."""
+    try:
+        exact = all(int(v) == v for v in n)
+        lo, cell, n = [float(v) for v in lo], [float(v) for v in cell], [int(v) for v in n]
+    except (TypeError, ValueError):
+        lo = cell = n = ()
+        exact = False
+    if len(lo) != 3 or len(cell) != 3 or len(n) != 3 or not exact:
+        raise ValueError("crnerf_amd: %s expects lo and cell as 3-sequences of floats and n as a 3-sequence of ints" % what)
+    lo, cell = [ctypes.c_float(v).value for v in lo], [ctypes.c_float(v).value for v in cell]      # what the library is handed
+    for v in cell:
+        if not (math.isfinite(v) and v > 0.0 and math.isfinite(ctypes.c_float(1.0 / v).value)):
+            raise ValueError("crnerf_amd: %s: cell must be finite and > 0 as float32, with a finite reciprocal; got %r" % (what, cell))
+    for v in lo:
+        if not math.isfinite(v):
+            raise ValueError("crnerf_amd: %s: lo must be finite as float32, got %r" % (what, lo))
+    if min(n) < 1 or max(n) > 2 ** 20:
+        raise ValueError("crnerf_amd: %s: n must hold 1 to 2^20 cells on every axis, got %r" % (what, n))
+    if n[0] * n[1] * n[2] > 2 ** 31 - 1:
+        raise ValueError("crnerf_amd: %s: n = %d x %d x %d is more than 2^31 - 1 cells" % (what, n[0], n[1], n[2]))
+    return lo, cell, n
+
+
+def mesh_cluster(vertices, faces, lo, cell, n, normals=None, colors=None):
+    """The mesh simplified by vertex clustering on the device (csrc/crnerf_mesh_simplify.h states every rule: one vertex per occupied cell of the
+    n[0] x n[1] x n[2] grid of cell-sized cells whose first corner is lo; cluster ids ascending in the smallest member id; positions, normals and
+    colours from exact integer sums; collapsed faces dropped, of the faces over the same three clusters the first kept; content deterministic).
+    vertices [V,3] float32, faces [F,3] int32, normals / colors [V,3] float32 or None: contiguous, on the device, as they are; lo, cell:
+    3-sequences of floats (rounded to float32); n: 3 ints.  Returns (vertices' [V',3], faces' [F',3], normals' or None, colors' or None,
+    vertex_cluster [V] int32).  Count, ONE read-back of V' and F' (the only synchronisation), allocate, emit."""
+    what = "mesh_cluster"
+    vp_ = fp = np_ = cp = None
+    for on_device in (False, True):      # every shape and dtype before any device
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        V = vertices.shape[0]
+        fp = _parts_input(faces, "faces", what, torch.int32, cols=3, on_device=on_device)
+        F = faces.shape[0]
+        np_ = None if normals is None else _parts_input(normals, "normals", what, torch.float32, cols=3, rows=V, on_device=on_device)
+        cp = None if colors is None else _parts_input(colors, "colors", what, torch.float32, cols=3, rows=V, on_device=on_device)
+        if not on_device:
+            lo, cell, n = _cluster_grid(lo, cell, n, what)
+    dev = vertices.device
+    lib = _lib.load()
+    st = _lib.stream_ptr()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    grid = lo + cell + n
+    vertex_cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    Vk = Fk = 0
+    if V:
+        workspace = torch.empty(max(int(lib.crnerf_mesh_cluster_workspace_bytes(V, F, n[0] * n[1] * n[2])), 16), dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.crnerf_mesh_cluster_count_f32(vp_, fp, V, F, *grid, p(workspace), p(vertex_cluster), p(counts), st), "crnerf_mesh_cluster_count_f32")
+        Vk, Fk = counts.tolist()
+    out_v = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+    out_n = None if normals is None else torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    out_c = None if colors is None else torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    if Vk or Fk:
+        _lib.check(lib.crnerf_mesh_cluster_emit_f32(vp_, np_, cp, fp, p(vertex_cluster), V, F, *grid, p(workspace), Vk, Fk, p(out_v),
+                                                    None if out_n is None else p(out_n), None if out_c is None else p(out_c), p(out_f), st),
+                   "crnerf_mesh_cluster_emit_f32")
+    return out_v, out_f, out_n, out_c, vertex_cluster
 
 
 def composite(raw, z, noise=None, noise_std=0.0):
