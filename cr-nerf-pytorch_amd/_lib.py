@@ -348,7 +348,15 @@ STAGED_MESH_SIGNATURES = {"crnerf_mesh_simplify.h": {   # mesh simplification by
     "crnerf_mesh_cluster_emit_f32": (i32, [vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp]),
 }}
 STAGED_MAPPINGS = (STAGED_SIGNATURES, STAGED_MESH_SIGNATURES)      # what load() binds behind the registry, in this order
-_staged = [n for mapping in STAGED_MAPPINGS for table in mapping.values() for n in table]
+# A third staged mapping of the same form (tests/test_mesh_simplify_host.py pins the second to its one header and STAGED_MAPPINGS to its two
+# mappings): load() binds it behind STAGED_MAPPINGS.
+STAGED_SMOOTH_SIGNATURES = {"crnerf_mesh_smooth.h": {     # Taubin smoothing and face-derived vertex normals: adjacency, then smooth; the box as four scalars
+    "crnerf_mesh_smooth_workspace_bytes": (usz, [i64, i64]),
+    "crnerf_mesh_adjacency_i32": (i32, [vp, i64, i64, vp, vp]),
+    "crnerf_mesh_smooth_f32": (i32, [vp, i64, i64, f32, f32, f32, i32, i32, f64, f64, i32, vp, vp, vp]),
+    "crnerf_mesh_vertex_normals_f32": (i32, [vp, vp, i64, i64, i32, vp, vp, vp]),
+}}
+_staged = [n for mapping in STAGED_MAPPINGS + (STAGED_SMOOTH_SIGNATURES,) for table in mapping.values() for n in table]
 if len(set(_staged)) != len(_staged) or set(_staged) & set(EXPORTS):
     raise ImportError("crnerf_amd._lib: a staged entry is declared twice: %s" % sorted(n for n in _staged if _staged.count(n) > 1 or n in EXPORTS))
 
@@ -378,7 +386,7 @@ def load():
                                      % (LIB_PATH, name, header_of(name))) from None
             fn.restype = res
             fn.argtypes = args
-        for header, table in itertools.chain.from_iterable(mapping.items() for mapping in STAGED_MAPPINGS):
+        for header, table in itertools.chain.from_iterable(mapping.items() for mapping in STAGED_MAPPINGS + (STAGED_SMOOTH_SIGNATURES,)):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(lib, name)

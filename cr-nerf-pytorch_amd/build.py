@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrnerf_hip.so")
 STAMP = os.path.join(HERE, ".build_stamp")
 SOURCES = ["abi.hip", "pack.hip", "mlp_forward16.hip", "render_fused16.hip", "mlp_forward_bf16p.hip", "sigma_query16.hip", "sigma_query_bf16p.hip", "feature_query16.hip", "feature_query_bf16p.hip", "mlp_forward_x3.hip", "mlp_forward_h2.hip", "render_fused_h2.hip", "mlp_backward_x3.hip", "mlp_backward_h2.hip", "render_fused_bf16p.hip", "render_fused_bf16p_f16.hip", "mlp_forward_bf16p_f16.hip", "render_fused_x3.hip", "render_fused_lean_x3.hip", "render_fused_lean_h2.hip", "mlp_train16.hip", "mlp_gemm_bf16.hip", "train_aux.hip", "ray_kernels.hip", "raygen.hip", "encoder.hip", "encoder_train.hip", "cgnet.hip", "cgnet_chain.hip",
-           "crossray.hip", "peer_xchg.hip", "metrics.hip", "lpips.hip", "imageprep.hip", "scenebounds.hip", "rgbaprep.hip", "mesh.hip", "mesh_parts.hip", "mesh_simplify.hip"]
+           "crossray.hip", "peer_xchg.hip", "metrics.hip", "lpips.hip", "imageprep.hip", "scenebounds.hip", "rgbaprep.hip", "mesh.hip", "mesh_parts.hip", "mesh_simplify.hip", "mesh_smooth.hip"]
 INCLUDE = os.path.join(HERE, "..", "include")
 HEADERS = (sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
            + ["../../include/" + f for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")])   # every header: any edit rebuilds

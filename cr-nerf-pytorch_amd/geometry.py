@@ -13,6 +13,9 @@ what mesh extraction, occupancy visualisation and point-cloud export start from 
     Mesh.colorize(model, decoder, style, dirs=None)         a new Mesh with colors [V,3] (dirs None: -normals); save_ply writes red green blue
     Mesh.simplify(cell, lo=None, hi=None)         a new Mesh with one vertex per occupied cell of a grid of `cell`-sized cells (vertex clustering);
                                                   extract_mesh(..., simplify_cell=c) ends with it
+    Mesh.smooth(steps=10, lam=0.5, mu=-0.53)      a new Mesh after Taubin's lambda | mu smoothing, normals recomputed from the smoothed faces;
+                                                  extract_mesh(..., smooth_steps=s) ends with it
+    Mesh.recompute_normals()                      a new Mesh with area-weighted normals derived from its faces (a mesh that had none included)
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
@@ -25,6 +28,11 @@ Simplification (csrc/crnerf_mesh_simplify.h): the mesh above follows the samplin
 makes it follow a cell size of the caller's -- one vertex per occupied cell at the members' mean (exact integer sums: the same bytes on every
 run), collapsed and duplicate faces dropped, normals and colours averaged.  Count, one read-back (V', F'), emit.  The order of a pipeline:
 floaters first, then simplify, then colorize (or colorize first: the colours are averaged).
+Smoothing and face normals (csrc/crnerf_mesh_smooth.h): the extracted surface carries the density's noise and a simplified one the blocks of
+its cells; a few steps of Taubin's lambda | mu smoothing take both out without the shrinkage of plain Laplacian smoothing.  The adjacency is
+built once a call, every pass is a gather over it; positions on a 2^30 integer lattice and neighbour sums in 64-bit integers -- the same bytes
+on every run, whatever the order of the faces.  Normals are then re-derived from the faces, area-weighted, from integer sums again.  One
+read-back, of the bounding box.  The order of a pipeline: floaters, simplify, smooth, colorize.
 Inference only; GPU tensors only: like every op of the package there is no CPU fallback.
 
 Domain: |coordinate| < 64.  Below it the kernels' embedding is the routine the stand-alone posenc uses (which switches to ocml's sincosf there);
@@ -70,7 +78,7 @@ class Mesh:
     """An indexed triangle mesh: vertices [V,3] float32, faces [F,3] int32 (vertex ids, counter-clockwise seen from outside the dense region),
     normals [V,3] float32 (unit length, or zero where the density gradient vanishes) or None, colors [V,3] float32 in [0,1] (colorize) or None.
     Every method returns a new Mesh and leaves this one as it is.  Order of a pipeline: floaters first (largest / drop_small / select), then
-    simplify, then colorize -- or colorize before simplify, which averages the colours it is handed."""
+    simplify, then smooth, then colorize -- or colorize before simplify, which averages the colours it is handed; smooth keeps them."""
     __slots__ = ("vertices", "faces", "normals", "colors")
 
     def __init__(self, vertices, faces, normals=None, colors=None):
@@ -196,6 +204,51 @@ class Mesh:
         v, f, nrm, col, _ = ops.mesh_cluster(self.vertices, self.faces, lo, cells, n, normals=self.normals, colors=self.colors)
         return Mesh(v, f, nrm, col)
 
+    @torch.no_grad()
+    def smooth(self, steps=10, lam=0.5, mu=-0.53, pin_border=True):
+        """A new Mesh after `steps` steps of Taubin's lambda | mu smoothing (csrc/crnerf_mesh_smooth.h states every rule): per step a pass that
+        moves every vertex by lam times the way to the mean of its neighbours and a pass with mu, which undoes the shrinkage -- the noise of a
+        trained density and the blocks of simplify go, the shape stays.  A neighbour counts once per face that joins the two.  Vertices without
+        a face stay where they are, and with pin_border so do the vertices of an open border.  Same faces and colours (not copied); normals,
+        when the mesh has them, are recomputed from the smoothed faces (recompute_normals), None stays None.  The positions live on a 2^30
+        lattice over a box around the bounding box (one read-back, of six floats): the same bytes on every run, whatever the order of the
+        faces.  steps = 0 returns this mesh; an empty mesh gives an empty mesh, without a read-back.
+        Order: floaters first, then simplify, then smooth, then colorize -- colorize(dirs=None) then looks along normals that belong to the
+        surface.  ValueError: steps that is not an int >= 0, a lam or mu that is not finite or has |w| > 2, a bounding box that is not finite."""
+        what = "crnerf_amd.geometry: smooth"
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= 65536:
+            raise ValueError("%s: steps must be an int in [0, 65536], got %r" % (what, steps))
+        weights = []
+        for name, w in (("lam", lam), ("mu", mu)):
+            try:
+                w = float(w)
+            except (TypeError, ValueError):
+                w = math.nan
+            if not (math.isfinite(w) and abs(w) <= 2.0):
+                raise ValueError("%s: %s must be a finite float with |%s| <= 2, got %r" % (what, name, name, lam if name == "lam" else mu))
+            weights.append(w)
+        if steps == 0:
+            return self
+        if self.vertices.shape[0] == 0:
+            empty = self.vertices.new_empty((0, 3))
+            return Mesh(empty, self.faces, None if self.normals is None else empty.clone(), self.colors)
+        lo, e = _lattice_box(self.vertices, what)
+        v = ops.mesh_smooth(self.vertices, self.faces, lo, 29 - e, steps, weights[0], weights[1], pin_border=bool(pin_border))
+        nrm = None if self.normals is None else ops.mesh_vertex_normals(v, self.faces, 44 - 2 * e)
+        return Mesh(v, self.faces, nrm, self.colors)
+
+    @torch.no_grad()
+    def recompute_normals(self):
+        """A new Mesh whose normals are derived from its faces (csrc/crnerf_mesh_smooth.h, Face normals per vertex): per vertex the
+        area-weighted mean of the normals of its faces, of unit length, and zero for a vertex no face uses.  The faces are counter-clockwise
+        seen from outside, so these point the way an extracted mesh's density-gradient normals do.  It works on a mesh that had none -- one a
+        caller built, which colorize(dirs=None) could not look at -- and replaces the averaged normals of simplify.  Same vertices, faces and
+        colours (not copied); one read-back, of six floats."""
+        if self.vertices.shape[0] == 0:
+            return Mesh(self.vertices, self.faces, self.vertices.new_empty((0, 3)), self.colors)
+        _, e = _lattice_box(self.vertices, "crnerf_amd.geometry: recompute_normals")
+        return Mesh(self.vertices, self.faces, ops.mesh_vertex_normals(self.vertices, self.faces, 44 - 2 * e), self.colors)
+
     def save_ply(self, path):
         """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals, then uchar red green blue when it has colors:
         (c.clamp(0, 1) * 255) truncated) per vertex, `uchar int` vertex_indices per face.  Copies to the host itself; needs no third-party package."""
@@ -270,6 +323,23 @@ def _cluster_cells(lo, hi, cell, what):
     if n[0] * n[1] * n[2] > 2 ** 31 - 1:
         raise ValueError("%s: cell = %r cuts the box into %d x %d x %d cells, more than 2^31 - 1 in all" % (what, cell, n[0], n[1], n[2]))
     return n
+
+
+def _lattice_box(vertices, what):
+    """(lo, e) of the smoothing lattice (csrc/crnerf_mesh_smooth.h, Fixed point): E = the largest extent of the bounding box (0 counts as 1),
+    e = ceil(log2(E)) -- from the exponent of E, not from a rounded logarithm --, lo_a = (min_a + max_a) / 2 - 2^e in Python floats; the caller
+    passes k = 29 - e and k2 = 44 - 2 e.  One read-back, of six floats."""
+    ops._parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=False)
+    # (over the rows of the transposed copy: a reduction along the short side of a [V,3] tensor takes five times as long, profiles/r25)
+    box = torch.stack(torch.aminmax(vertices.t().contiguous(), dim=1)).tolist()
+    if not all(math.isfinite(x) for x in box[0] + box[1]):
+        raise ValueError("%s: the vertices' bounding box is not finite" % what)
+    E = max(box[1][a] - box[0][a] for a in range(3))
+    m, x = math.frexp(E if E > 0.0 else 1.0)      # E = m 2^x, 0.5 <= m < 1
+    e = x - 1 if m == 0.5 else x
+    if not -71 <= e <= 126:      # k = 29 - e must lie in [-100, 100], and 2^e in float32
+        raise ValueError("%s: the bounding box's largest extent %g is outside [2^-71, 2^126]" % (what, E))
+    return [(box[0][a] + box[1][a]) / 2 - math.ldexp(1.0, e) for a in range(3)], e
 
 
 def _select(mesh, parts, keep):
@@ -382,15 +452,20 @@ def density_grid(model, lo, hi, resolution, precision="f32"):
 
 
 @torch.no_grad()
-def extract_mesh(model, lo, hi, resolution, threshold, precision="f32", keep_largest=False, simplify_cell=None):
+def extract_mesh(model, lo, hi, resolution, threshold, precision="f32", keep_largest=False, simplify_cell=None, smooth_steps=0):
     """density_grid(model, lo, hi, resolution, precision).mesh(threshold): the surface of the box's density as a Mesh.  keep_largest=True: its
     .largest(1) -- the part with the most faces, the floaters of a trained density gone.  simplify_cell=c: then its .simplify(c), in that order
-    -- extract, largest when asked, simplify (over the bounding box of what is left); None: the mesh as it is."""
+    -- extract, largest when asked, simplify (over the bounding box of what is left); None: the mesh as it is.  smooth_steps=s > 0: then its
+    .smooth(s) at the default weights, the normals recomputed from the smoothed faces."""
     if math.isnan(float(threshold)):      # before the grid is paid for
         raise ValueError("crnerf_amd.geometry: mesh: the threshold is NaN")
+    nothing = Mesh(torch.empty(0, 3), torch.empty(0, 3, dtype=torch.int32))
     if simplify_cell is not None:
-        Mesh(torch.empty(0, 3), torch.empty(0, 3, dtype=torch.int32)).simplify(simplify_cell)      # a bad cell: refused before the grid is paid for
+        nothing.simplify(simplify_cell)      # a bad cell: refused before the grid is paid for
+    nothing.smooth(smooth_steps)             # and bad steps
     mesh = density_grid(model, lo, hi, resolution, precision=precision).mesh(threshold)
     if keep_largest:
         mesh = mesh.largest(1)
-    return mesh if simplify_cell is None else mesh.simplify(simplify_cell)
+    if simplify_cell is not None:
+        mesh = mesh.simplify(simplify_cell)
+    return mesh.smooth(smooth_steps) if smooth_steps > 0 else mesh

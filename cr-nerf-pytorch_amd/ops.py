@@ -706,6 +706,84 @@ def mesh_cluster(vertices, faces, lo, cell, n, normals=None, colors=None):
     return out_v, out_f, out_n, out_c, vertex_cluster
 
 
+def _smooth_scalars(lo, k, steps, lam, mu, what):
+    """(lo as float32-rounded floats, k, steps, lam, mu) of a smoothing call, held to what the library accepts: no device is needed."""
+    try:
+        lo = [float(v) for v in lo]
+    except (TypeError, ValueError):
+        lo = []
+    if len(lo) != 3:
+        raise ValueError("crnerf_amd: %s expects lo as a 3-sequence of floats" % what)
+    lo = [ctypes.c_float(v).value for v in lo]      # what the library is handed
+    if not all(math.isfinite(v) for v in lo):
+        raise ValueError("crnerf_amd: %s: lo must be finite as float32, got %r" % (what, lo))
+    for name, v in (("k", k), ("steps", steps)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("crnerf_amd: %s: %s must be an int, got %r" % (what, name, v))
+    k, steps = int(k), int(steps)
+    if not -100 <= k <= 100:
+        raise ValueError("crnerf_amd: %s: k must lie in [-100, 100], got %d" % (what, k))
+    if not 0 <= steps <= 65536:
+        raise ValueError("crnerf_amd: %s: steps must lie in [0, 65536], got %d" % (what, steps))
+    lam, mu = float(lam), float(mu)
+    for name, v in (("lam", lam), ("mu", mu)):
+        if not (math.isfinite(v) and abs(v) <= 2.0):
+            raise ValueError("crnerf_amd: %s: %s must be finite with |%s| <= 2, got %r" % (what, name, name, v))
+    return lo, k, steps, lam, mu
+
+
+def mesh_smooth(vertices, faces, lo, k, steps, lam, mu, pin_border=True):
+    """The vertices after `steps` steps of Taubin's lambda | mu smoothing on the device (csrc/crnerf_mesh_smooth.h states every rule: positions
+    on the 2^30 lattice of the box lo, lo + 2^(30 - k); per pass every vertex moves by the weight times the way to the mean of its neighbour
+    entries, a pass with lam then a pass with mu per step; vertices without a face, and with pin_border the vertices of an open border, stay;
+    content deterministic and independent of the order of the faces).  vertices [V,3] float32, faces [F,3] int32: contiguous, on the device,
+    as they are; lo: a 3-sequence of floats (rounded to float32); k, steps: ints; lam, mu: floats.  Returns vertices' [V,3] float32; steps = 0
+    is the quantisation round trip.  No read-back."""
+    what = "mesh_smooth"
+    vp_ = fp = None
+    for on_device in (False, True):      # every shape and dtype before any device
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        fp = _parts_input(faces, "faces", what, torch.int32, cols=3, on_device=on_device)
+        if not on_device:
+            lo, k, steps, lam, mu = _smooth_scalars(lo, k, steps, lam, mu, what)
+    V, F, dev = vertices.shape[0], faces.shape[0], vertices.device
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    if V:
+        lib = _lib.load()
+        st = _lib.stream_ptr()
+        workspace = torch.empty(max(int(lib.crnerf_mesh_smooth_workspace_bytes(V, F)), 16), dtype=torch.uint8, device=dev)
+        wp = ctypes.c_void_p(workspace.data_ptr())
+        _lib.check(lib.crnerf_mesh_adjacency_i32(fp, V, F, wp, st), "crnerf_mesh_adjacency_i32")
+        _lib.check(lib.crnerf_mesh_smooth_f32(vp_, V, F, *lo, k, steps, lam, mu, 1 if pin_border else 0, wp, ctypes.c_void_p(out.data_ptr()), st),
+                   "crnerf_mesh_smooth_f32")
+    return out
+
+
+def mesh_vertex_normals(vertices, faces, k2):
+    """Area-weighted vertex normals from the faces, on the device (csrc/crnerf_mesh_smooth.h, Face normals per vertex: the float64 cross product
+    of every valid face, times 2^k2, rounded to a 64-bit integer and added to its three corners; the sums normalised in float64; the zero vector
+    for a vertex no face uses).  vertices [V,3] float32, faces [F,3] int32: contiguous, on the device, as they are; k2: an int in [-300, 300].
+    Returns normals [V,3] float32.  No read-back."""
+    what = "mesh_vertex_normals"
+    vp_ = fp = None
+    for on_device in (False, True):
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        fp = _parts_input(faces, "faces", what, torch.int32, cols=3, on_device=on_device)
+        if not on_device:
+            if isinstance(k2, bool) or int(k2) != k2 or not -300 <= int(k2) <= 300:
+                raise ValueError("crnerf_amd: %s: k2 must be an int in [-300, 300], got %r" % (what, k2))
+            k2 = int(k2)
+    V, F, dev = vertices.shape[0], faces.shape[0], vertices.device
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    if V:
+        lib = _lib.load()
+        # (F = 0: the neighbour list lies last in the workspace, and the normals do not use it)
+        workspace = torch.empty(max(int(lib.crnerf_mesh_smooth_workspace_bytes(V, 0)), 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.crnerf_mesh_vertex_normals_f32(vp_, fp, V, F, k2, ctypes.c_void_p(workspace.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                      _lib.stream_ptr()), "crnerf_mesh_vertex_normals_f32")
+    return out
+
+
 def composite(raw, z, noise=None, noise_std=0.0):
     lib = _lib.load()
     raw, z = _f32c(raw, "raw"), _f32c(z, "z")
