@@ -2,11 +2,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace crnerf {
 
 // thread-local last-error slot behind crnerf_last_error(); returns code
 int set_error(int code, const char* msg);
+// "<who>: <what>", composed on the failure path only
+inline int launch_fail(int code, const char* who, const char* what) {
+  char msg[200];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return set_error(code, msg);
+}
 int check_launch(const char* what);
 // compute units of the current device (hipDeviceAttributeMultiprocessorCount, cached per device): the persistent kernels launch
 // one workgroup per CU

@@ -3,17 +3,9 @@
 // preparation.  Device code and the kernel parameter blocks (RenderParams16 / X / P, their fields and field order) stay per core: kernarg offsets
 // are ISA.  Nothing here allocates or formats on the success path; an error text is composed only once its check has failed (abi.hip fail()).
 #pragma once
-#include <stdio.h>
 #include "kernels.h"
 
 namespace crnerf {
-
-// "<who>: <what>", composed on the failure path only
-inline int launch_fail(int code, const char* who, const char* what) {
-  char msg[200];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_error(code, msg);
-}
 
 // Persistent grid: one workgroup per CU walking `units` (ray quads, point groups) in `iters` rounds; one_per_unit (the repair launches): a
 // workgroup per unit, which leaves at once unless its unit needs the work.  units > 0, and <= INT_MAX when one_per_unit.

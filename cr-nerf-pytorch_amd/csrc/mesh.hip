@@ -3,19 +3,17 @@
 // every run.
 //
 // Three launches, none of which waits on another workgroup:
-//   mesh_count_kernel   one thread per 4 consecutive nodes, MT_SCAN = 1,024 nodes per workgroup: each node's 2x2x2 neighbourhood -> its 7-bit
-//                       active-edge mask, its vertex count (the mask's popcount) and, where the node is a cell's origin, the cell's face count;
-//                       a workgroup scan of both counts (packed 16 + 16 bits: a block holds at most 7,168 vertices and 12,288 faces) leaves each
-//                       node's offset inside its block, and the block's two totals
-//   mesh_scan_kernel    ONE workgroup walks the block totals in chunks of MT_SCAN with a running 64-bit carry: exclusive block bases in place,
-//                       then counts[0] = V, counts[1] = F
+//   mesh_count_kernel   one thread per 4 consecutive nodes: each node's 2x2x2 neighbourhood -> its 7-bit active-edge mask, its vertex count (the
+//                       mask's popcount) and, where the node is a cell's origin, the cell's face count; the block scan of mesh_common.h over both
+//                       counts at once (packed 16 + 16 bits: a block holds at most 7,168 vertices and 12,288 faces)
+//   mesh_block_scan_kernel  (mesh_common.h) both lists of block totals: counts[0] = V, counts[1] = F
 //   mesh_emit_kernel    one 16-byte load per 16 consecutive nodes' masks; a wave queues the active nodes of its 1,024 in LDS and walks them
 //                       one per lane.  An active node writes its vertices at base[block] + local + rank and, as a cell's origin, its faces; a neighbour's vertex id is
 //                       base[block(q)] + local[q] + popcount(mask[q] & ((1 << d) - 1)) -- the corner's inside bit is inside(origin) ^ mask bit,
 //                       so no sigma is read twice for the topology.
 // Offsets come from the scans alone: no atomics, so the order is the one the header defines.
 //
-// Workspace (5 bytes a node + 16 a block): vbase[nb] fbase[nb] (uint64) | mask[N] (uint8) | vloc[N] | floc[N] (uint16), nb = ceil(N / MT_SCAN),
+// Workspace (5 bytes a node + 16 a block): vbase[nb] fbase[nb] (uint64) | mask[N] (uint8) | vloc[N] | floc[N] (uint16), nb = ceil(N / MESH_SCAN),
 // every array on a 16-byte boundary.
 // The passes are not bound by bytes (profiles/r21/mesh.txt): with one node per thread the count pass ran at 0.12 and the emit pass at 0.03-0.05 of
 // their byte-count time, and staging the count pass's neighbourhoods through LDS changed its time by +2 % .. -7 %.  So the neighbourhoods overlap
@@ -26,19 +24,13 @@
 // non-finite t.  The interpolation is written with __fmul_rn / __fadd_rn: a multiply and an add, rounded separately.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include/crnerf_mesh.h"
-#include "kernels.h"
+#include "mesh_common.h"
 
 namespace crnerf {
 
-constexpr int MT_SCAN = 1024;                   // nodes per count workgroup = per block base
-constexpr int MT_SCAN_SHIFT = 10;
-constexpr int MT_WAVES = MT_SCAN / 64;
 constexpr int MT_EMIT_THREADS = 256;
-constexpr int64_t MT_MAX = 0x7fffffffLL;
-static_assert((1 << MT_SCAN_SHIFT) == MT_SCAN, "block of a node = node >> MT_SCAN_SHIFT");
-static_assert(7 * MT_SCAN < 65536 && 12 * MT_SCAN < 65536, "a block's vertex and face counts are scanned in 16 bits each");
+static_assert(7 * MESH_SCAN < 65536 && 12 * MESH_SCAN < 65536, "a block's vertex and face counts are scanned in 16 bits each");
 
 // ---------------------------------------------------------------------------------------------------------------- the case table
 // Tet t of a cell is the monotone path 0 -> 1 << a -> (1 << a) | (1 << b) -> 7 through the cell's corners (corner k = dx + 2 dy + 4 dz), (a, b, c)
@@ -109,41 +101,35 @@ struct MtWorkspace {
   uint16_t* floc;                 // [N] faces of the block's cells below this one
 };
 
-__host__ __device__ inline uint32_t mt_blocks(uint32_t N) { return (N + MT_SCAN - 1) >> MT_SCAN_SHIFT; }
-inline size_t mt_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // every array starts on a 16-byte boundary of a 16-byte aligned workspace: the passes move 4 or 16 nodes' entries per load / store
 constexpr size_t MT_WORKSPACE_PAD = 32;         // the two roundings, at most 15 bytes each
 
 static MtWorkspace mt_carve(void* workspace, uint32_t N) {
-  const size_t nb = mt_blocks(N);
+  const size_t nb = scan_blocks(N);
   MtWorkspace w;
   char* p = (char*)workspace;
   size_t off = 0;
   w.vbase = (unsigned long long*)(p + off); off += 8 * nb;
   w.fbase = (unsigned long long*)(p + off); off += 8 * nb;
-  w.mask = (uint8_t*)(p + off); off = mt_align16(off + N);
-  w.vloc = (uint16_t*)(p + off); off = mt_align16(off + 2 * (size_t)N);
+  w.mask = (uint8_t*)(p + off); off = align16(off + N);
+  w.vloc = (uint16_t*)(p + off); off = align16(off + 2 * (size_t)N);
   w.floc = (uint16_t*)(p + off);
   return w;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- count
-// One thread per MT_PER consecutive nodes (flat index: a run may wrap from one row, or slab, into the next).  The 2x2x2 neighbourhoods of a
-// run lie in four spans of MT_PER + 1 consecutive floats -- at the run, one row up, one slab up, both -- read once each and kept as inside
+// One thread per MESH_PER consecutive nodes (flat index: a run may wrap from one row, or slab, into the next).  The 2x2x2 neighbourhoods of a
+// run lie in four spans of MESH_PER + 1 consecutive floats -- at the run, one row up, one slab up, both -- read once each and kept as inside
 // bits; a corner outside the grid counts as the node's own side (no active edge), so a span element past the end of the grid only needs to be
 // SOMETHING: its index is clamped to the last node.  The divisions that split the flat index are paid once per run.
-constexpr int MT_PER = 4;
-constexpr int MT_COUNT_THREADS = MT_SCAN / MT_PER;
-constexpr int MT_COUNT_WAVES = MT_COUNT_THREADS / 64;
-
-__global__ __launch_bounds__(MT_COUNT_THREADS) void mesh_count_kernel(const float* __restrict__ sigma, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t N,
+__global__ __launch_bounds__(MESH_PER_THREADS) void mesh_count_kernel(const float* __restrict__ sigma, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t N,
                                                                       float threshold, MtWorkspace w) {
-  __shared__ uint32_t wave_sum[MT_COUNT_WAVES];
+  __shared__ uint32_t wave_sum[MESH_PER_WAVES];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t i0 = blockIdx.x * (uint32_t)MT_SCAN + MT_PER * tid;
-  uint32_t m[MT_PER], cnt[MT_PER];              // cnt: vertices | faces << 16
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * tid;
+  uint32_t m[MESH_PER], cnt[MESH_PER];          // cnt: vertices | faces << 16
 #pragma unroll
-  for (int j = 0; j < MT_PER; ++j) { m[j] = 0; cnt[j] = 0; }
+  for (int j = 0; j < MESH_PER; ++j) { m[j] = 0; cnt[j] = 0; }
   if (i0 < N) {
     uint32_t bits[4];
 #pragma unroll
@@ -151,14 +137,14 @@ __global__ __launch_bounds__(MT_COUNT_THREADS) void mesh_count_kernel(const floa
       const uint64_t at = (uint64_t)i0 + ((s & 1) ? nx : 0u) + ((s & 2) ? (uint64_t)nx * ny : 0ull);
       bits[s] = 0;
 #pragma unroll
-      for (int k = 0; k <= MT_PER; ++k) {       // clamped, not skipped: twenty independent loads in flight, no branch and no wait between them
+      for (int k = 0; k <= MESH_PER; ++k) {     // clamped, not skipped: twenty independent loads in flight, no branch and no wait between them
         const uint64_t q = at + k < N ? at + k : (uint64_t)N - 1;
         bits[s] |= (uint32_t)(sigma[q] > threshold) << k;
       }
     }
     uint32_t ix = i0 % nx, r = i0 / nx, iy = r % ny, iz = r / ny;
 #pragma unroll
-    for (int j = 0; j < MT_PER; ++j) {
+    for (int j = 0; j < MESH_PER; ++j) {
       if (i0 + j < N) {
         const bool vx = ix + 1 < nx, vy = iy + 1 < ny, vz = iz + 1 < nz;
         const uint32_t in0 = (bits[0] >> j) & 1u;
@@ -185,34 +171,21 @@ __global__ __launch_bounds__(MT_COUNT_THREADS) void mesh_count_kernel(const floa
   }
   uint32_t own = 0;
 #pragma unroll
-  for (int j = 0; j < MT_PER; ++j) own += cnt[j];
-  uint32_t incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t below = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < MT_COUNT_WAVES; ++k) {
-    const uint32_t s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
+  for (int j = 0; j < MESH_PER; ++j) own += cnt[j];
+  uint32_t total;
+  const uint32_t below = block_scan_exclusive<uint32_t, MESH_PER_WAVES, false>(own, wave_sum, lane, wave, total);
   if (i0 < N) {
-    uint32_t excl[MT_PER];
-    excl[0] = below + incl - own;
+    uint32_t excl[MESH_PER];
+    excl[0] = below;
 #pragma unroll
-    for (int j = 1; j < MT_PER; ++j) excl[j] = excl[j - 1] + cnt[j - 1];
-    if (i0 + MT_PER <= N) {                     // i0 is a multiple of 4 and the arrays start on 16 bytes: one store each
+    for (int j = 1; j < MESH_PER; ++j) excl[j] = excl[j - 1] + cnt[j - 1];
+    if (i0 + MESH_PER <= N) {                   // i0 is a multiple of 4 and the arrays start on 16 bytes: one store each
       *(uint32_t*)(w.mask + i0) = m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24);
       *(uint2*)(w.vloc + i0) = make_uint2((excl[0] & 0xffffu) | (excl[1] << 16), (excl[2] & 0xffffu) | (excl[3] << 16));
       *(uint2*)(w.floc + i0) = make_uint2((excl[0] >> 16) | (excl[1] & 0xffff0000u), (excl[2] >> 16) | (excl[3] & 0xffff0000u));
     } else {                                    // the grid's last, partial run
 #pragma unroll
-      for (int j = 0; j < MT_PER; ++j)
+      for (int j = 0; j < MESH_PER; ++j)
         if (i0 + j < N) {
           w.mask[i0 + j] = (uint8_t)m[j];
           w.vloc[i0 + j] = (uint16_t)(excl[j] & 0xffffu);
@@ -225,48 +198,7 @@ __global__ __launch_bounds__(MT_COUNT_THREADS) void mesh_count_kernel(const floa
     w.fbase[blockIdx.x] = total >> 16;
   }
 }
-static_assert(MT_PER == 4, "the packed stores above hold four nodes");
-
-// ---------------------------------------------------------------------------------------------------------------- scan of the block totals
-__device__ __forceinline__ unsigned long long mt_block_scan64(unsigned long long own, unsigned long long* wave_sum, uint32_t lane, uint32_t wave,
-                                                              unsigned long long& total) {
-  unsigned long long incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  __syncthreads();                              // the previous use of wave_sum has been read
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  unsigned long long below = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < MT_WAVES; ++k) {
-    const unsigned long long s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  return below + incl - own;
-}
-
-__global__ __launch_bounds__(MT_SCAN) void mesh_scan_kernel(unsigned long long* __restrict__ vbase, unsigned long long* __restrict__ fbase, uint32_t nb,
-                                                            long long* __restrict__ counts) {
-  __shared__ unsigned long long wave_sum[MT_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry_v = 0, carry_f = 0;
-  for (uint32_t base = 0; base < nb; base += MT_SCAN) {      // (the trip count is the same in every thread: the barriers inside are uniform)
-    const uint32_t j = base + tid;
-    const unsigned long long v = j < nb ? vbase[j] : 0ull, f = j < nb ? fbase[j] : 0ull;
-    unsigned long long tv, tf;
-    const unsigned long long ev = mt_block_scan64(v, wave_sum, lane, wave, tv);
-    const unsigned long long ef = mt_block_scan64(f, wave_sum, lane, wave, tf);
-    if (j < nb) { vbase[j] = carry_v + ev; fbase[j] = carry_f + ef; }
-    carry_v += tv;
-    carry_f += tf;
-  }
-  if (tid == 0) { counts[0] = (long long)carry_v; counts[1] = (long long)carry_f; }
-}
+static_assert(MESH_PER == 4, "the packed stores above hold four nodes");
 
 // ---------------------------------------------------------------------------------------------------------------- emit
 struct MtGrid {
@@ -294,7 +226,7 @@ __device__ __forceinline__ void mt_emit_node(const MtGrid& g, float threshold, c
   const uint32_t ix = i % g.nx, r = i / g.nx, iy = r % g.ny, iz = r / g.ny;
   const uint32_t sxy = g.nx * g.ny;
   const float sa = g.sigma[i];
-  const long long voff = (long long)(w.vbase[i >> MT_SCAN_SHIFT] + w.vloc[i]);
+  const long long voff = (long long)(w.vbase[i >> MESH_SCAN_SHIFT] + w.vloc[i]);
 
   if (voff < v_cap) {
     const float xa = g.xs[ix], ya = g.ys[iy], za = g.zs[iz];
@@ -329,7 +261,7 @@ __device__ __forceinline__ void mt_emit_node(const MtGrid& g, float threshold, c
   }
 
   if (!(ix + 1 < g.nx && iy + 1 < g.ny && iz + 1 < g.nz)) return;
-  long long f = (long long)(w.fbase[i >> MT_SCAN_SHIFT] + w.floc[i]);
+  long long f = (long long)(w.fbase[i >> MESH_SCAN_SHIFT] + w.floc[i]);
   if (f >= f_cap) return;
   const uint32_t in = ((m << 1) ^ (sa > threshold ? 0xffu : 0u)) & 0xffu;      // bit k: corner k is inside
   for (int t = 0; t < 6; ++t) {
@@ -345,7 +277,7 @@ __device__ __forceinline__ void mt_emit_node(const MtGrid& g, float threshold, c
       if (j < n) {
         const uint32_t lo = c.lo[j], d = (uint32_t)c.hi[j] - lo - 1u;       // the lower corner owns the edge; d = its direction index
         const uint32_t q = i + (lo & 1u) + ((lo >> 1) & 1u) * g.nx + (lo >> 2) * sxy;
-        id[j] = (long long)(w.vbase[q >> MT_SCAN_SHIFT] + w.vloc[q]) + __popc((uint32_t)w.mask[q] & ((1u << d) - 1u));
+        id[j] = (long long)(w.vbase[q >> MESH_SCAN_SHIFT] + w.vloc[q]) + __popc((uint32_t)w.mask[q] & ((1u << d) - 1u));
       }
     }
 #pragma unroll
@@ -423,19 +355,13 @@ __global__ __launch_bounds__(MT_EMIT_THREADS) void mesh_emit_kernel(MtGrid g, fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int mt_fail(int code, const char* who, const char* what) {
-  static thread_local char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_error(code, msg);
-}
-
 // negative: refused.  0 with *empty set: nothing to do (an empty axis, or one shorter than 2: no cell)
 static int mt_shape(const char* who, int32_t nx, int32_t ny, int32_t nz, bool* empty) {
   *empty = false;
-  if (nx < 0 || ny < 0 || nz < 0) return mt_fail(CRNERF_ERR_SHAPE, who, "negative axis length");
+  if (nx < 0 || ny < 0 || nz < 0) return launch_fail(CRNERF_ERR_SHAPE, who, "negative axis length");
   if (nx == 0 || ny == 0 || nz == 0) { *empty = true; return 0; }
   // (nx * ny < 2^62, and the quotient test keeps the triple product out of 64-bit overflow)
-  if ((int64_t)nx * ny > MT_MAX / nz) return mt_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 nodes in one call");
+  if ((int64_t)nx * ny > MESH_MAX / nz) return launch_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 nodes in one call");
   if (nx < 2 || ny < 2 || nz < 2) *empty = true;
   return 0;
 }
@@ -448,9 +374,9 @@ using namespace crnerf;
   if (!(p)) return set_error(CRNERF_ERR_NULL, name " is NULL")
 
 extern "C" size_t crnerf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
-  if (nx <= 0 || ny <= 0 || nz <= 0 || (int64_t)nx * ny > MT_MAX / nz) return 0;
+  if (nx <= 0 || ny <= 0 || nz <= 0 || (int64_t)nx * ny > MESH_MAX / nz) return 0;
   const uint32_t N = (uint32_t)((int64_t)nx * ny * nz);
-  return (size_t)16 * mt_blocks(N) + (size_t)5 * N + MT_WORKSPACE_PAD;
+  return (size_t)16 * scan_blocks(N) + (size_t)5 * N + MT_WORKSPACE_PAD;
 }
 
 extern "C" int crnerf_mesh_count_f32(const float* sigma, int32_t nx, int32_t ny, int32_t nz, float threshold, void* workspace, int64_t* counts,
@@ -463,13 +389,14 @@ extern "C" int crnerf_mesh_count_f32(const float* sigma, int32_t nx, int32_t ny,
     return 0;
   }
   MT_REQUIRE(sigma, "sigma"); MT_REQUIRE(workspace, "workspace"); MT_REQUIRE(counts, "counts");
-  if ((uintptr_t)workspace & 15u) return mt_fail(CRNERF_ERR_CONFIG, "mesh_count", "workspace must be 16-byte aligned");
-  const uint32_t N = (uint32_t)((int64_t)nx * ny * nz), nb = mt_blocks(N);
+  MESH_ALIGNED(workspace, "mesh_count");
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t N = (uint32_t)((int64_t)nx * ny * nz), nb = scan_blocks(N);
   const MtWorkspace w = mt_carve(workspace, N);
-  hipLaunchKernelGGL(mesh_count_kernel, dim3(nb), dim3(MT_COUNT_THREADS), 0, (hipStream_t)stream, sigma, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, N, threshold, w);
-  if (int rc = check_launch("mesh_count_kernel")) return rc;
-  hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(MT_SCAN), 0, (hipStream_t)stream, w.vbase, w.fbase, nb, (long long*)counts);
-  return check_launch("mesh_scan_kernel");
+  if (int rc = mesh_launch(mesh_count_kernel, "mesh_count_kernel", nb, MESH_PER_THREADS, st, sigma, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, N, threshold, w))
+    return rc;
+  long long* const out = (long long*)counts;
+  return mesh_block_scan(st, ScanList<1>{w.vbase, nb, {out}}, ScanList<1>{w.fbase, nb, {out + 1}});
 }
 
 extern "C" int crnerf_mesh_emit_f32(const float* sigma, const float* xs, const float* ys, const float* zs, int32_t nx, int32_t ny, int32_t nz,
@@ -477,18 +404,15 @@ extern "C" int crnerf_mesh_emit_f32(const float* sigma, const float* xs, const f
                                     int32_t* faces, void* stream) {
   bool empty;
   if (int rc = mt_shape("mesh_emit", nx, ny, nz, &empty)) return rc;
-  if (v_cap < 0 || f_cap < 0) return mt_fail(CRNERF_ERR_SHAPE, "mesh_emit", "negative capacity");
-  if (v_cap > MT_MAX || f_cap > MT_MAX) return mt_fail(CRNERF_ERR_SHAPE, "mesh_emit", "a capacity above 2^31 - 1 (faces hold int32 vertex ids)");
+  if (int rc = mesh_caps("mesh_emit", v_cap, f_cap)) return rc;
   if (empty || (v_cap == 0 && f_cap == 0)) return 0;
   MT_REQUIRE(sigma, "sigma"); MT_REQUIRE(xs, "xs"); MT_REQUIRE(ys, "ys"); MT_REQUIRE(zs, "zs"); MT_REQUIRE(workspace, "workspace");
   if (v_cap > 0) MT_REQUIRE(vertices, "vertices");
   if (f_cap > 0) MT_REQUIRE(faces, "faces");
-  if ((uintptr_t)workspace & 15u) return mt_fail(CRNERF_ERR_CONFIG, "mesh_emit", "workspace must be 16-byte aligned");
+  MESH_ALIGNED(workspace, "mesh_emit");
   const uint32_t N = (uint32_t)((int64_t)nx * ny * nz);
   const MtWorkspace w = mt_carve(const_cast<void*>(workspace), N);
   const MtGrid g{sigma, xs, ys, zs, (uint32_t)nx, (uint32_t)ny, (uint32_t)nz, N};
-  const uint32_t blocks = (uint32_t)(((uint64_t)N + MT_EMIT_THREADS * MT_EMIT_PER - 1) / (MT_EMIT_THREADS * MT_EMIT_PER));
-  hipLaunchKernelGGL(mesh_emit_kernel, dim3(blocks), dim3(MT_EMIT_THREADS), 0, (hipStream_t)stream, g, threshold, w, (long long)v_cap, (long long)f_cap,
-                     vertices, normals, faces);
-  return check_launch("mesh_emit_kernel");
+  return mesh_launch(mesh_emit_kernel, "mesh_emit_kernel", launch_blocks(N, MT_EMIT_THREADS * MT_EMIT_PER), MT_EMIT_THREADS, (hipStream_t)stream, g, threshold,
+                     w, (long long)v_cap, (long long)f_cap, vertices, normals, faces);
 }

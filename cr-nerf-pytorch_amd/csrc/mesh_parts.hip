@@ -8,9 +8,8 @@
 //                         hooked under the smaller end with one atomicCAS(parent[larger], larger, smaller), and the walk goes on only when that
 //                         CAS lost to another thread's update.  parent[v] <= v throughout, so every chain falls and ends, and the root of a
 //                         finished tree is its smallest id: the labels do not depend on the order the unions ran in.
-//   parts_roots_kernel    flatten (parent[v] = root) and a workgroup scan of the root flags over MP_SCAN = 1,024 vertices: each root's rank inside
-//                         its block, the block's total
-//   parts_scan_kernel     ONE workgroup walks the block totals in chunks of MP_SCAN with a running 64-bit carry: exclusive bases, counts[]
+//   parts_roots_kernel    flatten (parent[v] = root) and the block scan of mesh_common.h over the root flags
+//   mesh_block_scan_kernel  (mesh_common.h) the one list of block totals: counts[0] = K
 //   parts_apply_kernel    vertex_part[v] = base[block(root)] + rank[root]; face_part[f] likewise through the face's first id, -1 when invalid
 // Roots are ranked in id order and a root is its part's smallest id: part ids ascend in the smallest vertex id.
 //
@@ -25,30 +24,19 @@
 // a workgroup merge their sums through LDS: a mesh that is mostly one part makes at most 512 adds to that part's counter, not one per wave --
 // adds to one address retire one after another, about 26 ns each (profiles/r22/mesh_parts.txt).
 //
-// Selection: parts_keep_kernel (workgroup scan of the keep flags, vertices and faces in a launch each), the same parts_scan_kernel over both
-// lists of block totals, parts_emit_kernel (rows copied as 32-bit words, ids remapped through the vertex offsets).
+// Selection: parts_keep_kernel (block scan of the keep flags, vertices and faces in a launch each), mesh_block_scan_kernel over both lists of
+// block totals, parts_emit_kernel (rows copied as 32-bit words, ids remapped through the vertex offsets).
 //
 // Workspace: vbase[nbV] fbase[nbF] (uint64) | parent[V] (int32) | vloc[V] | floc[F] (uint16), every array on a 16-byte boundary.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "../../include/crnerf_mesh_parts.h"
-#include "kernels.h"
+#include "mesh_common.h"
 
 namespace crnerf {
 
-constexpr int MP_SCAN = 1024;                   // entries per scan workgroup = per block base
-constexpr int MP_SCAN_SHIFT = 10;
-constexpr int MP_WAVES = MP_SCAN / 64;
-constexpr int MP_PER = 4;                       // consecutive entries per thread of a flag scan
-constexpr int MP_FLAG_THREADS = MP_SCAN / MP_PER;
-constexpr int MP_FLAG_WAVES = MP_FLAG_THREADS / 64;
-constexpr int MP_THREADS = 256;                 // the per-entry kernels
 constexpr int MP_SIZE_STEPS = 16;               // a wave of the size pass takes 64 * 16 labels at a time
 constexpr int MP_SIZE_BLOCKS = 512;             // and at most this many workgroups share a list: adds to ONE address cost ~26 ns each, one after another
-constexpr int64_t MP_MAX = 0x7fffffffLL;
-static_assert((1 << MP_SCAN_SHIFT) == MP_SCAN, "block of an entry = entry >> MP_SCAN_SHIFT");
-static_assert(MP_SCAN < 65536, "an offset inside a block is kept in 16 bits");
 
 struct MpWorkspace {
   unsigned long long* vbase;      // [nbV] block totals, then exclusive bases
@@ -58,25 +46,23 @@ struct MpWorkspace {
   uint16_t* floc;                 // [F]
 };
 
-__host__ __device__ inline uint32_t mp_blocks(uint32_t n) { return (n + MP_SCAN - 1) >> MP_SCAN_SHIFT; }
-inline size_t mp_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 constexpr size_t MP_WORKSPACE_PAD = 64;         // four roundings, at most 15 bytes each
 
 static MpWorkspace mp_carve(void* workspace, uint32_t V, uint32_t F) {
   MpWorkspace w;
   char* p = (char*)workspace;
   size_t off = 0;
-  w.vbase = (unsigned long long*)(p + off); off += 8 * (size_t)mp_blocks(V);
-  w.fbase = (unsigned long long*)(p + off); off = mp_align16(off + 8 * (size_t)mp_blocks(F));
-  w.parent = (int32_t*)(p + off); off = mp_align16(off + 4 * (size_t)V);
-  w.vloc = (uint16_t*)(p + off); off = mp_align16(off + 2 * (size_t)V);
+  w.vbase = (unsigned long long*)(p + off); off += 8 * (size_t)scan_blocks(V);
+  w.fbase = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)scan_blocks(F));
+  w.parent = (int32_t*)(p + off); off = align16(off + 4 * (size_t)V);
+  w.vloc = (uint16_t*)(p + off); off = align16(off + 2 * (size_t)V);
   w.floc = (uint16_t*)(p + off);
   return w;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- union-find
-__global__ __launch_bounds__(MP_THREADS) void parts_init_kernel(int32_t* __restrict__ parent, uint32_t V) {
-  const uint32_t i = blockIdx.x * (uint32_t)MP_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void parts_init_kernel(int32_t* __restrict__ parent, uint32_t V) {
+  const uint32_t i = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (i < V) parent[i] = (int32_t)i;
 }
 
@@ -103,54 +89,22 @@ __device__ __forceinline__ void mp_union(int32_t* parent, const int32_t a0, cons
   if (a < b0) atomicMin(parent + b0, a);
 }
 
-__global__ __launch_bounds__(MP_THREADS) void parts_union_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, int32_t* parent) {
-  const uint32_t f = blockIdx.x * (uint32_t)MP_THREADS + threadIdx.x;
-  if (f >= F) return;
-  const int32_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if ((uint32_t)a >= V || (uint32_t)b >= V || (uint32_t)c >= V) return;      // (a negative id is a large unsigned one)
+__global__ __launch_bounds__(MESH_THREADS) void parts_union_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, int32_t* parent) {
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
+  int32_t id[3];
+  if (!load_face(faces, f, F, V, id)) return;
+  const int32_t a = id[0], b = id[1], c = id[2];
   if (a != b) mp_union(parent, a, b);
   if (a != c && b != c) mp_union(parent, a, c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- flags -> offsets inside a block
-// flag[j] (0 / 1) of the entries i0 .. i0 + MP_PER - 1 of this thread: their exclusive ranks inside the workgroup's MP_SCAN entries, the total
-__device__ __forceinline__ void mp_block_offsets(const uint32_t flag[MP_PER], uint32_t i0, uint32_t n, uint16_t* __restrict__ loc,
-                                                 unsigned long long* __restrict__ base) {
-  __shared__ uint32_t wave_sum[MP_FLAG_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t own = 0;
-#pragma unroll
-  for (int j = 0; j < MP_PER; ++j) own += flag[j];
-  uint32_t incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t below = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < MP_FLAG_WAVES; ++k) {
-    const uint32_t s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  uint32_t excl = below + incl - own;
-#pragma unroll
-  for (int j = 0; j < MP_PER; ++j) {
-    if (i0 + j < n) loc[i0 + j] = (uint16_t)excl;
-    excl += flag[j];
-  }
-  if (tid == 0) base[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(MP_FLAG_THREADS) void parts_roots_kernel(int32_t* parent, uint32_t V, uint16_t* __restrict__ loc,
+__global__ __launch_bounds__(MESH_PER_THREADS) void parts_roots_kernel(int32_t* parent, uint32_t V, uint16_t* __restrict__ loc,
                                                                       unsigned long long* __restrict__ base) {
-  const uint32_t i0 = blockIdx.x * (uint32_t)MP_SCAN + MP_PER * threadIdx.x;
-  uint32_t flag[MP_PER];
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * threadIdx.x;
+  uint32_t flag[MESH_PER];
 #pragma unroll
-  for (int j = 0; j < MP_PER; ++j) {
+  for (int j = 0; j < MESH_PER; ++j) {
     flag[j] = 0;
     const uint32_t i = i0 + j;
     if (i < V) {
@@ -160,98 +114,50 @@ __global__ __launch_bounds__(MP_FLAG_THREADS) void parts_roots_kernel(int32_t* p
       flag[j] = (uint32_t)r == i;
     }
   }
-  mp_block_offsets(flag, i0, V, loc, base);
+  block_offsets(flag, i0, V, 0, loc, base);
 }
 
 __device__ __forceinline__ bool mp_kept(int32_t label, uint32_t K, const uint8_t* __restrict__ keep) {
   return (uint32_t)label < K && keep[label] != 0;   // (a negative label is a large unsigned one: keep[] is read inside [0, K) only)
 }
 
-__global__ __launch_bounds__(MP_FLAG_THREADS) void parts_keep_kernel(const int32_t* __restrict__ labels, uint32_t n, uint32_t K,
+__global__ __launch_bounds__(MESH_PER_THREADS) void parts_keep_kernel(const int32_t* __restrict__ labels, uint32_t n, uint32_t K,
                                                                      const uint8_t* __restrict__ keep, uint16_t* __restrict__ loc,
                                                                      unsigned long long* __restrict__ base) {
-  const uint32_t i0 = blockIdx.x * (uint32_t)MP_SCAN + MP_PER * threadIdx.x;
-  uint32_t flag[MP_PER];
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * threadIdx.x;
+  uint32_t flag[MESH_PER];
 #pragma unroll
-  for (int j = 0; j < MP_PER; ++j) flag[j] = (i0 + j < n && mp_kept(labels[i0 + j], K, keep)) ? 1u : 0u;
-  mp_block_offsets(flag, i0, n, loc, base);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- scan of the block totals
-__device__ __forceinline__ unsigned long long mp_block_scan64(unsigned long long own, unsigned long long* wave_sum, uint32_t lane, uint32_t wave,
-                                                              unsigned long long& total) {
-  unsigned long long incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  __syncthreads();                              // the previous use of wave_sum has been read
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  unsigned long long below = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < MP_WAVES; ++k) {
-    const unsigned long long s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  return below + incl - own;
-}
-
-// a[na] and, when nb > 0, b[nb]: exclusive scans in place; counts[0] = sum a, counts[1] = sum b when two_counts
-__global__ __launch_bounds__(MP_SCAN) void parts_scan_kernel(unsigned long long* __restrict__ a, uint32_t na, unsigned long long* __restrict__ b,
-                                                             uint32_t nb, int two_counts, long long* __restrict__ counts) {
-  __shared__ unsigned long long wave_sum[MP_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry_a = 0, carry_b = 0;
-  const uint32_t top = na > nb ? na : nb;
-  for (uint32_t first = 0; first < top; first += MP_SCAN) {   // (the trip count is the same in every thread: the barriers inside are uniform)
-    const uint32_t j = first + tid;
-    const unsigned long long va = j < na ? a[j] : 0ull, vb = j < nb ? b[j] : 0ull;
-    unsigned long long ta, tb;
-    const unsigned long long ea = mp_block_scan64(va, wave_sum, lane, wave, ta);
-    const unsigned long long eb = mp_block_scan64(vb, wave_sum, lane, wave, tb);
-    if (j < na) a[j] = carry_a + ea;
-    if (j < nb) b[j] = carry_b + eb;
-    carry_a += ta;
-    carry_b += tb;
-  }
-  if (tid == 0) {
-    counts[0] = (long long)carry_a;
-    if (two_counts) counts[1] = (long long)carry_b;
-  }
+  for (int j = 0; j < MESH_PER; ++j) flag[j] = (i0 + j < n && mp_kept(labels[i0 + j], K, keep)) ? 1u : 0u;
+  block_offsets(flag, i0, n, 0, loc, base);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- labels
-__global__ __launch_bounds__(MP_THREADS) void parts_apply_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, MpWorkspace w,
+__global__ __launch_bounds__(MESH_THREADS) void parts_apply_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, MpWorkspace w,
                                                                  int32_t* __restrict__ vertex_part, int32_t* __restrict__ face_part) {
-  const uint32_t i = blockIdx.x * (uint32_t)MP_THREADS + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (i < V) {
     const uint32_t r = (uint32_t)w.parent[i];
-    vertex_part[i] = (int32_t)(w.vbase[r >> MP_SCAN_SHIFT] + w.vloc[r]);
+    vertex_part[i] = (int32_t)(w.vbase[r >> MESH_SCAN_SHIFT] + w.vloc[r]);
   }
-  if (i < F && face_part) {
-    const int32_t a = faces[3 * (size_t)i], b = faces[3 * (size_t)i + 1], c = faces[3 * (size_t)i + 2];
-    int32_t part = -1;
-    if ((uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V) {
-      const uint32_t r = (uint32_t)w.parent[a];
-      part = (int32_t)(w.vbase[r >> MP_SCAN_SHIFT] + w.vloc[r]);
+  if (i < F && face_part) {                     // (i < F here as well: a dropped face below F still gets its -1)
+    int32_t id[3], part = -1;
+    if (load_face(faces, i, F, V, id)) {
+      const uint32_t r = (uint32_t)w.parent[id[0]];
+      part = (int32_t)(w.vbase[r >> MESH_SCAN_SHIFT] + w.vloc[r]);
     }
     face_part[i] = part;
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- sizes
-__global__ __launch_bounds__(MP_THREADS) void parts_sizes_kernel(const int32_t* __restrict__ labels, uint32_t n, uint32_t K, int32_t* out) {
-  __shared__ int32_t wave_label[MP_THREADS / 64];
-  __shared__ uint32_t wave_acc[MP_THREADS / 64];
+__global__ __launch_bounds__(MESH_THREADS) void parts_sizes_kernel(const int32_t* __restrict__ labels, uint32_t n, uint32_t K, int32_t* out) {
+  __shared__ int32_t wave_label[MESH_THREADS / 64];
+  __shared__ uint32_t wave_acc[MESH_THREADS / 64];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t waves = (uint64_t)gridDim.x * (MP_THREADS / 64);
+  const uint64_t waves = (uint64_t)gridDim.x * (MESH_THREADS / 64);
   int32_t acc_label = -1;         // wave-uniform: the label this wave sums in a register, and its sum
   uint32_t acc = 0;
-  for (uint64_t chunk = (uint64_t)blockIdx.x * (MP_THREADS / 64) + wave; chunk * (64 * MP_SIZE_STEPS) < n; chunk += waves) {
+  for (uint64_t chunk = (uint64_t)blockIdx.x * (MESH_THREADS / 64) + wave; chunk * (64 * MP_SIZE_STEPS) < n; chunk += waves) {
     const uint64_t wave_first = chunk * (64 * MP_SIZE_STEPS);
     int32_t mine[MP_SIZE_STEPS];  // every load first: one memory latency a chunk, not sixteen
 #pragma unroll
@@ -285,10 +191,10 @@ __global__ __launch_bounds__(MP_THREADS) void parts_sizes_kernel(const int32_t* 
   if (lane == 0) { wave_label[wave] = acc_label; wave_acc[wave] = acc; }
   __syncthreads();
   if (threadIdx.x == 0) {         // the waves of a workgroup mostly sum the same label: one add for all of them
-    for (int a = 0; a < MP_THREADS / 64; ++a) {
+    for (int a = 0; a < MESH_THREADS / 64; ++a) {
       uint32_t total = wave_acc[a];
       if (!total) continue;
-      for (int b = a + 1; b < MP_THREADS / 64; ++b)
+      for (int b = a + 1; b < MESH_THREADS / 64; ++b)
         if (wave_label[b] == wave_label[a]) { total += wave_acc[b]; wave_acc[b] = 0; }
       atomicAdd(out + wave_label[a], (int32_t)total);
     }
@@ -296,15 +202,15 @@ __global__ __launch_bounds__(MP_THREADS) void parts_sizes_kernel(const int32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- emit
-__global__ __launch_bounds__(MP_THREADS) void parts_emit_kernel(const uint32_t* __restrict__ vertices, const uint32_t* __restrict__ normals,
+__global__ __launch_bounds__(MESH_THREADS) void parts_emit_kernel(const uint32_t* __restrict__ vertices, const uint32_t* __restrict__ normals,
                                                                 const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_part,
                                                                 const int32_t* __restrict__ face_part, uint32_t V, uint32_t F, uint32_t K,
                                                                 const uint8_t* __restrict__ keep, MpWorkspace w, long long v_cap, long long f_cap,
                                                                 uint32_t* __restrict__ out_vertices, uint32_t* __restrict__ out_normals,
                                                                 int32_t* __restrict__ out_faces) {
-  const uint32_t i = blockIdx.x * (uint32_t)MP_THREADS + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (i < V && v_cap > 0 && mp_kept(vertex_part[i], K, keep)) {
-    const long long id = (long long)(w.vbase[i >> MP_SCAN_SHIFT] + w.vloc[i]);
+    const long long id = (long long)(w.vbase[i >> MESH_SCAN_SHIFT] + w.vloc[i]);
     if (id < v_cap) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) out_vertices[3 * id + k] = vertices[3 * (size_t)i + k];
@@ -315,108 +221,81 @@ __global__ __launch_bounds__(MP_THREADS) void parts_emit_kernel(const uint32_t* 
     }
   }
   if (i < F && f_cap > 0 && mp_kept(face_part[i], K, keep)) {
-    const long long id = (long long)(w.fbase[i >> MP_SCAN_SHIFT] + w.floc[i]);
+    const long long id = (long long)(w.fbase[i >> MESH_SCAN_SHIFT] + w.floc[i]);
     if (id < f_cap) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const uint32_t q = (uint32_t)faces[3 * (size_t)i + k];
-        out_faces[3 * id + k] = q < V ? (int32_t)(w.vbase[q >> MP_SCAN_SHIFT] + w.vloc[q]) : -1;
+        out_faces[3 * id + k] = q < V ? (int32_t)(w.vbase[q >> MESH_SCAN_SHIFT] + w.vloc[q]) : -1;
       }
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int mp_fail(int code, const char* who, const char* what) {
-  static thread_local char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_error(code, msg);
-}
-
-static int mp_sizes(const char* who, int64_t V, int64_t F) {
-  if (V < 0 || F < 0) return mp_fail(CRNERF_ERR_SHAPE, who, "negative size");
-  if (V > MP_MAX || F > MP_MAX) return mp_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 vertices or faces in one call");
-  return 0;
-}
-
 static int mp_parts(const char* who, int64_t V, int64_t K) {
-  if (K < 0) return mp_fail(CRNERF_ERR_SHAPE, who, "negative size");
-  if (K > V) return mp_fail(CRNERF_ERR_SHAPE, who, "more parts than vertices (K > V)");
+  if (K < 0) return launch_fail(CRNERF_ERR_SHAPE, who, "negative size");
+  if (K > V) return launch_fail(CRNERF_ERR_SHAPE, who, "more parts than vertices (K > V)");
   return 0;
 }
-
-static inline uint32_t mp_grid(uint32_t n, uint32_t per) { return (uint32_t)(((uint64_t)n + per - 1) / per); }
 
 }  // namespace crnerf
 
 using namespace crnerf;
 
-#define MP_REQUIRE(p, who, name) \
-  if (!(p)) return mp_fail(CRNERF_ERR_NULL, who, name " is NULL")
-#define MP_ALIGNED(p, who) \
-  if ((uintptr_t)(p) & 15u) return mp_fail(CRNERF_ERR_CONFIG, who, "workspace must be 16-byte aligned")
-
 extern "C" size_t crnerf_mesh_parts_workspace_bytes(int64_t V, int64_t F) {
-  if (V <= 0 || F < 0 || V > MP_MAX || F > MP_MAX) return 0;
-  return (size_t)8 * mp_blocks((uint32_t)V) + (size_t)8 * mp_blocks((uint32_t)F) + (size_t)6 * (size_t)V + (size_t)2 * (size_t)F + MP_WORKSPACE_PAD;
+  if (V <= 0 || F < 0 || V > MESH_MAX || F > MESH_MAX) return 0;
+  return (size_t)8 * scan_blocks((uint32_t)V) + (size_t)8 * scan_blocks((uint32_t)F) + (size_t)6 * (size_t)V + (size_t)2 * (size_t)F + MP_WORKSPACE_PAD;
 }
 
 extern "C" int crnerf_mesh_parts_label_i32(const int32_t* faces, int64_t V, int64_t F, void* workspace, int32_t* vertex_part, int32_t* face_part,
                                            int64_t* counts, void* stream) {
   static const char* who = "mesh_parts_label";
-  if (int rc = mp_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (V == 0) {                                 // no vertex: K = 0, nothing is launched
     if (counts && hipMemsetAsync(counts, 0, sizeof(int64_t), st) != hipSuccess)
       return set_error(CRNERF_ERR_HIP, "mesh_parts_label: hipMemsetAsync(counts) failed");
     return 0;
   }
-  MP_REQUIRE(workspace, who, "workspace"); MP_REQUIRE(vertex_part, who, "vertex_part"); MP_REQUIRE(counts, who, "counts");
-  if (F > 0) { MP_REQUIRE(faces, who, "faces"); MP_REQUIRE(face_part, who, "face_part"); }
-  MP_ALIGNED(workspace, who);
+  MESH_REQUIRE(workspace, who, "workspace"); MESH_REQUIRE(vertex_part, who, "vertex_part"); MESH_REQUIRE(counts, who, "counts");
+  if (F > 0) { MESH_REQUIRE(faces, who, "faces"); MESH_REQUIRE(face_part, who, "face_part"); }
+  MESH_ALIGNED(workspace, who);
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const MpWorkspace w = mp_carve(workspace, v, f);
-  hipLaunchKernelGGL(parts_init_kernel, dim3(mp_grid(v, MP_THREADS)), dim3(MP_THREADS), 0, st, w.parent, v);
-  if (int rc = check_launch("parts_init_kernel")) return rc;
+  if (int rc = mesh_launch(parts_init_kernel, "parts_init_kernel", launch_blocks(v, MESH_THREADS), MESH_THREADS, st, w.parent, v)) return rc;
   if (f > 0) {
-    hipLaunchKernelGGL(parts_union_kernel, dim3(mp_grid(f, MP_THREADS)), dim3(MP_THREADS), 0, st, faces, v, f, w.parent);
-    if (int rc = check_launch("parts_union_kernel")) return rc;
+    if (int rc = mesh_launch(parts_union_kernel, "parts_union_kernel", launch_blocks(f, MESH_THREADS), MESH_THREADS, st, faces, v, f, w.parent)) return rc;
   }
-  hipLaunchKernelGGL(parts_roots_kernel, dim3(mp_blocks(v)), dim3(MP_FLAG_THREADS), 0, st, w.parent, v, w.vloc, w.vbase);
-  if (int rc = check_launch("parts_roots_kernel")) return rc;
-  hipLaunchKernelGGL(parts_scan_kernel, dim3(1), dim3(MP_SCAN), 0, st, w.vbase, mp_blocks(v), w.fbase, 0u, 0, (long long*)counts);
-  if (int rc = check_launch("parts_scan_kernel")) return rc;
-  hipLaunchKernelGGL(parts_apply_kernel, dim3(mp_grid(v > f ? v : f, MP_THREADS)), dim3(MP_THREADS), 0, st, faces, v, f, w, vertex_part,
+  if (int rc = mesh_launch(parts_roots_kernel, "parts_roots_kernel", scan_blocks(v), MESH_PER_THREADS, st, w.parent, v, w.vloc, w.vbase)) return rc;
+  if (int rc = mesh_block_scan(st, ScanList<1>{w.vbase, scan_blocks(v), {(long long*)counts}})) return rc;
+  return mesh_launch(parts_apply_kernel, "parts_apply_kernel", launch_blocks(v > f ? v : f, MESH_THREADS), MESH_THREADS, st, faces, v, f, w, vertex_part,
                      f > 0 ? face_part : (int32_t*)nullptr);
-  return check_launch("parts_apply_kernel");
 }
 
 extern "C" int crnerf_mesh_parts_sizes_i32(const int32_t* vertex_part, const int32_t* face_part, int64_t V, int64_t F, int64_t K,
                                            int32_t* part_vertices, int32_t* part_faces, void* stream) {
   static const char* who = "mesh_parts_sizes";
-  if (int rc = mp_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   if (int rc = mp_parts(who, V, K)) return rc;
   if (V == 0 || K == 0) return 0;
-  MP_REQUIRE(vertex_part, who, "vertex_part"); MP_REQUIRE(part_vertices, who, "part_vertices"); MP_REQUIRE(part_faces, who, "part_faces");
-  if (F > 0) MP_REQUIRE(face_part, who, "face_part");
+  MESH_REQUIRE(vertex_part, who, "vertex_part"); MESH_REQUIRE(part_vertices, who, "part_vertices"); MESH_REQUIRE(part_faces, who, "part_faces");
+  if (F > 0) MESH_REQUIRE(face_part, who, "face_part");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(part_vertices, 0, sizeof(int32_t) * (size_t)K, st) != hipSuccess || hipMemsetAsync(part_faces, 0, sizeof(int32_t) * (size_t)K, st) != hipSuccess)
-    return set_error(CRNERF_ERR_HIP, "mesh_parts_sizes: hipMemsetAsync failed");
-  const uint32_t per = MP_THREADS * MP_SIZE_STEPS;
-  auto blocks = [per](uint32_t n) { const uint32_t b = mp_grid(n, per); return b < (uint32_t)MP_SIZE_BLOCKS ? b : (uint32_t)MP_SIZE_BLOCKS; };
-  hipLaunchKernelGGL(parts_sizes_kernel, dim3(blocks((uint32_t)V)), dim3(MP_THREADS), 0, st, vertex_part, (uint32_t)V, (uint32_t)K, part_vertices);
-  if (int rc = check_launch("parts_sizes_kernel")) return rc;
-  if (F > 0) {
-    hipLaunchKernelGGL(parts_sizes_kernel, dim3(blocks((uint32_t)F)), dim3(MP_THREADS), 0, st, face_part, (uint32_t)F, (uint32_t)K, part_faces);
-    return check_launch("parts_sizes_kernel");
-  }
+  MESH_FILL(part_vertices, 0, sizeof(int32_t) * (size_t)K, st, who);
+  MESH_FILL(part_faces, 0, sizeof(int32_t) * (size_t)K, st, who);
+  const uint32_t per = MESH_THREADS * MP_SIZE_STEPS;
+  auto blocks = [per](uint32_t n) { const uint32_t b = launch_blocks(n, per); return b < (uint32_t)MP_SIZE_BLOCKS ? b : (uint32_t)MP_SIZE_BLOCKS; };
+  if (int rc = mesh_launch(parts_sizes_kernel, "parts_sizes_kernel", blocks((uint32_t)V), MESH_THREADS, st, vertex_part, (uint32_t)V, (uint32_t)K, part_vertices))
+    return rc;
+  if (F > 0) return mesh_launch(parts_sizes_kernel, "parts_sizes_kernel", blocks((uint32_t)F), MESH_THREADS, st, face_part, (uint32_t)F, (uint32_t)K, part_faces);
   return 0;
 }
 
 extern "C" int crnerf_mesh_parts_select_count(const int32_t* vertex_part, const int32_t* face_part, int64_t V, int64_t F, int64_t K,
                                               const uint8_t* keep, void* workspace, int64_t* counts, void* stream) {
   static const char* who = "mesh_parts_select_count";
-  if (int rc = mp_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   if (int rc = mp_parts(who, V, K)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (V == 0) {
@@ -424,20 +303,20 @@ extern "C" int crnerf_mesh_parts_select_count(const int32_t* vertex_part, const 
       return set_error(CRNERF_ERR_HIP, "mesh_parts_select_count: hipMemsetAsync(counts) failed");
     return 0;
   }
-  MP_REQUIRE(vertex_part, who, "vertex_part"); MP_REQUIRE(workspace, who, "workspace"); MP_REQUIRE(counts, who, "counts");
-  if (F > 0) MP_REQUIRE(face_part, who, "face_part");
-  if (K > 0) MP_REQUIRE(keep, who, "keep");
-  MP_ALIGNED(workspace, who);
+  MESH_REQUIRE(vertex_part, who, "vertex_part"); MESH_REQUIRE(workspace, who, "workspace"); MESH_REQUIRE(counts, who, "counts");
+  if (F > 0) MESH_REQUIRE(face_part, who, "face_part");
+  if (K > 0) MESH_REQUIRE(keep, who, "keep");
+  MESH_ALIGNED(workspace, who);
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const MpWorkspace w = mp_carve(workspace, v, f);
-  hipLaunchKernelGGL(parts_keep_kernel, dim3(mp_blocks(v)), dim3(MP_FLAG_THREADS), 0, st, vertex_part, v, (uint32_t)K, keep, w.vloc, w.vbase);
-  if (int rc = check_launch("parts_keep_kernel")) return rc;
+  if (int rc = mesh_launch(parts_keep_kernel, "parts_keep_kernel", scan_blocks(v), MESH_PER_THREADS, st, vertex_part, v, (uint32_t)K, keep, w.vloc, w.vbase))
+    return rc;
   if (f > 0) {
-    hipLaunchKernelGGL(parts_keep_kernel, dim3(mp_blocks(f)), dim3(MP_FLAG_THREADS), 0, st, face_part, f, (uint32_t)K, keep, w.floc, w.fbase);
-    if (int rc = check_launch("parts_keep_kernel")) return rc;
+    if (int rc = mesh_launch(parts_keep_kernel, "parts_keep_kernel", scan_blocks(f), MESH_PER_THREADS, st, face_part, f, (uint32_t)K, keep, w.floc, w.fbase))
+      return rc;
   }
-  hipLaunchKernelGGL(parts_scan_kernel, dim3(1), dim3(MP_SCAN), 0, st, w.vbase, mp_blocks(v), w.fbase, mp_blocks(f), 1, (long long*)counts);
-  return check_launch("parts_scan_kernel");
+  long long* const out = (long long*)counts;
+  return mesh_block_scan(st, ScanList<1>{w.vbase, scan_blocks(v), {out}}, ScanList<1>{w.fbase, scan_blocks(f), {out + 1}});
 }
 
 extern "C" int crnerf_mesh_parts_select_emit_f32(const float* vertices, const float* normals, const int32_t* faces, const int32_t* vertex_part,
@@ -445,23 +324,21 @@ extern "C" int crnerf_mesh_parts_select_emit_f32(const float* vertices, const fl
                                                  const void* workspace, int64_t v_cap, int64_t f_cap, float* out_vertices, float* out_normals,
                                                  int32_t* out_faces, void* stream) {
   static const char* who = "mesh_parts_select_emit";
-  if (int rc = mp_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   if (int rc = mp_parts(who, V, K)) return rc;
-  if (v_cap < 0 || f_cap < 0) return mp_fail(CRNERF_ERR_SHAPE, who, "negative capacity");
-  if (v_cap > MP_MAX || f_cap > MP_MAX) return mp_fail(CRNERF_ERR_SHAPE, who, "a capacity above 2^31 - 1 (faces hold int32 vertex ids)");
+  if (int rc = mesh_caps(who, v_cap, f_cap)) return rc;
   const bool want_v = v_cap > 0, want_f = f_cap > 0 && F > 0;
   if (V == 0 || K == 0 || (!want_v && !want_f)) return 0;      // K == 0: nothing is kept
-  MP_REQUIRE(vertex_part, who, "vertex_part"); MP_REQUIRE(keep, who, "keep"); MP_REQUIRE(workspace, who, "workspace");
+  MESH_REQUIRE(vertex_part, who, "vertex_part"); MESH_REQUIRE(keep, who, "keep"); MESH_REQUIRE(workspace, who, "workspace");
   if (want_v) {
-    MP_REQUIRE(vertices, who, "vertices"); MP_REQUIRE(out_vertices, who, "out_vertices");
-    if (normals) MP_REQUIRE(out_normals, who, "out_normals");
+    MESH_REQUIRE(vertices, who, "vertices"); MESH_REQUIRE(out_vertices, who, "out_vertices");
+    if (normals) MESH_REQUIRE(out_normals, who, "out_normals");
   }
-  if (want_f) { MP_REQUIRE(faces, who, "faces"); MP_REQUIRE(face_part, who, "face_part"); MP_REQUIRE(out_faces, who, "out_faces"); }
-  MP_ALIGNED(workspace, who);
+  if (want_f) { MESH_REQUIRE(faces, who, "faces"); MESH_REQUIRE(face_part, who, "face_part"); MESH_REQUIRE(out_faces, who, "out_faces"); }
+  MESH_ALIGNED(workspace, who);
   const uint32_t v = (uint32_t)V, f = want_f ? (uint32_t)F : 0u;
   const MpWorkspace w = mp_carve(const_cast<void*>(workspace), v, (uint32_t)F);
-  hipLaunchKernelGGL(parts_emit_kernel, dim3(mp_grid(v > f ? v : f, MP_THREADS)), dim3(MP_THREADS), 0, (hipStream_t)stream, (const uint32_t*)vertices,
-                     (const uint32_t*)normals, faces, vertex_part, face_part, v, f, (uint32_t)K, keep, w, (long long)v_cap, (long long)f_cap,
-                     (uint32_t*)out_vertices, (uint32_t*)out_normals, out_faces);
-  return check_launch("parts_emit_kernel");
+  return mesh_launch(parts_emit_kernel, "parts_emit_kernel", launch_blocks(v > f ? v : f, MESH_THREADS), MESH_THREADS, (hipStream_t)stream,
+                     (const uint32_t*)vertices, (const uint32_t*)normals, faces, vertex_part, face_part, v, f, (uint32_t)K, keep, w, (long long)v_cap,
+                     (long long)f_cap, (uint32_t*)out_vertices, (uint32_t*)out_normals, out_faces);
 }

@@ -6,8 +6,8 @@
 //   (fill)                    leader[cells] = 0xffffffff, table[T] = -1
 //   cluster_key_kernel        one thread per vertex: key[v] = its cell; atomicMin(leader[key], v) -- by the first lane of every run of equal keys in
 //                             a wave only: the lanes of a wave hold rising ids, so that lane holds the run's smallest
-//   cluster_leaders_kernel    flag[v] = leader[key[v]] == v; workgroup scan over MS_SCAN = 1,024 vertices: each leader's rank inside its block
-//   cluster_scan_kernel       ONE workgroup walks the block totals in chunks of MS_SCAN with a running 64-bit carry: exclusive bases, counts[0]
+//   cluster_leaders_kernel    flag[v] = leader[key[v]] == v; the block scan of mesh_common.h over the flags
+//   mesh_block_scan_kernel    (mesh_common.h) the vertices' block totals: counts[0] and, kept for emit, totals[0]
 //   cluster_apply_kernel      vertex_cluster[v] = base[block(leader)] + rank[leader]; the leader writes ckey[cluster] = key
 //   cluster_faces_kernel      one thread per face: an invalid face is dropped before any of its ids is used; tri[f] = its three cluster ids,
 //                             sorted; tri[f][0] = -1 for an invalid or a collapsed face
@@ -16,12 +16,12 @@
 //                             passed.  A slot never empties and only ever changes to a face of the SAME set, so every face of a set stops at the
 //                             set's one slot, and that slot ends as the set's smallest face index whatever order the inserts ran in.  fslot[f] =
 //                             the slot.  The triples compared were written by the launch before: plain reads
-//   cluster_keep_kernel       kept[f] = survivor && table[fslot[f]] == f; workgroup scan, rank and flag in floc[f]
-//   cluster_scan_kernel       again, over the faces' block totals: counts[1]
+//   cluster_keep_kernel       kept[f] = survivor && table[fslot[f]] == f; block scan, rank and flag in floc[f]
+//   mesh_block_scan_kernel    again, over the faces' block totals: counts[1], totals[1]
 // Emit: (fill) the sums of the clusters below v_cap = 0; cluster_sum_kernel (integer atomicAdd on 64-bit words: exact, so deterministic; the
-// lanes of a run of equal clusters are summed by a segmented wave scan first and the run's last lane adds -- adds to one address retire one
-// after another, about 26 ns each (profiles/r22/mesh_parts.txt), and the ids of an extracted mesh are spatially coherent); cluster_finish_kernel,
-// one thread per cluster; cluster_emit_faces_kernel.
+// lanes of a run of equal clusters are merged first, mesh_common.h, and the run's last lane adds -- adds to one address retire one after
+// another, about 26 ns each (profiles/r22/mesh_parts.txt), and the ids of an extracted mesh are spatially coherent); cluster_finish_kernel, one
+// thread per cluster; cluster_emit_faces_kernel.
 //
 // Coherence.  The XCDs' L2s are not coherent for plain accesses inside one kernel (mesh_parts.hip): leader[] and table[] are touched with
 // agent-scope atomics only -- loads included -- inside the kernels that write them, and the sums by atomic adds only; later launches read all
@@ -32,26 +32,16 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "crnerf_mesh_simplify.h"
-#include "kernels.h"
+#include "mesh_common.h"
 
 namespace crnerf {
 
-constexpr int MS_SCAN = 1024;                   // entries per scan workgroup = per block base
-constexpr int MS_SCAN_SHIFT = 10;
-constexpr int MS_WAVES = MS_SCAN / 64;
-constexpr int MS_PER = 4;                       // consecutive entries per thread of a flag scan
-constexpr int MS_FLAG_THREADS = MS_SCAN / MS_PER;
-constexpr int MS_FLAG_WAVES = MS_FLAG_THREADS / 64;
-constexpr int MS_THREADS = 256;                 // the per-entry kernels
-constexpr int64_t MS_MAX = 0x7fffffffLL;
 constexpr int32_t MS_MAX_AXIS = 1 << 20;
 constexpr int MS_SUMS = 10;                     // per cluster: 3 position sums, the member count, 3 normal sums, 3 colour sums
 constexpr uint16_t MS_KEPT = 0x8000;            // floc[f]: the rank inside the block (< 1,024) and this flag
 constexpr float MS_FIXED = 1048576.0f;          // 2^20
-static_assert((1 << MS_SCAN_SHIFT) == MS_SCAN, "block of an entry = entry >> MS_SCAN_SHIFT");
-static_assert(MS_SCAN <= MS_KEPT, "a rank inside a block and the kept flag share 16 bits");
+static_assert(MESH_SCAN <= MS_KEPT, "a rank inside a block and the kept flag share 16 bits");
 
 struct MsGrid {
   float lo[3], inv[3], cell[3];
@@ -74,8 +64,6 @@ struct MsWorkspace {
   uint64_t slots;                 // T
 };
 
-__host__ __device__ inline uint32_t ms_blocks(uint32_t n) { return (n + MS_SCAN - 1) >> MS_SCAN_SHIFT; }
-inline size_t ms_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 constexpr size_t MS_WORKSPACE_PAD = 192;        // totals[2], and eleven roundings of at most 15 bytes each
 
 static uint64_t ms_slots(uint32_t F) {          // the smallest power of two >= 2 F (F > 0), at most 2^32
@@ -92,16 +80,16 @@ static MsWorkspace ms_carve(void* workspace, uint32_t V, uint32_t F, uint64_t ce
   const uint64_t C = ms_clusters(V, cells);
   w.slots = F ? ms_slots(F) : 0;
   w.totals = (long long*)(p + off); off += 16;
-  w.vbase = (unsigned long long*)(p + off); off = ms_align16(off + 8 * (size_t)ms_blocks(V));
-  w.fbase = (unsigned long long*)(p + off); off = ms_align16(off + 8 * (size_t)ms_blocks(F));
-  w.leader = (uint32_t*)(p + off); off = ms_align16(off + 4 * (size_t)cells);
-  w.key = (int32_t*)(p + off); off = ms_align16(off + 4 * (size_t)V);
-  w.vloc = (uint16_t*)(p + off); off = ms_align16(off + 2 * (size_t)V);
-  w.floc = (uint16_t*)(p + off); off = ms_align16(off + 2 * (size_t)F);
-  w.tri = (int32_t*)(p + off); off = ms_align16(off + 12 * (size_t)F);
-  w.fslot = (uint32_t*)(p + off); off = ms_align16(off + 4 * (size_t)F);
-  w.table = (int32_t*)(p + off); off = ms_align16(off + 4 * (size_t)w.slots);
-  w.ckey = (int32_t*)(p + off); off = ms_align16(off + 4 * (size_t)C);
+  w.vbase = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)scan_blocks(V));
+  w.fbase = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)scan_blocks(F));
+  w.leader = (uint32_t*)(p + off); off = align16(off + 4 * (size_t)cells);
+  w.key = (int32_t*)(p + off); off = align16(off + 4 * (size_t)V);
+  w.vloc = (uint16_t*)(p + off); off = align16(off + 2 * (size_t)V);
+  w.floc = (uint16_t*)(p + off); off = align16(off + 2 * (size_t)F);
+  w.tri = (int32_t*)(p + off); off = align16(off + 12 * (size_t)F);
+  w.fslot = (uint32_t*)(p + off); off = align16(off + 4 * (size_t)F);
+  w.table = (int32_t*)(p + off); off = align16(off + 4 * (size_t)w.slots);
+  w.ckey = (int32_t*)(p + off); off = align16(off + 4 * (size_t)C);
   w.sums = (long long*)(p + off);
   return w;
 }
@@ -136,17 +124,9 @@ __device__ __forceinline__ int32_t ms_fixed(float x, float lo, float hi) {
   return q > qlo ? q : qlo;
 }
 
-// the first lane of the run of equal `id`s this lane lies in (the lanes of a wave hold consecutive entries); every lane takes part
-__device__ __forceinline__ uint32_t ms_run_first(int32_t id, uint32_t lane, unsigned long long& heads) {
-  const int32_t before = __shfl_up(id, 1, 64);
-  heads = __ballot(lane == 0 || before != id);
-  const unsigned long long upto = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
-  return 63u - (uint32_t)__clzll((long long)upto);      // (bit 0 of heads is set: upto != 0)
-}
-
-__global__ __launch_bounds__(MS_THREADS) void cluster_key_kernel(const float* __restrict__ vertices, uint32_t V, MsGrid g, int32_t* __restrict__ key,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_key_kernel(const float* __restrict__ vertices, uint32_t V, MsGrid g, int32_t* __restrict__ key,
                                                                  uint32_t* leader) {
-  const uint32_t v = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   int32_t k = -1;                                            // (past the end: a run of its own that adds nothing)
   if (v < V) {
     float s;
@@ -157,126 +137,52 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_key_kernel(const float* __
     key[v] = k;
   }
   unsigned long long heads;
-  const uint32_t first = ms_run_first(k, lane, heads);
+  const uint32_t first = run_first(k, lane, heads);
   if (v < V && first == lane) atomicMin(leader + k, v);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- flags -> offsets inside a block
-// flag[j] (0 / 1) of the entries i0 .. i0 + MS_PER - 1 of this thread: their exclusive ranks inside the workgroup's MS_SCAN entries (or'ed with
-// mark when the flag is set), the total
-__device__ __forceinline__ void ms_block_offsets(const uint32_t flag[MS_PER], uint32_t i0, uint32_t n, uint16_t mark, uint16_t* __restrict__ loc,
-                                                 unsigned long long* __restrict__ base) {
-  __shared__ uint32_t wave_sum[MS_FLAG_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t own = 0;
-#pragma unroll
-  for (int j = 0; j < MS_PER; ++j) own += flag[j];
-  uint32_t incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t below = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < MS_FLAG_WAVES; ++k) {
-    const uint32_t s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  uint32_t excl = below + incl - own;
-#pragma unroll
-  for (int j = 0; j < MS_PER; ++j) {
-    if (i0 + j < n) loc[i0 + j] = (uint16_t)(excl | (flag[j] ? mark : 0));
-    excl += flag[j];
-  }
-  if (tid == 0) base[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(MS_FLAG_THREADS) void cluster_leaders_kernel(const int32_t* __restrict__ key, const uint32_t* __restrict__ leader, uint32_t V,
+__global__ __launch_bounds__(MESH_PER_THREADS) void cluster_leaders_kernel(const int32_t* __restrict__ key, const uint32_t* __restrict__ leader, uint32_t V,
                                                                           uint16_t* __restrict__ loc, unsigned long long* __restrict__ base) {
-  const uint32_t i0 = blockIdx.x * (uint32_t)MS_SCAN + MS_PER * threadIdx.x;
-  uint32_t flag[MS_PER];
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * threadIdx.x;
+  uint32_t flag[MESH_PER];
 #pragma unroll
-  for (int j = 0; j < MS_PER; ++j) flag[j] = (i0 + j < V && leader[key[i0 + j]] == i0 + j) ? 1u : 0u;
-  ms_block_offsets(flag, i0, V, 0, loc, base);
+  for (int j = 0; j < MESH_PER; ++j) flag[j] = (i0 + j < V && leader[key[i0 + j]] == i0 + j) ? 1u : 0u;
+  block_offsets(flag, i0, V, 0, loc, base);
 }
 
-__global__ __launch_bounds__(MS_FLAG_THREADS) void cluster_keep_kernel(const int32_t* __restrict__ tri, const uint32_t* __restrict__ fslot,
+__global__ __launch_bounds__(MESH_PER_THREADS) void cluster_keep_kernel(const int32_t* __restrict__ tri, const uint32_t* __restrict__ fslot,
                                                                        const int32_t* __restrict__ table, uint32_t F, uint16_t* __restrict__ loc,
                                                                        unsigned long long* __restrict__ base) {
-  const uint32_t i0 = blockIdx.x * (uint32_t)MS_SCAN + MS_PER * threadIdx.x;
-  uint32_t flag[MS_PER];
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * threadIdx.x;
+  uint32_t flag[MESH_PER];
 #pragma unroll
-  for (int j = 0; j < MS_PER; ++j) {
+  for (int j = 0; j < MESH_PER; ++j) {
     const uint32_t f = i0 + j;
     flag[j] = (f < F && tri[3 * (size_t)f] >= 0 && table[fslot[f]] == (int32_t)f) ? 1u : 0u;
   }
-  ms_block_offsets(flag, i0, F, MS_KEPT, loc, base);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- scan of the block totals
-__device__ __forceinline__ unsigned long long ms_block_scan64(unsigned long long own, unsigned long long* wave_sum, uint32_t lane, uint32_t wave,
-                                                              unsigned long long& total) {
-  unsigned long long incl = own;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  __syncthreads();                              // the previous use of wave_sum has been read
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  unsigned long long below = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < MS_WAVES; ++k) {
-    const unsigned long long s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  return below + incl - own;
-}
-
-// a[na]: exclusive scan in place; *count = *kept = sum a (0 when na == 0)
-__global__ __launch_bounds__(MS_SCAN) void cluster_scan_kernel(unsigned long long* __restrict__ a, uint32_t na, long long* __restrict__ count,
-                                                               long long* __restrict__ kept) {
-  __shared__ unsigned long long wave_sum[MS_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry = 0;
-  for (uint32_t first = 0; first < na; first += MS_SCAN) {    // (the trip count is the same in every thread: the barriers inside are uniform)
-    const uint32_t j = first + tid;
-    const unsigned long long va = j < na ? a[j] : 0ull;
-    unsigned long long ta;
-    const unsigned long long ea = ms_block_scan64(va, wave_sum, lane, wave, ta);
-    if (j < na) a[j] = carry + ea;
-    carry += ta;
-  }
-  if (tid == 0) *count = *kept = (long long)carry;
+  block_offsets(flag, i0, F, MS_KEPT, loc, base);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- cluster ids
-__global__ __launch_bounds__(MS_THREADS) void cluster_apply_kernel(uint32_t V, MsWorkspace w, int32_t* __restrict__ vertex_cluster) {
-  const uint32_t v = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void cluster_apply_kernel(uint32_t V, MsWorkspace w, int32_t* __restrict__ vertex_cluster) {
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const int32_t k = w.key[v];
   const uint32_t l = w.leader[k];                            // <= v < V: some member lowered it
-  const int32_t id = (int32_t)(w.vbase[l >> MS_SCAN_SHIFT] + w.vloc[l]);
+  const int32_t id = (int32_t)(w.vbase[l >> MESH_SCAN_SHIFT] + w.vloc[l]);
   vertex_cluster[v] = id;
   if (l == v) w.ckey[id] = k;                                // id < the number of occupied cells <= min(V, cells)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- faces
-__global__ __launch_bounds__(MS_THREADS) void cluster_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_cluster,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_cluster,
                                                                    uint32_t V, uint32_t F, int32_t* __restrict__ tri) {
-  const uint32_t f = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x;
-  if (f >= F) return;
-  const int32_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  int32_t x = -1, y = -1, z = -1;
-  if ((uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V) {      // (a negative id is a large unsigned one)
-    x = vertex_cluster[a]; y = vertex_cluster[b]; z = vertex_cluster[c];
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
+  if (f >= F) return;                                        // (tested here as well: a dropped face below F still gets its tri[f])
+  int32_t id[3], x = -1, y = -1, z = -1;
+  if (load_face(faces, f, F, V, id)) {
+    x = vertex_cluster[id[0]]; y = vertex_cluster[id[1]]; z = vertex_cluster[id[2]];
     if (x == y || x == z || y == z) {
       x = y = z = -1;
     } else {
@@ -296,9 +202,9 @@ __device__ __forceinline__ uint32_t ms_hash(uint32_t x, uint32_t y, uint32_t z) 
   return h;
 }
 
-__global__ __launch_bounds__(MS_THREADS) void cluster_insert_kernel(const int32_t* __restrict__ tri, uint32_t F, uint32_t mask, int32_t* table,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_insert_kernel(const int32_t* __restrict__ tri, uint32_t F, uint32_t mask, int32_t* table,
                                                                     uint32_t* __restrict__ fslot) {
-  const uint32_t f = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x;
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (f >= F) return;
   const int32_t x = tri[3 * (size_t)f], y = tri[3 * (size_t)f + 1], z = tri[3 * (size_t)f + 2];
   if (x < 0) return;
@@ -321,22 +227,12 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_insert_kernel(const int32_
 }
 
 // ---------------------------------------------------------------------------------------------------------------- emit
-// inclusive sum of x over the lanes first .. lane of this lane's run (first: ms_run_first)
-__device__ __forceinline__ int32_t ms_run_sum(int32_t x, uint32_t lane, uint32_t first) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int32_t up = __shfl_up(x, d, 64);
-    if (lane >= first + (uint32_t)d) x += up;
-  }
-  return x;
-}
-
 __device__ __forceinline__ void ms_add(long long* p, int32_t x) { atomicAdd((unsigned long long*)p, (unsigned long long)(long long)x); }
 
-__global__ __launch_bounds__(MS_THREADS) void cluster_sum_kernel(const float* __restrict__ vertices, const float* __restrict__ normals,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_sum_kernel(const float* __restrict__ vertices, const float* __restrict__ normals,
                                                                  const float* __restrict__ colors, const int32_t* __restrict__ vertex_cluster,
                                                                  uint32_t V, MsGrid g, long long v_cap, long long* sums) {
-  const uint32_t v = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   int32_t id = -1, r[3] = {0, 0, 0}, qn[3] = {0, 0, 0}, qc[3] = {0, 0, 0};
   if (v < V) {
     id = vertex_cluster[v];
@@ -354,13 +250,13 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_sum_kernel(const float* __
   }
   // a run is at most 64 lanes long: its sums stay below 2^27 in magnitude
   unsigned long long heads;
-  const uint32_t first = ms_run_first(id, lane, heads);
-  const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+  const uint32_t first = run_first(id, lane, heads);
+  const bool last = run_last(heads, lane);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    r[a] = ms_run_sum(r[a], lane, first);
-    if (normals) qn[a] = ms_run_sum(qn[a], lane, first);     // (normals, colors: the same in every lane)
-    if (colors) qc[a] = ms_run_sum(qc[a], lane, first);
+    r[a] = run_sum(r[a], lane, first);
+    if (normals) qn[a] = run_sum(qn[a], lane, first);        // (normals, colors: the same in every lane)
+    if (colors) qc[a] = run_sum(qc[a], lane, first);
   }
   if (id < 0 || !last) return;
   long long* p = sums + (size_t)MS_SUMS * (size_t)id;
@@ -373,11 +269,11 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_sum_kernel(const float* __
   ms_add(p + 3, (int32_t)(lane - first + 1));
 }
 
-__global__ __launch_bounds__(MS_THREADS) void cluster_finish_kernel(const long long* __restrict__ totals, const int32_t* __restrict__ ckey,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_finish_kernel(const long long* __restrict__ totals, const int32_t* __restrict__ ckey,
                                                                     const long long* __restrict__ sums, MsGrid g, long long v_cap, int has_normals,
                                                                     int has_colors, float* __restrict__ out_vertices, float* __restrict__ out_normals,
                                                                     float* __restrict__ out_colors) {
-  const long long id = (long long)blockIdx.x * MS_THREADS + threadIdx.x;
+  const long long id = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (id >= v_cap || id >= totals[0]) return;                // (a row past V' is not written either)
   const long long* p = sums + (size_t)MS_SUMS * (size_t)id;
   int32_t k = ckey[id];
@@ -405,20 +301,20 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_finish_kernel(const long l
   }
 }
 
-__global__ __launch_bounds__(MS_THREADS) void cluster_emit_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_cluster,
+__global__ __launch_bounds__(MESH_THREADS) void cluster_emit_faces_kernel(const int32_t* __restrict__ faces, const int32_t* __restrict__ vertex_cluster,
                                                                         uint32_t V, uint32_t F, const uint16_t* __restrict__ floc,
                                                                         const unsigned long long* __restrict__ fbase, long long f_cap,
                                                                         int32_t* __restrict__ out_faces) {
-  const uint32_t f = blockIdx.x * (uint32_t)MS_THREADS + threadIdx.x;
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (f >= F) return;
   const uint16_t loc = floc[f];
   if (!(loc & MS_KEPT)) return;
-  const long long id = (long long)(fbase[f >> MS_SCAN_SHIFT] + (loc & (MS_KEPT - 1)));
+  const long long id = (long long)(fbase[f >> MESH_SCAN_SHIFT] + (loc & (MS_KEPT - 1)));
   if (id >= f_cap) return;
   // kept: the ids passed the test of cluster_faces_kernel; they are tested again -- emit may be handed other faces than count was
-  const int32_t i = faces[3 * (size_t)f], j = faces[3 * (size_t)f + 1], k = faces[3 * (size_t)f + 2];
-  if ((uint32_t)i >= V || (uint32_t)j >= V || (uint32_t)k >= V) return;
-  const int32_t a = vertex_cluster[i], b = vertex_cluster[j], c = vertex_cluster[k];
+  int32_t id3[3];
+  if (!load_face(faces, f, F, V, id3)) return;
+  const int32_t a = vertex_cluster[id3[0]], b = vertex_cluster[id3[1]], c = vertex_cluster[id3[2]];
   int32_t x = a, y = b, z = c;                               // the cycle as given, the smallest id first
   if (b < a && b < c) { x = b; y = c; z = a; }
   else if (c < a && c < b) { x = c; y = a; z = b; }
@@ -426,55 +322,34 @@ __global__ __launch_bounds__(MS_THREADS) void cluster_emit_faces_kernel(const in
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int ms_fail(int code, const char* who, const char* what) {
-  static thread_local char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_error(code, msg);
-}
-
-static int ms_sizes(const char* who, int64_t V, int64_t F) {
-  if (V < 0 || F < 0) return ms_fail(CRNERF_ERR_SHAPE, who, "negative size");
-  if (V > MS_MAX || F > MS_MAX) return ms_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 vertices or faces in one call");
-  return 0;
-}
-
 // the nine scalars, judged and folded into an MsGrid; *cells = n0 n1 n2
 static int ms_grid_of(const char* who, const float lo[3], const float cell[3], const int32_t n[3], MsGrid* g, uint64_t* cells) {
   uint64_t total = 1;
   for (int a = 0; a < 3; ++a) {
-    if (n[a] < 1) return ms_fail(CRNERF_ERR_SHAPE, who, "fewer than one cell on an axis");
-    if (n[a] > MS_MAX_AXIS) return ms_fail(CRNERF_ERR_SHAPE, who, "more than 2^20 cells on an axis");
+    if (n[a] < 1) return launch_fail(CRNERF_ERR_SHAPE, who, "fewer than one cell on an axis");
+    if (n[a] > MS_MAX_AXIS) return launch_fail(CRNERF_ERR_SHAPE, who, "more than 2^20 cells on an axis");
     total *= (uint64_t)n[a];                                 // <= 2^60
   }
-  if (total > (uint64_t)MS_MAX) return ms_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 cells");
+  if (total > (uint64_t)MESH_MAX) return launch_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 cells");
   for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(cell[a]) || !(cell[a] > 0.0f)) return ms_fail(CRNERF_ERR_SHAPE, who, "a cell size that is not finite and > 0");
+    if (!std::isfinite(cell[a]) || !(cell[a] > 0.0f)) return launch_fail(CRNERF_ERR_SHAPE, who, "a cell size that is not finite and > 0");
     const float inv = 1.0f / cell[a];
-    if (!std::isfinite(inv)) return ms_fail(CRNERF_ERR_SHAPE, who, "a cell size whose float32 reciprocal is not finite");
-    if (!std::isfinite(lo[a])) return ms_fail(CRNERF_ERR_SHAPE, who, "a box origin that is not finite");
+    if (!std::isfinite(inv)) return launch_fail(CRNERF_ERR_SHAPE, who, "a cell size whose float32 reciprocal is not finite");
+    if (!std::isfinite(lo[a])) return launch_fail(CRNERF_ERR_SHAPE, who, "a box origin that is not finite");
     g->lo[a] = lo[a]; g->inv[a] = inv; g->cell[a] = cell[a]; g->n[a] = n[a];
   }
   *cells = total;
   return 0;
 }
 
-static inline uint32_t ms_launch_blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
 }  // namespace crnerf
 
 using namespace crnerf;
 
-#define MS_REQUIRE(p, who, name) \
-  if (!(p)) return ms_fail(CRNERF_ERR_NULL, who, name " is NULL")
-#define MS_ALIGNED(p, who) \
-  if ((uintptr_t)(p) & 15u) return ms_fail(CRNERF_ERR_CONFIG, who, "workspace must be 16-byte aligned")
-#define MS_FILL(p, byte, bytes, who) \
-  if (hipMemsetAsync(p, byte, bytes, st) != hipSuccess) return ms_fail(CRNERF_ERR_HIP, who, "hipMemsetAsync failed")
-
 extern "C" size_t crnerf_mesh_cluster_workspace_bytes(int64_t V, int64_t F, int64_t cells) {
-  if (V <= 0 || F < 0 || V > MS_MAX || F > MS_MAX || cells < 1 || cells > MS_MAX) return 0;
+  if (V <= 0 || F < 0 || V > MESH_MAX || F > MESH_MAX || cells < 1 || cells > MESH_MAX) return 0;
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
-  return (size_t)8 * ms_blocks(v) + (size_t)8 * ms_blocks(f) + (size_t)4 * (size_t)cells + (size_t)6 * (size_t)V + (size_t)18 * (size_t)F +
+  return (size_t)8 * scan_blocks(v) + (size_t)8 * scan_blocks(f) + (size_t)4 * (size_t)cells + (size_t)6 * (size_t)V + (size_t)18 * (size_t)F +
          (size_t)4 * (size_t)(f ? ms_slots(f) : 0) + (size_t)(4 + 8 * MS_SUMS) * (size_t)ms_clusters(v, (uint64_t)cells) + MS_WORKSPACE_PAD;
 }
 
@@ -482,7 +357,7 @@ extern "C" int crnerf_mesh_cluster_count_f32(const float* vertices, const int32_
                                              float cell0, float cell1, float cell2, int32_t n0, int32_t n1, int32_t n2, void* workspace,
                                              int32_t* vertex_cluster, int64_t* counts, void* stream) {
   static const char* who = "mesh_cluster_count";
-  if (int rc = ms_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   MsGrid g;
   uint64_t cells;
   const float lo[3] = {lo0, lo1, lo2}, cell[3] = {cell0, cell1, cell2};
@@ -490,36 +365,32 @@ extern "C" int crnerf_mesh_cluster_count_f32(const float* vertices, const int32_
   if (int rc = ms_grid_of(who, lo, cell, n, &g, &cells)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (V == 0) {                                 // no vertex: V' = F' = 0, nothing is launched
-    if (counts) MS_FILL(counts, 0, 2 * sizeof(int64_t), who);
+    if (counts) MESH_FILL(counts, 0, 2 * sizeof(int64_t), st, who);
     return 0;
   }
-  MS_REQUIRE(vertices, who, "vertices"); MS_REQUIRE(workspace, who, "workspace"); MS_REQUIRE(vertex_cluster, who, "vertex_cluster");
-  MS_REQUIRE(counts, who, "counts");
-  if (F > 0) MS_REQUIRE(faces, who, "faces");
-  MS_ALIGNED(workspace, who);
+  MESH_REQUIRE(vertices, who, "vertices"); MESH_REQUIRE(workspace, who, "workspace"); MESH_REQUIRE(vertex_cluster, who, "vertex_cluster");
+  MESH_REQUIRE(counts, who, "counts");
+  if (F > 0) MESH_REQUIRE(faces, who, "faces");
+  MESH_ALIGNED(workspace, who);
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const MsWorkspace w = ms_carve(workspace, v, f, cells);
-  MS_FILL(w.leader, 0xff, 4 * (size_t)cells, who);
-  hipLaunchKernelGGL(cluster_key_kernel, dim3(ms_launch_blocks(v, MS_THREADS)), dim3(MS_THREADS), 0, st, vertices, v, g, w.key, w.leader);
-  if (int rc = check_launch("cluster_key_kernel")) return rc;
-  hipLaunchKernelGGL(cluster_leaders_kernel, dim3(ms_blocks(v)), dim3(MS_FLAG_THREADS), 0, st, w.key, w.leader, v, w.vloc, w.vbase);
-  if (int rc = check_launch("cluster_leaders_kernel")) return rc;
-  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(MS_SCAN), 0, st, w.vbase, ms_blocks(v), (long long*)counts, w.totals);
-  if (int rc = check_launch("cluster_scan_kernel")) return rc;
-  hipLaunchKernelGGL(cluster_apply_kernel, dim3(ms_launch_blocks(v, MS_THREADS)), dim3(MS_THREADS), 0, st, v, w, vertex_cluster);
-  if (int rc = check_launch("cluster_apply_kernel")) return rc;
+  const uint32_t vblocks = launch_blocks(v, MESH_THREADS), fblocks = launch_blocks(f, MESH_THREADS);
+  long long* const out = (long long*)counts;
+  MESH_FILL(w.leader, 0xff, 4 * (size_t)cells, st, who);
+  if (int rc = mesh_launch(cluster_key_kernel, "cluster_key_kernel", vblocks, MESH_THREADS, st, vertices, v, g, w.key, w.leader)) return rc;
+  if (int rc = mesh_launch(cluster_leaders_kernel, "cluster_leaders_kernel", scan_blocks(v), MESH_PER_THREADS, st, w.key, w.leader, v, w.vloc, w.vbase))
+    return rc;
+  if (int rc = mesh_block_scan(st, ScanList<2>{w.vbase, scan_blocks(v), {out, w.totals}})) return rc;
+  if (int rc = mesh_launch(cluster_apply_kernel, "cluster_apply_kernel", vblocks, MESH_THREADS, st, v, w, vertex_cluster)) return rc;
   if (f > 0) {
-    MS_FILL(w.table, 0xff, 4 * (size_t)w.slots, who);
-    hipLaunchKernelGGL(cluster_faces_kernel, dim3(ms_launch_blocks(f, MS_THREADS)), dim3(MS_THREADS), 0, st, faces, vertex_cluster, v, f, w.tri);
-    if (int rc = check_launch("cluster_faces_kernel")) return rc;
-    hipLaunchKernelGGL(cluster_insert_kernel, dim3(ms_launch_blocks(f, MS_THREADS)), dim3(MS_THREADS), 0, st, w.tri, f, (uint32_t)(w.slots - 1), w.table,
-                       w.fslot);
-    if (int rc = check_launch("cluster_insert_kernel")) return rc;
-    hipLaunchKernelGGL(cluster_keep_kernel, dim3(ms_blocks(f)), dim3(MS_FLAG_THREADS), 0, st, w.tri, w.fslot, w.table, f, w.floc, w.fbase);
-    if (int rc = check_launch("cluster_keep_kernel")) return rc;
+    MESH_FILL(w.table, 0xff, 4 * (size_t)w.slots, st, who);
+    if (int rc = mesh_launch(cluster_faces_kernel, "cluster_faces_kernel", fblocks, MESH_THREADS, st, faces, vertex_cluster, v, f, w.tri)) return rc;
+    if (int rc = mesh_launch(cluster_insert_kernel, "cluster_insert_kernel", fblocks, MESH_THREADS, st, w.tri, f, (uint32_t)(w.slots - 1), w.table, w.fslot))
+      return rc;
+    if (int rc = mesh_launch(cluster_keep_kernel, "cluster_keep_kernel", scan_blocks(f), MESH_PER_THREADS, st, w.tri, w.fslot, w.table, f, w.floc, w.fbase))
+      return rc;
   }
-  hipLaunchKernelGGL(cluster_scan_kernel, dim3(1), dim3(MS_SCAN), 0, st, w.fbase, ms_blocks(f), (long long*)counts + 1, w.totals + 1);
-  return check_launch("cluster_scan_kernel");
+  return mesh_block_scan(st, ScanList<2>{w.fbase, scan_blocks(f), {out + 1, w.totals + 1}});      // (F = 0: no block, the sum is 0)
 }
 
 extern "C" int crnerf_mesh_cluster_emit_f32(const float* vertices, const float* normals, const float* colors, const int32_t* faces,
@@ -528,9 +399,8 @@ extern "C" int crnerf_mesh_cluster_emit_f32(const float* vertices, const float* 
                                             int64_t f_cap, float* out_vertices, float* out_normals, float* out_colors, int32_t* out_faces,
                                             void* stream) {
   static const char* who = "mesh_cluster_emit";
-  if (int rc = ms_sizes(who, V, F)) return rc;
-  if (v_cap < 0 || f_cap < 0) return ms_fail(CRNERF_ERR_SHAPE, who, "negative capacity");
-  if (v_cap > MS_MAX || f_cap > MS_MAX) return ms_fail(CRNERF_ERR_SHAPE, who, "a capacity above 2^31 - 1 (faces hold int32 vertex ids)");
+  if (int rc = mesh_sizes(who, V, F)) return rc;
+  if (int rc = mesh_caps(who, v_cap, f_cap)) return rc;
   MsGrid g;
   uint64_t cells;
   const float lo[3] = {lo0, lo1, lo2}, cell[3] = {cell0, cell1, cell2};
@@ -538,31 +408,29 @@ extern "C" int crnerf_mesh_cluster_emit_f32(const float* vertices, const float* 
   if (int rc = ms_grid_of(who, lo, cell, n, &g, &cells)) return rc;
   const bool want_v = v_cap > 0, want_f = f_cap > 0 && F > 0;
   if (V == 0 || (!want_v && !want_f)) return 0;
-  MS_REQUIRE(vertex_cluster, who, "vertex_cluster"); MS_REQUIRE(workspace, who, "workspace");
+  MESH_REQUIRE(vertex_cluster, who, "vertex_cluster"); MESH_REQUIRE(workspace, who, "workspace");
   if (want_v) {
-    MS_REQUIRE(vertices, who, "vertices"); MS_REQUIRE(out_vertices, who, "out_vertices");
-    if (normals) MS_REQUIRE(out_normals, who, "out_normals");
-    if (colors) MS_REQUIRE(out_colors, who, "out_colors");
+    MESH_REQUIRE(vertices, who, "vertices"); MESH_REQUIRE(out_vertices, who, "out_vertices");
+    if (normals) MESH_REQUIRE(out_normals, who, "out_normals");
+    if (colors) MESH_REQUIRE(out_colors, who, "out_colors");
   }
-  if (want_f) { MS_REQUIRE(faces, who, "faces"); MS_REQUIRE(out_faces, who, "out_faces"); }
-  MS_ALIGNED(workspace, who);
+  if (want_f) { MESH_REQUIRE(faces, who, "faces"); MESH_REQUIRE(out_faces, who, "out_faces"); }
+  MESH_ALIGNED(workspace, who);
   hipStream_t st = (hipStream_t)stream;
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const MsWorkspace w = ms_carve(workspace, v, f, cells);
   if (want_v) {
     const uint64_t C = ms_clusters(v, cells), rows = (uint64_t)v_cap < C ? (uint64_t)v_cap : C;      // V' <= C: no cluster id reaches C
-    MS_FILL(w.sums, 0, sizeof(long long) * MS_SUMS * (size_t)rows, who);
-    hipLaunchKernelGGL(cluster_sum_kernel, dim3(ms_launch_blocks(v, MS_THREADS)), dim3(MS_THREADS), 0, st, vertices, normals, colors, vertex_cluster, v, g,
-                       (long long)rows, w.sums);
-    if (int rc = check_launch("cluster_sum_kernel")) return rc;
-    hipLaunchKernelGGL(cluster_finish_kernel, dim3(ms_launch_blocks(rows, MS_THREADS)), dim3(MS_THREADS), 0, st, w.totals, w.ckey, w.sums, g,
-                       (long long)rows, normals ? 1 : 0, colors ? 1 : 0, out_vertices, out_normals, out_colors);
-    if (int rc = check_launch("cluster_finish_kernel")) return rc;
+    MESH_FILL(w.sums, 0, sizeof(long long) * MS_SUMS * (size_t)rows, st, who);
+    if (int rc = mesh_launch(cluster_sum_kernel, "cluster_sum_kernel", launch_blocks(v, MESH_THREADS), MESH_THREADS, st, vertices, normals, colors,
+                             vertex_cluster, v, g, (long long)rows, w.sums))
+      return rc;
+    if (int rc = mesh_launch(cluster_finish_kernel, "cluster_finish_kernel", launch_blocks(rows, MESH_THREADS), MESH_THREADS, st, w.totals, w.ckey, w.sums, g,
+                             (long long)rows, normals ? 1 : 0, colors ? 1 : 0, out_vertices, out_normals, out_colors))
+      return rc;
   }
-  if (want_f) {
-    hipLaunchKernelGGL(cluster_emit_faces_kernel, dim3(ms_launch_blocks(f, MS_THREADS)), dim3(MS_THREADS), 0, st, faces, vertex_cluster, v, f, w.floc, w.fbase,
-                       (long long)f_cap, out_faces);
-    return check_launch("cluster_emit_faces_kernel");
-  }
+  if (want_f)
+    return mesh_launch(cluster_emit_faces_kernel, "cluster_emit_faces_kernel", launch_blocks(f, MESH_THREADS), MESH_THREADS, st, faces, vertex_cluster, v, f,
+                       w.floc, w.fbase, (long long)f_cap, out_faces);
   return 0;
 }

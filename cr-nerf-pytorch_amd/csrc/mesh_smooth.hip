@@ -4,12 +4,11 @@
 // Adjacency, five launches (three when F = 0) behind one fill, none of which waits on another workgroup:
 //   (fill)                    deg[V] = cursor[V] = 0, h[V] = 0
 //   smooth_degree_kernel      one thread per face: an invalid face is dropped before any of its ids is used; per corner deg += 2 and
-//                             h += mix(next) - mix(prev), by the last lane of every run of equal ids in a wave only (the run's sums are made in
-//                             registers first: adds to one address retire one after another, about 26 ns each, profiles/r22/mesh_parts.txt, and an
+//                             h += mix(next) - mix(prev), by the last lane of every run of equal ids in a wave only (the run merge of
+//                             mesh_common.h: adds to one address retire one after another, about 26 ns each, profiles/r22/mesh_parts.txt, and an
 //                             extracted mesh lists the fan of a vertex in neighbouring faces)
-//   smooth_offsets_kernel     workgroup scan of deg over SM_SCAN = 1,024 vertices: each row's start inside its block, the block's total
-//   smooth_scan_kernel        ONE workgroup walks the block totals in chunks of SM_SCAN with a running 64-bit carry: exclusive bases
-//                             (the scan of mesh_parts.hip and mesh_simplify.hip, restated: a __global__ of one name cannot live in two units)
+//   smooth_offsets_kernel     the block scan of mesh_common.h over deg, in 64 bits: each row's start inside its block, the block's total
+//   mesh_block_scan_kernel    (mesh_common.h) the block totals: exclusive bases, no sum is kept
 //   smooth_fill_kernel        one thread per face: the first lane of a run takes 2 x (run length) slots of the row with ONE add on cursor[id] and
 //                             hands them out; nbr[start + slot] = next, prev.  The order inside a row follows the order the adds retire in
 // Smooth: smooth_quantise_kernel (P as 16 bytes a vertex: the three lattice coordinates and, in the fourth word, the row's length -- 0 for a
@@ -27,24 +26,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include "crnerf_mesh_smooth.h"
-#include "kernels.h"
+#include "mesh_common.h"
 
 namespace crnerf {
 
-constexpr int SM_SCAN = 1024;                   // vertices per scan workgroup = per block base
-constexpr int SM_SCAN_SHIFT = 10;
-constexpr int SM_WAVES = SM_SCAN / 64;
-constexpr int SM_PER = 4;                       // consecutive vertices per thread of the offsets scan
-constexpr int SM_OFF_THREADS = SM_SCAN / SM_PER;
-constexpr int SM_OFF_WAVES = SM_OFF_THREADS / 64;
-constexpr int SM_THREADS = 256;                 // the per-entry kernels
 constexpr uint32_t SM_LONG = 64;                // entries: a longer row is summed by the wave together
-constexpr int64_t SM_MAX = 0x7fffffffLL;
 constexpr int32_t SM_ONE = 1 << 30;             // the lattice: P in [0, 2^30]
 constexpr int32_t SM_MAX_STEPS = 65536;
-static_assert((1 << SM_SCAN_SHIFT) == SM_SCAN, "block of a vertex = vertex >> SM_SCAN_SHIFT");
 
 struct SmWorkspace {
   unsigned long long* base;       // [nb] block totals, then exclusive bases
@@ -58,44 +47,22 @@ struct SmWorkspace {
   int32_t* nbr;                   // [6 F]
 };
 
-__host__ __device__ inline uint32_t sm_blocks(uint32_t n) { return (n + SM_SCAN - 1) >> SM_SCAN_SHIFT; }
-inline size_t sm_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 constexpr size_t SM_WORKSPACE_PAD = 192;        // nine roundings of at most 15 bytes each, and room to spare
 
 static SmWorkspace sm_carve(void* workspace, uint32_t V) {
   SmWorkspace w;
   char* p = (char*)workspace;
   size_t off = 0;
-  w.base = (unsigned long long*)(p + off); off = sm_align16(off + 8 * (size_t)sm_blocks(V));
-  w.deg = (uint32_t*)(p + off); off = sm_align16(off + 4 * (size_t)V);
-  w.cursor = (uint32_t*)(p + off); off = sm_align16(off + 4 * (size_t)V);
-  w.h = (unsigned long long*)(p + off); off = sm_align16(off + 8 * (size_t)V);
-  w.rowstart = (unsigned long long*)(p + off); off = sm_align16(off + 8 * (size_t)V);
-  w.p0 = (int4*)(p + off); off = sm_align16(off + 16 * (size_t)V);
-  w.p1 = (int4*)(p + off); off = sm_align16(off + 16 * (size_t)V);
-  w.nsum = (long long*)(p + off); off = sm_align16(off + 24 * (size_t)V);
+  w.base = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)scan_blocks(V));
+  w.deg = (uint32_t*)(p + off); off = align16(off + 4 * (size_t)V);
+  w.cursor = (uint32_t*)(p + off); off = align16(off + 4 * (size_t)V);
+  w.h = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)V);
+  w.rowstart = (unsigned long long*)(p + off); off = align16(off + 8 * (size_t)V);
+  w.p0 = (int4*)(p + off); off = align16(off + 16 * (size_t)V);
+  w.p1 = (int4*)(p + off); off = align16(off + 16 * (size_t)V);
+  w.nsum = (long long*)(p + off); off = align16(off + 24 * (size_t)V);
   w.nbr = (int32_t*)(p + off);
   return w;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- runs of equal ids in a wave
-// the first lane of the run of equal `id`s this lane lies in (the lanes of a wave hold consecutive faces); every lane takes part
-__device__ __forceinline__ uint32_t sm_run_first(int32_t id, uint32_t lane, bool& last) {
-  const int32_t before = __shfl_up(id, 1, 64);
-  const unsigned long long heads = __ballot(lane == 0 || before != id);
-  const unsigned long long upto = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
-  last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
-  return 63u - (uint32_t)__clzll((long long)upto);      // (bit 0 of heads is set: upto != 0)
-}
-
-// inclusive wrapping sum of x over the lanes first .. lane of this lane's run
-__device__ __forceinline__ unsigned long long sm_run_sum(unsigned long long x, uint32_t lane, uint32_t first) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = __shfl_up(x, d, 64);
-    if (lane >= first + (uint32_t)d) x += up;
-  }
-  return x;
 }
 
 __device__ __forceinline__ unsigned long long sm_mix(int32_t id) {
@@ -105,20 +72,12 @@ __device__ __forceinline__ unsigned long long sm_mix(int32_t id) {
   return z ^ (z >> 31);
 }
 
-// the three ids of face f, or -1, -1, -1 for a face past the end or with an id outside [0, V): nothing of such a face is used
-__device__ __forceinline__ void sm_face(const int32_t* __restrict__ faces, uint32_t f, uint32_t F, uint32_t V, int32_t id[3]) {
-  id[0] = id[1] = id[2] = -1;
-  if (f >= F) return;
-  const int32_t a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if ((uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V) { id[0] = a; id[1] = b; id[2] = c; }      // (a negative id is a large unsigned one)
-}
-
 // ---------------------------------------------------------------------------------------------------------------- adjacency
-__global__ __launch_bounds__(SM_THREADS) void smooth_degree_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, uint32_t* deg,
+__global__ __launch_bounds__(MESH_THREADS) void smooth_degree_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F, uint32_t* deg,
                                                                    unsigned long long* h) {
-  const uint32_t f = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   int32_t id[3];
-  sm_face(faces, f, F, V, id);
+  load_face(faces, f, F, V, id);
   unsigned long long m[3] = {0, 0, 0};
   if (id[0] >= 0) {
 #pragma unroll
@@ -126,100 +85,57 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_degree_kernel(const int32_t
   }
 #pragma unroll
   for (int j = 0; j < 3; ++j) {                              // corner j: next = j + 1, prev = j + 2 (every lane runs the shuffles)
-    bool last;
-    const uint32_t first = sm_run_first(id[j], lane, last);
-    const unsigned long long sum = sm_run_sum(m[(j + 1) % 3] - m[(j + 2) % 3], lane, first);
-    if (id[j] >= 0 && last) {                                // id[j] < V
+    unsigned long long heads;
+    const uint32_t first = run_first(id[j], lane, heads);
+    const unsigned long long sum = run_sum(m[(j + 1) % 3] - m[(j + 2) % 3], lane, first);
+    if (id[j] >= 0 && run_last(heads, lane)) {               // id[j] < V
       atomicAdd(deg + id[j], 2u * (lane - first + 1u));
       atomicAdd(h + id[j], sum);
     }
   }
 }
 
-__global__ __launch_bounds__(SM_OFF_THREADS) void smooth_offsets_kernel(const uint32_t* __restrict__ deg, uint32_t V,
+__global__ __launch_bounds__(MESH_PER_THREADS) void smooth_offsets_kernel(const uint32_t* __restrict__ deg, uint32_t V,
                                                                         unsigned long long* __restrict__ rowstart,
                                                                         unsigned long long* __restrict__ base) {
-  __shared__ unsigned long long wave_sum[SM_OFF_WAVES];
+  __shared__ unsigned long long wave_sum[MESH_PER_WAVES];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t i0 = blockIdx.x * (uint32_t)SM_SCAN + SM_PER * tid;
-  uint32_t d[SM_PER];
+  const uint32_t i0 = blockIdx.x * (uint32_t)MESH_SCAN + MESH_PER * tid;
+  uint32_t d[MESH_PER];
   unsigned long long own = 0;
 #pragma unroll
-  for (int j = 0; j < SM_PER; ++j) {
+  for (int j = 0; j < MESH_PER; ++j) {
     d[j] = i0 + j < V ? deg[i0 + j] : 0u;
     own += d[j];
   }
-  unsigned long long incl = own;
+  unsigned long long total;
+  unsigned long long excl = block_scan_exclusive<unsigned long long, MESH_PER_WAVES, false>(own, wave_sum, lane, wave, total);
 #pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const unsigned long long up = __shfl_up(incl, s, 64);
-    if (lane >= (uint32_t)s) incl += up;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  unsigned long long below = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < SM_OFF_WAVES; ++k) {
-    const unsigned long long s = wave_sum[k];
-    if ((uint32_t)k < wave) below += s;
-    total += s;
-  }
-  unsigned long long excl = below + incl - own;
-#pragma unroll
-  for (int j = 0; j < SM_PER; ++j) {
+  for (int j = 0; j < MESH_PER; ++j) {
     if (i0 + j < V) rowstart[i0 + j] = excl;
     excl += d[j];
   }
   if (tid == 0) base[blockIdx.x] = total;
 }
 
-// a[na]: exclusive scan in place
-__global__ __launch_bounds__(SM_SCAN) void smooth_scan_kernel(unsigned long long* __restrict__ a, uint32_t na) {
-  __shared__ unsigned long long wave_sum[SM_WAVES];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry = 0;
-  for (uint32_t first = 0; first < na; first += SM_SCAN) {    // (the trip count is the same in every thread: the barriers inside are uniform)
-    const uint32_t j = first + tid;
-    const unsigned long long own = j < na ? a[j] : 0ull;
-    unsigned long long incl = own;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const unsigned long long up = __shfl_up(incl, s, 64);
-      if (lane >= (uint32_t)s) incl += up;
-    }
-    __syncthreads();                            // the previous trip's wave_sum has been read
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    unsigned long long below = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < SM_WAVES; ++k) {
-      const unsigned long long s = wave_sum[k];
-      if ((uint32_t)k < wave) below += s;
-      total += s;
-    }
-    if (j < na) a[j] = carry + below + incl - own;
-    carry += total;
-  }
-}
-
-__global__ __launch_bounds__(SM_THREADS) void smooth_fill_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F,
+__global__ __launch_bounds__(MESH_THREADS) void smooth_fill_kernel(const int32_t* __restrict__ faces, uint32_t V, uint32_t F,
                                                                  const unsigned long long* __restrict__ base,
                                                                  const unsigned long long* __restrict__ rowstart, uint32_t* cursor,
                                                                  unsigned long long entries, int32_t* __restrict__ nbr) {
-  const uint32_t f = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   int32_t id[3];
-  sm_face(faces, f, F, V, id);
+  load_face(faces, f, F, V, id);
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    bool last;
-    const uint32_t first = sm_run_first(id[j], lane, last);
-    const unsigned long long run = __ballot(last);           // the last lane of this lane's run: the lowest set bit at or above this lane
+    unsigned long long heads;
+    const uint32_t first = run_first(id[j], lane, heads);
+    const unsigned long long run = __ballot(run_last(heads, lane));      // the last lane of this lane's run: the lowest set bit at or above this lane
     const uint32_t end = (uint32_t)__ffsll((long long)(run >> lane)) - 1u + lane;
     uint32_t slot = 0;
     if (id[j] >= 0 && lane == first) slot = atomicAdd(cursor + id[j], 2u * (end - first + 1u));
     slot = __shfl(slot, (int)first, 64) + 2u * (lane - first);
     if (id[j] >= 0) {
-      const unsigned long long at = base[(uint32_t)id[j] >> SM_SCAN_SHIFT] + rowstart[id[j]] + slot;
+      const unsigned long long at = base[(uint32_t)id[j] >> MESH_SCAN_SHIFT] + rowstart[id[j]] + slot;
       if (at + 1 < entries) {                                // entries = 6 F, the room nbr has; slot + 1 < deg[id] when the faces are those degree saw
         nbr[at] = id[(j + 1) % 3];
         nbr[at + 1] = id[(j + 2) % 3];
@@ -229,10 +145,10 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_fill_kernel(const int32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- smooth
-__global__ __launch_bounds__(SM_THREADS) void smooth_quantise_kernel(const float* __restrict__ vertices, uint32_t V, double lo0, double lo1, double lo2,
+__global__ __launch_bounds__(MESH_THREADS) void smooth_quantise_kernel(const float* __restrict__ vertices, uint32_t V, double lo0, double lo1, double lo2,
                                                                      double scale, const uint32_t* __restrict__ deg,
                                                                      const unsigned long long* __restrict__ h, int pin_border, int4* __restrict__ p) {
-  const uint32_t v = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x;
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const double lo[3] = {lo0, lo1, lo2};
   int32_t q[3];
@@ -258,17 +174,17 @@ __device__ __forceinline__ int32_t sm_relax(int32_t p, long long s, uint32_t d, 
   return (int32_t)r;
 }
 
-__global__ __launch_bounds__(SM_THREADS) void smooth_pass_kernel(const int4* __restrict__ p, uint32_t V, const unsigned long long* __restrict__ base,
+__global__ __launch_bounds__(MESH_THREADS) void smooth_pass_kernel(const int4* __restrict__ p, uint32_t V, const unsigned long long* __restrict__ base,
                                                                  const unsigned long long* __restrict__ rowstart, const int32_t* __restrict__ nbr,
                                                                  unsigned long long entries, double w, int4* __restrict__ out) {
-  const uint32_t v = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   uint32_t d = 0;
   unsigned long long start = 0;
   int4 own = make_int4(0, 0, 0, 0);
   if (v < V) {
     own = p[v];
     d = (uint32_t)own.w;                                       // 0: the vertex stays
-    start = base[v >> SM_SCAN_SHIFT] + rowstart[v];
+    start = base[v >> MESH_SCAN_SHIFT] + rowstart[v];
     if (start + d > entries) d = 0;                            // (never, for the workspace adjacency left: a row read stays inside nbr)
   }
   long long s[3] = {0, 0, 0};
@@ -317,9 +233,9 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_pass_kernel(const int4* __r
   out[v] = own;
 }
 
-__global__ __launch_bounds__(SM_THREADS) void smooth_output_kernel(const int4* __restrict__ p, uint32_t V, double lo0, double lo1, double lo2,
+__global__ __launch_bounds__(MESH_THREADS) void smooth_output_kernel(const int4* __restrict__ p, uint32_t V, double lo0, double lo1, double lo2,
                                                                    double inv_scale, float* __restrict__ out) {
-  const uint32_t v = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x;
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const int4 q = p[v];
   out[3 * (size_t)v] = (float)(lo0 + (double)q.x * inv_scale);      // (2^-k: the product is ldexp's)
@@ -334,11 +250,11 @@ __device__ __forceinline__ long long sm_fixed64(double c, double scale) {
   return (long long)rint(fmin(fmax(t, -lim), lim));
 }
 
-__global__ __launch_bounds__(SM_THREADS) void normals_sum_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces, uint32_t V,
+__global__ __launch_bounds__(MESH_THREADS) void normals_sum_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces, uint32_t V,
                                                                  uint32_t F, double scale, long long* nsum) {
-  const uint32_t f = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+  const uint32_t f = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x, lane = threadIdx.x & 63;
   int32_t id[3];
-  sm_face(faces, f, F, V, id);
+  load_face(faces, f, F, V, id);
   unsigned long long q[3] = {0, 0, 0};
   if (id[0] >= 0) {
     double a[3], e1[3], e2[3];
@@ -354,20 +270,19 @@ __global__ __launch_bounds__(SM_THREADS) void normals_sum_kernel(const float* __
   }
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    bool last;
-    const uint32_t first = sm_run_first(id[j], lane, last);
-    unsigned long long sum[3];
+    unsigned long long heads, sum[3];
+    const uint32_t first = run_first(id[j], lane, heads);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) sum[k] = sm_run_sum(q[k], lane, first);
-    if (id[j] >= 0 && last) {
+    for (int k = 0; k < 3; ++k) sum[k] = run_sum(q[k], lane, first);
+    if (id[j] >= 0 && run_last(heads, lane)) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) atomicAdd((unsigned long long*)nsum + 3 * (size_t)id[j] + k, sum[k]);
     }
   }
 }
 
-__global__ __launch_bounds__(SM_THREADS) void normals_finish_kernel(const long long* __restrict__ nsum, uint32_t V, float* __restrict__ out) {
-  const uint32_t v = blockIdx.x * (uint32_t)SM_THREADS + threadIdx.x;
+__global__ __launch_bounds__(MESH_THREADS) void normals_finish_kernel(const long long* __restrict__ nsum, uint32_t V, float* __restrict__ out) {
+  const uint32_t v = blockIdx.x * (uint32_t)MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const long long* n = nsum + 3 * (size_t)v;
   const double x = (double)n[0], y = (double)n[1], z = (double)n[2];
@@ -378,115 +293,88 @@ __global__ __launch_bounds__(SM_THREADS) void normals_finish_kernel(const long l
   out[3 * (size_t)v + 2] = zero ? 0.0f : (float)(z / len);
 }
 
-// ---------------------------------------------------------------------------------------------------------------- host
-static int sm_fail(int code, const char* who, const char* what) {
-  static thread_local char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_error(code, msg);
-}
-
-static int sm_sizes(const char* who, int64_t V, int64_t F) {
-  if (V < 0 || F < 0) return sm_fail(CRNERF_ERR_SHAPE, who, "negative size");
-  if (V > SM_MAX || F > SM_MAX) return sm_fail(CRNERF_ERR_SHAPE, who, "more than 2^31 - 1 vertices or faces in one call");
-  return 0;
-}
-
-static inline uint32_t sm_launch_blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
 }  // namespace crnerf
 
+// ---------------------------------------------------------------------------------------------------------------- host
 using namespace crnerf;
 
-#define SM_REQUIRE(p, who, name) \
-  if (!(p)) return sm_fail(CRNERF_ERR_NULL, who, name " is NULL")
-#define SM_ALIGNED(p, who) \
-  if ((uintptr_t)(p) & 15u) return sm_fail(CRNERF_ERR_CONFIG, who, "workspace must be 16-byte aligned")
-#define SM_FILL(p, byte, bytes, who) \
-  if (hipMemsetAsync(p, byte, bytes, st) != hipSuccess) return sm_fail(CRNERF_ERR_HIP, who, "hipMemsetAsync failed")
-
 extern "C" size_t crnerf_mesh_smooth_workspace_bytes(int64_t V, int64_t F) {
-  if (V <= 0 || F < 0 || V > SM_MAX || F > SM_MAX) return 0;
-  return (size_t)8 * sm_blocks((uint32_t)V) + (size_t)80 * (size_t)V + (size_t)24 * (size_t)F + SM_WORKSPACE_PAD;
+  if (V <= 0 || F < 0 || V > MESH_MAX || F > MESH_MAX) return 0;
+  return (size_t)8 * scan_blocks((uint32_t)V) + (size_t)80 * (size_t)V + (size_t)24 * (size_t)F + SM_WORKSPACE_PAD;
 }
 
 extern "C" int crnerf_mesh_adjacency_i32(const int32_t* faces, int64_t V, int64_t F, void* workspace, void* stream) {
   static const char* who = "mesh_adjacency";
-  if (int rc = sm_sizes(who, V, F)) return rc;
+  if (int rc = mesh_sizes(who, V, F)) return rc;
   if (V == 0) return 0;
-  SM_REQUIRE(workspace, who, "workspace");
-  if (F > 0) SM_REQUIRE(faces, who, "faces");
-  SM_ALIGNED(workspace, who);
+  MESH_REQUIRE(workspace, who, "workspace");
+  if (F > 0) MESH_REQUIRE(faces, who, "faces");
+  MESH_ALIGNED(workspace, who);
   hipStream_t st = (hipStream_t)stream;
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const SmWorkspace w = sm_carve(workspace, v);
   // deg, cursor and h lie one behind the other; the roundings between them are zeroed with them
-  SM_FILL(w.deg, 0, (size_t)((char*)w.rowstart - (char*)w.deg), who);
+  MESH_FILL(w.deg, 0, (size_t)((char*)w.rowstart - (char*)w.deg), st, who);
+  const uint32_t fblocks = launch_blocks(f, MESH_THREADS);
   if (f > 0) {
-    hipLaunchKernelGGL(smooth_degree_kernel, dim3(sm_launch_blocks(f, SM_THREADS)), dim3(SM_THREADS), 0, st, faces, v, f, w.deg, w.h);
-    if (int rc = check_launch("smooth_degree_kernel")) return rc;
+    if (int rc = mesh_launch(smooth_degree_kernel, "smooth_degree_kernel", fblocks, MESH_THREADS, st, faces, v, f, w.deg, w.h)) return rc;
   }
-  hipLaunchKernelGGL(smooth_offsets_kernel, dim3(sm_blocks(v)), dim3(SM_OFF_THREADS), 0, st, w.deg, v, w.rowstart, w.base);
-  if (int rc = check_launch("smooth_offsets_kernel")) return rc;
-  hipLaunchKernelGGL(smooth_scan_kernel, dim3(1), dim3(SM_SCAN), 0, st, w.base, sm_blocks(v));
-  if (int rc = check_launch("smooth_scan_kernel")) return rc;
-  if (f > 0) {
-    hipLaunchKernelGGL(smooth_fill_kernel, dim3(sm_launch_blocks(f, SM_THREADS)), dim3(SM_THREADS), 0, st, faces, v, f, w.base, w.rowstart, w.cursor,
-                       6ull * f, w.nbr);
-    if (int rc = check_launch("smooth_fill_kernel")) return rc;
-  }
+  if (int rc = mesh_launch(smooth_offsets_kernel, "smooth_offsets_kernel", scan_blocks(v), MESH_PER_THREADS, st, w.deg, v, w.rowstart, w.base)) return rc;
+  if (int rc = mesh_block_scan(st, ScanList<0>{w.base, scan_blocks(v), {}})) return rc;
+  if (f > 0)
+    return mesh_launch(smooth_fill_kernel, "smooth_fill_kernel", fblocks, MESH_THREADS, st, faces, v, f, w.base, w.rowstart, w.cursor, 6ull * f, w.nbr);
   return 0;
 }
 
 extern "C" int crnerf_mesh_smooth_f32(const float* vertices, int64_t V, int64_t F, float lo0, float lo1, float lo2, int32_t k, int32_t steps,
                                       double lambda, double mu, int32_t pin_border, void* workspace, float* out_vertices, void* stream) {
   static const char* who = "mesh_smooth";
-  if (int rc = sm_sizes(who, V, F)) return rc;
-  if (steps < 0) return sm_fail(CRNERF_ERR_SHAPE, who, "negative steps");
-  if (steps > SM_MAX_STEPS) return sm_fail(CRNERF_ERR_SHAPE, who, "more than 65,536 steps");
-  if (!std::isfinite(lambda) || fabs(lambda) > 2.0) return sm_fail(CRNERF_ERR_SHAPE, who, "a lambda that is not finite or has |lambda| > 2");
-  if (!std::isfinite(mu) || fabs(mu) > 2.0) return sm_fail(CRNERF_ERR_SHAPE, who, "a mu that is not finite or has |mu| > 2");
-  if (k < -100 || k > 100) return sm_fail(CRNERF_ERR_SHAPE, who, "k outside [-100, 100]");
-  if (!std::isfinite(lo0) || !std::isfinite(lo1) || !std::isfinite(lo2)) return sm_fail(CRNERF_ERR_SHAPE, who, "a box origin that is not finite");
+  if (int rc = mesh_sizes(who, V, F)) return rc;
+  if (steps < 0) return launch_fail(CRNERF_ERR_SHAPE, who, "negative steps");
+  if (steps > SM_MAX_STEPS) return launch_fail(CRNERF_ERR_SHAPE, who, "more than 65,536 steps");
+  if (!std::isfinite(lambda) || fabs(lambda) > 2.0) return launch_fail(CRNERF_ERR_SHAPE, who, "a lambda that is not finite or has |lambda| > 2");
+  if (!std::isfinite(mu) || fabs(mu) > 2.0) return launch_fail(CRNERF_ERR_SHAPE, who, "a mu that is not finite or has |mu| > 2");
+  if (k < -100 || k > 100) return launch_fail(CRNERF_ERR_SHAPE, who, "k outside [-100, 100]");
+  if (!std::isfinite(lo0) || !std::isfinite(lo1) || !std::isfinite(lo2)) return launch_fail(CRNERF_ERR_SHAPE, who, "a box origin that is not finite");
   if (V == 0) return 0;
-  SM_REQUIRE(vertices, who, "vertices"); SM_REQUIRE(workspace, who, "workspace"); SM_REQUIRE(out_vertices, who, "out_vertices");
-  SM_ALIGNED(workspace, who);
+  MESH_REQUIRE(vertices, who, "vertices"); MESH_REQUIRE(workspace, who, "workspace"); MESH_REQUIRE(out_vertices, who, "out_vertices");
+  MESH_ALIGNED(workspace, who);
   hipStream_t st = (hipStream_t)stream;
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const SmWorkspace w = sm_carve(workspace, v);
-  const uint32_t blocks = sm_launch_blocks(v, SM_THREADS);
-  hipLaunchKernelGGL(smooth_quantise_kernel, dim3(blocks), dim3(SM_THREADS), 0, st, vertices, v, (double)lo0, (double)lo1, (double)lo2, ldexp(1.0, k),
-                     w.deg, w.h, pin_border ? 1 : 0, w.p0);
-  if (int rc = check_launch("smooth_quantise_kernel")) return rc;
+  const uint32_t blocks = launch_blocks(v, MESH_THREADS);
+  if (int rc = mesh_launch(smooth_quantise_kernel, "smooth_quantise_kernel", blocks, MESH_THREADS, st, vertices, v, (double)lo0, (double)lo1, (double)lo2,
+                           ldexp(1.0, k), w.deg, w.h, pin_border ? 1 : 0, w.p0))
+    return rc;
   int4* from = w.p0;
   int4* to = w.p1;
   for (int32_t pass = 0; pass < 2 * steps; ++pass) {
-    hipLaunchKernelGGL(smooth_pass_kernel, dim3(blocks), dim3(SM_THREADS), 0, st, from, v, w.base, w.rowstart, w.nbr, 6ull * f,
-                       (pass & 1) ? mu : lambda, to);
-    if (int rc = check_launch("smooth_pass_kernel")) return rc;
+    if (int rc = mesh_launch(smooth_pass_kernel, "smooth_pass_kernel", blocks, MESH_THREADS, st, from, v, w.base, w.rowstart, w.nbr, 6ull * f,
+                             (pass & 1) ? mu : lambda, to))
+      return rc;
     int4* t = from; from = to; to = t;
   }
-  hipLaunchKernelGGL(smooth_output_kernel, dim3(blocks), dim3(SM_THREADS), 0, st, from, v, (double)lo0, (double)lo1, (double)lo2, ldexp(1.0, -k),
+  return mesh_launch(smooth_output_kernel, "smooth_output_kernel", blocks, MESH_THREADS, st, from, v, (double)lo0, (double)lo1, (double)lo2, ldexp(1.0, -k),
                      out_vertices);
-  return check_launch("smooth_output_kernel");
 }
 
 extern "C" int crnerf_mesh_vertex_normals_f32(const float* vertices, const int32_t* faces, int64_t V, int64_t F, int32_t k2, void* workspace,
                                               float* out_normals, void* stream) {
   static const char* who = "mesh_vertex_normals";
-  if (int rc = sm_sizes(who, V, F)) return rc;
-  if (k2 < -300 || k2 > 300) return sm_fail(CRNERF_ERR_SHAPE, who, "k2 outside [-300, 300]");
+  if (int rc = mesh_sizes(who, V, F)) return rc;
+  if (k2 < -300 || k2 > 300) return launch_fail(CRNERF_ERR_SHAPE, who, "k2 outside [-300, 300]");
   if (V == 0) return 0;
-  SM_REQUIRE(workspace, who, "workspace"); SM_REQUIRE(out_normals, who, "out_normals");
-  if (F > 0) { SM_REQUIRE(vertices, who, "vertices"); SM_REQUIRE(faces, who, "faces"); }
-  SM_ALIGNED(workspace, who);
+  MESH_REQUIRE(workspace, who, "workspace"); MESH_REQUIRE(out_normals, who, "out_normals");
+  if (F > 0) { MESH_REQUIRE(vertices, who, "vertices"); MESH_REQUIRE(faces, who, "faces"); }
+  MESH_ALIGNED(workspace, who);
   hipStream_t st = (hipStream_t)stream;
   const uint32_t v = (uint32_t)V, f = (uint32_t)F;
   const SmWorkspace w = sm_carve(workspace, v);
-  SM_FILL(w.nsum, 0, 24 * (size_t)V, who);
+  MESH_FILL(w.nsum, 0, 24 * (size_t)V, st, who);
   if (f > 0) {
-    hipLaunchKernelGGL(normals_sum_kernel, dim3(sm_launch_blocks(f, SM_THREADS)), dim3(SM_THREADS), 0, st, vertices, faces, v, f, ldexp(1.0, k2), w.nsum);
-    if (int rc = check_launch("normals_sum_kernel")) return rc;
+    if (int rc = mesh_launch(normals_sum_kernel, "normals_sum_kernel", launch_blocks(f, MESH_THREADS), MESH_THREADS, st, vertices, faces, v, f, ldexp(1.0, k2),
+                             w.nsum))
+      return rc;
   }
-  hipLaunchKernelGGL(normals_finish_kernel, dim3(sm_launch_blocks(v, SM_THREADS)), dim3(SM_THREADS), 0, st, w.nsum, v, out_normals);
-  return check_launch("normals_finish_kernel");
+  return mesh_launch(normals_finish_kernel, "normals_finish_kernel", launch_blocks(v, MESH_THREADS), MESH_THREADS, st, w.nsum, v, out_normals);
 }
