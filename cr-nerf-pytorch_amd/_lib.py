@@ -234,7 +234,7 @@ HEADER_SIGNATURES = {"crnerf.h": {
     "crnerf_loss_backward_f32": (i32, [ctypes.POINTER(LossArgs), vp, ctypes.POINTER(LossGrads), vp]),
     "crnerf_grid_sample_batch_f32": (i32, [ctypes.POINTER(BatchArgs), vp]),
     "crnerf_adam_max_tensors": (i32, []),
-    "crnerf_adam_step_f32": (i32, [vp, vp, vp, vp, i32, pp, i32, f32, f32, f32, f32, f32, f32, vp]),
+    "crnerf_adam_step_f32": (i32, [vp, vp, vp, vp, i32, pp, i32, f32, f64, f64, f32, f32, f32, vp]),
     "crnerf_conv2d_f32": (i32, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp]),
     "crnerf_conv2d_backward_f32": (i32, [ctypes.POINTER(ConvGeom), vp, vp, vp, vp, vp, vp]),
     "crnerf_bn_prelu_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, f32, i32, vp]),

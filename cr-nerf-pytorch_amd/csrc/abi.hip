@@ -906,13 +906,14 @@ int crnerf_grid_sample_batch_round_f32(const crnerf_batch_args* a, void* stream)
 int crnerf_adam_max_tensors(void) { return ADAM_MAX_TENSORS; }
 
 int crnerf_adam_step_f32(float* params, float* exp_avg, float* exp_avg_sq, const int32_t* blocks, int32_t n_blocks, const float* const* grads,
-                         int32_t n_tensors, float step_size, float beta1, float beta2, float eps, float weight_decay, float bias_correction2_sqrt,
+                         int32_t n_tensors, float step_size, double beta1, double beta2, float eps, float weight_decay, float bias_correction2_sqrt,
                          void* stream) {
   if (n_blocks <= 0) return 0;
   REQUIRE(params, "params"); REQUIRE(exp_avg, "exp_avg"); REQUIRE(exp_avg_sq, "exp_avg_sq"); REQUIRE(blocks, "blocks"); REQUIRE(grads, "grads");
   if (n_tensors <= 0 || n_tensors > ADAM_MAX_TENSORS) return set_error(CRNERF_ERR_SHAPE, "adam_step: n_tensors outside 1 ... crnerf_adam_max_tensors()");
   if (!(bias_correction2_sqrt > 0.0f) || !(eps >= 0.0f)) return set_error(CRNERF_ERR_CONFIG, "adam_step: bias_correction2_sqrt must be positive and eps non-negative");
-  const AdamHyper h{step_size, beta1, beta2, eps, weight_decay, bias_correction2_sqrt};
+  // 1 - beta in double, rounded once: what torch.optim.Adam hands its fp32 kernels (1.0f - (float)0.999 is 1.3e-5 relative off)
+  const AdamHyper h{step_size, (float)beta1, (float)beta2, eps, weight_decay, bias_correction2_sqrt, (float)(1.0 - beta1), (float)(1.0 - beta2)};
   return launch_adam_step(params, exp_avg, exp_avg_sq, blocks, n_blocks, grads, n_tensors, h, (hipStream_t)stream);
 }
 

@@ -266,7 +266,7 @@ int launch_grid_batch(const BatchArgs& a, hipStream_t stream);
 int launch_grid_batch_round(const BatchArgs& a, hipStream_t stream);   // the same gather with rintf for floorf (the Blender batcher's .round())
 constexpr int ADAM_MAX_TENSORS = 448;             // gradient pointers ride in the kernel arguments (3.5 KB of the 4 KB)
 constexpr int ADAM_BLOCK_ELEMS = 4096;            // elements one workgroup updates
-struct AdamHyper { float step_size, beta1, beta2, eps, weight_decay, bias_correction2_sqrt; };
+struct AdamHyper { float step_size, beta1, beta2, eps, weight_decay, bias_correction2_sqrt, one_minus_beta1, one_minus_beta2; };   // beta1 itself is not read by the update
 int launch_adam_step(float* p, float* m, float* v, const int* blocks, int n_blocks, const float* const* grads, int n_tensors,
                      const AdamHyper& h, hipStream_t stream);
 

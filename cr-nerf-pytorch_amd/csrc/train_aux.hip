@@ -186,8 +186,8 @@ struct AdamGradPtrs { const float* g[ADAM_MAX_TENSORS]; };
 
 __device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, const AdamHyper& h) {
   if (h.weight_decay != 0.0f) g = fmaf(h.weight_decay, p, g);
-  m = m + (g - m) * (1.0f - h.beta1);                         // exp_avg.lerp_(grad, 1 - beta1)
-  v = h.beta2 * v + (1.0f - h.beta2) * g * g;            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+  m = m + (g - m) * h.one_minus_beta1;                        // exp_avg.lerp_(grad, 1 - beta1); the weights are (float)(1 - beta), formed in double by the entry
+  v = h.beta2 * v + h.one_minus_beta2 * g * g;                // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
   const float denom = sqrtf(v) / h.bias_correction2_sqrt + h.eps;
   p = p - h.step_size * (m / denom);                          // param.addcdiv_(exp_avg, denom, value=-step_size)
 }

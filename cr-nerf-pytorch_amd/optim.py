@@ -12,8 +12,10 @@ Scope: the optimiser STEP is on the training step's critical path (SURVEY 8f N4 
 and are not mirrored: `FlatAdam(get_parameters(models), lr=hparams.lr, eps=1e-8, weight_decay=hparams.weight_decay)` is the reference's
 'adam' branch, and any torch.optim.lr_scheduler drives it like any other optimiser.
 
-Same update as `torch.optim.Adam` (amsgrad / maximize / capturable off): tests/test_gpu_optim.py steps both on the same
-gradients.  A parameter whose `.grad` is None is skipped; its step count is the group's (torch keeps one per parameter --
+Same update as `torch.optim.Adam` (amsgrad / maximize / capturable off), parameters AND both moments: the betas reach the entry as
+doubles and the moment weights are (float)(1 - beta) with the subtraction in double, as torch forms them (1.0f - (float)0.999 is 1.3e-5
+relative away, and `exp_avg_sq` is what state_dict() writes into a checkpoint).  tests/test_gpu_optim.py steps both on the same gradients and
+compares all three; tests/test_gpu_train_aux_exact.py holds the kernel bit for bit to a NumPy restatement of its fp32 arithmetic.  A parameter whose `.grad` is None is skipped; its step count is the group's (torch keeps one per parameter --
 they only differ for a parameter that misses steps, which no module of this pipeline does; `load_state_dict` therefore REFUSES an
 optimiser state whose parameters of one group hold different step counts instead of resuming it with the wrong bias correction).
 """

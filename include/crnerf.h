@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define CRNERF_ABI_VERSION 2    /* 2: crnerf_render_args grew the in-kernel random-draw fields (appended), crnerf_rng_fill_f32 */
+#define CRNERF_ABI_VERSION 3    /* 2: crnerf_render_args grew the in-kernel random-draw fields (appended), crnerf_rng_fill_f32 */
+                                /* 3: crnerf_adam_step_f32 takes beta1 / beta2 as double (1 - beta is formed in double, as torch.optim.Adam does) */
 
 #define CRNERF_OK 0
 #define CRNERF_ERR_NULL (-1)     /* required pointer is NULL */
@@ -536,10 +537,12 @@ int crnerf_grid_sample_batch_f32(const crnerf_batch_args* args, void* stream);
  * parameter has no gradient this step and is skipped, as torch skips `p.grad is None`).  blocks[n_blocks][4] (device, int32):
  * {tensor index, flat offset, element count, offset inside the tensor} per workgroup -- built once by the host.
  * step_size = lr / (1 - beta1^t), bias_correction2_sqrt = sqrt(1 - beta2^t) for step t (1-based), computed by the host in
- * double like torch/optim/adam.py.  n_tensors <= crnerf_adam_max_tensors() per call. */
+ * double like torch/optim/adam.py.  beta1 / beta2 come as double for the same reason: the moment weights are (float)(1 - beta)
+ * with the subtraction in double, as torch forms them -- 1.0f - (float)beta is 1.3e-5 relative away for beta2 = 0.999.
+ * n_tensors <= crnerf_adam_max_tensors() per call. */
 int crnerf_adam_max_tensors(void);
 int crnerf_adam_step_f32(float* params, float* exp_avg, float* exp_avg_sq, const int32_t* blocks, int32_t n_blocks,
-                         const float* const* grads, int32_t n_tensors, float step_size, float beta1, float beta2, float eps,
+                         const float* const* grads, int32_t n_tensors, float step_size, double beta1, double beta2, float eps,
                          float weight_decay, float bias_correction2_sqrt, void* stream);
 
 /* -------- evaluation metrics: metrics.py:4-20 (mse / psnr / ssim) on a region of interest of an image pair, e.g. the

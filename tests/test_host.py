@@ -77,7 +77,7 @@ def test_library_exports_every_declared_symbol():
     for name in header_symbols():
         assert hasattr(lib, name), name
     lib.crnerf_abi_version.restype = ctypes.c_int
-    assert lib.crnerf_abi_version() == 2
+    assert lib.crnerf_abi_version() == 3
     lib.crnerf_packed_mlp_bytes.restype = ctypes.c_size_t
     assert lib.crnerf_packed_mlp_bytes() == 11264 + 2416 * 1024
     # the split-precision packs: three bf16 pieces per weight (f32x3; dir_encoding padded to whole stages and queue turns), two fp16 pieces (f32h2)

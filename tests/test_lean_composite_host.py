@@ -61,7 +61,7 @@ def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(n
         assert fn(ctypes.byref(_args(128)), None) == -2                       # a coarse-weights entry renders the coarse pass alone
         assert fn(ctypes.byref(_args(ni, n_samples=1)), None) == -2
         assert fn(ctypes.byref(_args(ni, packed_coarse=None)), None) == -1
-    assert _abi.bound("crnerf_abi_version")() == 2
+    assert _abi.bound("crnerf_abi_version")() == 3
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f32", "bf16_hc", "nonsense"])

@@ -45,7 +45,7 @@ def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(n
     assert fn(ctypes.byref(_args(z_coarse_out=4096)), None) == -3
     assert fn(ctypes.byref(_args(packed_fine=None)), None) == -1
     assert b"packed_fine" in _abi.last_error()
-    assert _abi.bound("crnerf_abi_version")() == 2
+    assert _abi.bound("crnerf_abi_version")() == 3
 
 
 @pytest.mark.parametrize("precision", ["f32x3", "f32h2", "auto"])

@@ -60,7 +60,7 @@ def test_built_library_exports_the_entry_and_it_refuses_before_any_device_work(n
     for over in (dict(rng_flags=1), dict(z_coarse_out=4096), dict(noise_coarse_out=4096), dict(noise_fine_out=4096)):
         assert fn(ctypes.byref(_args(**over)), None) == -3, over              # CRNERF_ERR_CONFIG: no draws in the lean kernels
         assert _last_error().startswith(b"render_rays_lean: no in-kernel random draws")
-    assert _abi.bound("crnerf_abi_version")() == 2
+    assert _abi.bound("crnerf_abi_version")() == 3
 
 
 # ---------------------------------------------------------------- ops.render_rays_lean_x

@@ -169,4 +169,4 @@ def test_abi_workspace_and_tile_constants():
     assert lib.crnerf_image_metrics_workspace_bytes(3, tw, th) == 3 * 16              # one tile per channel, two doubles each
     assert lib.crnerf_image_metrics_workspace_bytes(3, tw + 1, th + 1) == 3 * 4 * 16
     assert lib.crnerf_image_metrics_workspace_bytes(3, 0, 5) == 0
-    assert lib.crnerf_abi_version() == 2
+    assert lib.crnerf_abi_version() == 3

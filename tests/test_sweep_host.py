@@ -45,7 +45,7 @@ def test_header_constants_and_struct_match_the_binding():
 def test_built_library_exports_the_entries():
     for name in SYMBOLS:
         _abi.bound(name)
-    assert _abi.bound("crnerf_abi_version")() == 2
+    assert _abi.bound("crnerf_abi_version")() == 3
 
 
 def _weights(hole=None):
