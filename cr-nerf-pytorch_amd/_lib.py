@@ -356,7 +356,13 @@ STAGED_SMOOTH_SIGNATURES = {"crnerf_mesh_smooth.h": {     # Taubin smoothing and
     "crnerf_mesh_smooth_f32": (i32, [vp, i64, i64, f32, f32, f32, i32, i32, f64, f64, i32, vp, vp, vp]),
     "crnerf_mesh_vertex_normals_f32": (i32, [vp, vp, i64, i64, i32, vp, vp, vp]),
 }}
-_staged = [n for mapping in STAGED_MAPPINGS + (STAGED_SMOOTH_SIGNATURES,) for table in mapping.values() for n in table]
+# A fourth staged mapping of the same form (tests/test_mesh_smooth_host.py pins the third to its one header): load() binds it behind the third.
+STAGED_PHOTO_SIGNATURES = {"crnerf_mesh_photo.h": {       # photo colours for meshes: a z-buffer per posed view, then project / test / sample / average
+    "crnerf_mesh_zbuffer_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, i64, i64, f64, vp, vp]),
+    "crnerf_mesh_photo_colors_u8": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, f64, f64, vp, vp, vp]),
+}}
+_STAGED_ALL = STAGED_MAPPINGS + (STAGED_SMOOTH_SIGNATURES, STAGED_PHOTO_SIGNATURES)      # every staged mapping, in binding order
+_staged = [n for mapping in _STAGED_ALL for table in mapping.values() for n in table]
 if len(set(_staged)) != len(_staged) or set(_staged) & set(EXPORTS):
     raise ImportError("crnerf_amd._lib: a staged entry is declared twice: %s" % sorted(n for n in _staged if _staged.count(n) > 1 or n in EXPORTS))
 
@@ -386,7 +392,7 @@ def load():
                                      % (LIB_PATH, name, header_of(name))) from None
             fn.restype = res
             fn.argtypes = args
-        for header, table in itertools.chain.from_iterable(mapping.items() for mapping in STAGED_MAPPINGS + (STAGED_SMOOTH_SIGNATURES,)):
+        for header, table in itertools.chain.from_iterable(mapping.items() for mapping in _STAGED_ALL):
             for name, (res, args) in table.items():
                 try:
                     fn = getattr(lib, name)

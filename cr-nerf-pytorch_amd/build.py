@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrnerf_hip.so")
 STAMP = os.path.join(HERE, ".build_stamp")
 SOURCES = ["abi.hip", "pack.hip", "mlp_forward16.hip", "render_fused16.hip", "mlp_forward_bf16p.hip", "sigma_query16.hip", "sigma_query_bf16p.hip", "feature_query16.hip", "feature_query_bf16p.hip", "mlp_forward_x3.hip", "mlp_forward_h2.hip", "render_fused_h2.hip", "mlp_backward_x3.hip", "mlp_backward_h2.hip", "render_fused_bf16p.hip", "render_fused_bf16p_f16.hip", "mlp_forward_bf16p_f16.hip", "render_fused_x3.hip", "render_fused_lean_x3.hip", "render_fused_lean_h2.hip", "mlp_train16.hip", "mlp_gemm_bf16.hip", "train_aux.hip", "ray_kernels.hip", "raygen.hip", "encoder.hip", "encoder_train.hip", "cgnet.hip", "cgnet_chain.hip",
-           "crossray.hip", "peer_xchg.hip", "metrics.hip", "lpips.hip", "imageprep.hip", "scenebounds.hip", "rgbaprep.hip", "mesh.hip", "mesh_parts.hip", "mesh_simplify.hip", "mesh_smooth.hip"]
+           "crossray.hip", "peer_xchg.hip", "metrics.hip", "lpips.hip", "imageprep.hip", "scenebounds.hip", "rgbaprep.hip", "mesh.hip", "mesh_parts.hip", "mesh_simplify.hip", "mesh_smooth.hip", "mesh_photo.hip"]
 INCLUDE = os.path.join(HERE, "..", "include")
 HEADERS = (sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
            + ["../../include/" + f for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")])   # every header: any edit rebuilds
@@ -40,7 +40,9 @@ PER_FILE_FLAGS = {# pragma-unroll-threshold: the tile loop of the 22-k-step laye
                   # the unit tools/isa_audit.py flags for SGPR spill reloads in front of its LDS-DMA statements (csrc/mlp_core.h "HAZARD")
                   "mlp_forward_h2.hip": ["-DCRNERF_GLDS_SALU_COPY"],
                   # marching tetrahedra: `sigma > threshold` is false for a NaN node and a non-finite t falls back to 0.5 (include/crnerf_mesh.h)
-                  "mesh.hip": ["-fhonor-nans"]}
+                  "mesh.hip": ["-fhonor-nans"],
+                  # photo colours: `z >= z_near`, the range tests of u and v and `g > 0` are false for a NaN (csrc/crnerf_mesh_photo.h)
+                  "mesh_photo.hip": ["-fhonor-nans"]}
 for _kv in os.environ.get("CRNERF_EXTRA_FILE_FLAGS", "").split(";"):      # tuning builds only: "mlp_train16.hip=-fno-slp-vectorize -DX;other.hip=..."
     if "=" in _kv:
         PER_FILE_FLAGS.setdefault(_kv.split("=", 1)[0].strip(), []).extend(_kv.split("=", 1)[1].split())

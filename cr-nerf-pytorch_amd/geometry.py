@@ -16,6 +16,10 @@ what mesh extraction, occupancy visualisation and point-cloud export start from 
     Mesh.smooth(steps=10, lam=0.5, mu=-0.53)      a new Mesh after Taubin's lambda | mu smoothing, normals recomputed from the smoothed faces;
                                                   extract_mesh(..., smooth_steps=s) ends with it
     Mesh.recompute_normals()                      a new Mesh with area-weighted normals derived from its faces (a mesh that had none included)
+    Views(Ks, c2ws, sizes)                        N posed pinhole views (scene.prepare_scene's Ks / poses as they are): the device tables, .pack / .split
+    Mesh.depth_maps(views)                        a list of [H,W] float32 depths of the mesh in the views, +inf where it does not cover
+    photo_colors(vertices, photos, views, ...)    ([n,3], [n]) colours of points by reprojection of posed photos, and the views that counted
+    Mesh.colorize_from_photos(photos, views)      a new Mesh with the colours of the photographs: z-buffer, project, test, sample, average
 
 One launch each (include/crnerf_geometry.h): the coordinates are all that is read, the embedding is built in registers and the weight stream is
 walked up to the sigma head only.  `model` is a NeRF_sigma; its packed_weights(precision) is the pack.  precision "f32" or "bf16".
@@ -33,6 +37,10 @@ its cells; a few steps of Taubin's lambda | mu smoothing take both out without t
 built once a call, every pass is a gather over it; positions on a 2^30 integer lattice and neighbour sums in 64-bit integers -- the same bytes
 on every run, whatever the order of the faces.  Normals are then re-derived from the faces, area-weighted, from integer sums again.  One
 read-back, of the bounding box.  The order of a pipeline: floaters, simplify, smooth, colorize.
+Photo colours (csrc/crnerf_mesh_photo.h): colorize decodes features under one style image; colorize_from_photos gives the mesh the colours of
+the posed photographs themselves -- every vertex is projected into every photo, the views in which it is occluded (a z-buffer of the mesh per
+view, drawn first) or faces away are dropped, and what the others see is averaged, from integer sums: the same bytes on every run.  No
+read-back.  The order of a pipeline: floaters, simplify, smooth, then either colorize.
 Inference only; GPU tensors only: like every op of the package there is no CPU fallback.
 
 Domain: |coordinate| < 64.  Below it the kernels' embedding is the routine the stand-alone posenc uses (which switches to ocml's sincosf there);
@@ -42,6 +50,7 @@ reads them back); sigma_points does not check its points.
 import math
 import struct
 
+import numpy as np
 import torch
 
 from . import ops
@@ -249,6 +258,37 @@ class Mesh:
         _, e = _lattice_box(self.vertices, "crnerf_amd.geometry: recompute_normals")
         return Mesh(self.vertices, self.faces, ops.mesh_vertex_normals(self.vertices, self.faces, 44 - 2 * e), self.colors)
 
+    @torch.no_grad()
+    def depth_maps(self, views, z_near=1e-3):
+        """The z-buffer of this mesh in every view of `views` (a Views; csrc/crnerf_mesh_photo.h states every rule): a list of [H,W] float32
+        tensors -- views of one flat buffer, views.split's --, the depth along the optical axis of the nearest face at each pixel and +inf
+        where the mesh does not cover.  Both orientations of a face are drawn; a face with a corner nearer than z_near (or behind the camera)
+        is not drawn at all: there is no near-plane clipping.  An empty mesh gives maps of +inf."""
+        return views.split(_zbuffer(self, views, z_near))
+
+    @torch.no_grad()
+    def colorize_from_photos(self, photos, views, occlusion=True, facing=True, depth_tol=0.02, z_near=1e-3, fallback=None):
+        """A new Mesh with colors [V,3] float32 in [0,1] taken from posed photographs (same vertices, faces and normals, not copied):
+        photo_colors at the vertices.  photos: a list of uint8 [H,W,3] arrays or tensors, one per view of `views` (a Views), or views.pack's
+        buffer.  occlusion=True draws the z-buffer of THIS mesh first (depth_maps) and drops a view in which the vertex lies behind it by more
+        than the factor 1 + depth_tol: a smaller tolerance rejects grazing views, in which the depth changes fast across a pixel; a larger one
+        lets background leak onto the surface at silhouettes.  facing=True hands the normals over when the mesh has them: a view the surface
+        faces away from does not count.  z_near: a vertex (and for the z-buffer a face with a corner) nearer to a camera than this is ignored
+        by that camera.  A vertex no view sees takes `fallback` [V,3] if given, else the mesh's existing colour if it has colours, else 0.5
+        grey.  An empty mesh gives an empty mesh, without a launch.  Order: floaters, simplify, smooth, then this."""
+        V = self.vertices.shape[0]
+        if fallback is not None and (not torch.is_tensor(fallback) or tuple(fallback.shape) != (V, 3)):
+            raise ValueError("crnerf_amd.geometry: colorize_from_photos: fallback must be a [%d,3] tensor" % V)
+        if V == 0:
+            _check_views(views, "colorize_from_photos")
+            return Mesh(self.vertices, self.faces, self.normals, self.vertices.new_empty((0, 3)))
+        depths = _zbuffer(self, views, z_near) if occlusion else None
+        colors, seen = photo_colors(self.vertices, photos, views, normals=self.normals if facing else None, depths=depths, depth_tol=depth_tol,
+                                    z_near=z_near)
+        rest = fallback if fallback is not None else self.colors
+        rest = torch.full_like(colors, 0.5) if rest is None else rest.to(colors.device, torch.float32)
+        return Mesh(self.vertices, self.faces, self.normals, torch.where((seen > 0)[:, None], colors, rest))
+
     def save_ply(self, path):
         """Binary little-endian PLY: float32 x y z (and nx ny nz when the mesh has normals, then uchar red green blue when it has colors:
         (c.clamp(0, 1) * 255) truncated) per vertex, `uchar int` vertex_indices per face.  Copies to the host itself; needs no third-party package."""
@@ -282,6 +322,114 @@ class Mesh:
             out.write(header.encode("ascii"))
             out.write(vrows.numpy().tobytes())
             out.write(rows.numpy().tobytes())
+
+
+class Views:
+    """N posed pinhole views as the three device tables of csrc/crnerf_mesh_photo.h, built once.  Ks: N 3x3 intrinsics (fx = K[0][0],
+    fy = K[1][1], cx = K[0][2], cy = K[1][2]); c2ws: N 3x4 camera-to-world poses in the training rays' convention (x right, y up, looking
+    along -z) -- datasets.scene.prepare_scene's sc.Ks / sc.poses go in as they are, float64 is kept --; sizes: N (W, H) pairs.  The views lie
+    one behind the other in a flat buffer of total_pixels pixels.  ValueError, before the device is needed: wrong shapes, an entry that is
+    not finite, a W or H outside [2, 16384].
+    .n, .sizes [(W, H)], .offsets [int], .total_pixels; .cams [N,16] float64, .dims [N,2] int32, .offset_table [N] int64 on the device;
+    .split(flat) -> the list of [H,W] (or [H,W,3]) views of a flat [total_pixels] (or [total_pixels,3]) buffer; .pack(photos) -> the flat
+    uint8 [total_pixels,3] device buffer of a list of uint8 [H,W,3] photos."""
+    __slots__ = ("n", "sizes", "offsets", "total_pixels", "cams", "dims", "offset_table")
+
+    def __init__(self, Ks, c2ws, sizes, device="cuda"):
+        what = "crnerf_amd.geometry: Views"
+        try:
+            K, P = _host_f64(Ks), _host_f64(c2ws)
+            sizes = [tuple(s) for s in sizes]
+            wh = [(int(w), int(h)) for w, h in sizes]
+            exact = all(w == a and h == b for (w, h), (a, b) in zip(wh, sizes))
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("%s expects Ks as N 3x3 intrinsics, c2ws as N 3x4 poses and sizes as N (W, H) pairs of ints" % what) from None
+        N = len(wh)
+        if N == 0 and K.numel() == 0 and P.numel() == 0:      # no view: the tables are empty
+            K, P = K.reshape(0, 3, 3), P.reshape(0, 3, 4)
+        if K.dim() != 3 or tuple(K.shape) != (N, 3, 3) or tuple(P.shape) != (N, 3, 4) or not exact:
+            raise ValueError("%s expects Ks [N,3,3], c2ws [N,3,4] and N (W, H) pairs of ints, got %s, %s and %d sizes"
+                             % (what, tuple(K.shape), tuple(P.shape), N))
+        if not (bool(torch.isfinite(K).all()) and bool(torch.isfinite(P).all())):
+            raise ValueError("%s: an entry of Ks or c2ws is not finite" % what)
+        for w, h in wh:
+            if not (2 <= w <= 16384 and 2 <= h <= 16384):
+                raise ValueError("%s: a view of %d x %d; W and H must lie in [2, 16384]" % (what, w, h))
+        cams = torch.cat((K[:, 0, 0:1], K[:, 1, 1:2], K[:, 0, 2:3], K[:, 1, 2:3], P[:, :, :3].reshape(N, 9), P[:, :, 3]), dim=1)
+        offsets, total = [], 0
+        for w, h in wh:
+            offsets.append(total)
+            total += w * h
+        self.n, self.sizes, self.offsets, self.total_pixels = N, wh, offsets, total
+        self.cams = cams.contiguous().to(device)
+        self.dims = torch.tensor(wh, dtype=torch.int32).reshape(N, 2).to(device)
+        self.offset_table = torch.tensor(offsets, dtype=torch.int64).to(device)
+
+    def split(self, flat):
+        """The views of a flat buffer [total_pixels] or [total_pixels, C] as a list of [H,W] or [H,W,C] tensors (views of it, not copies)."""
+        if not torch.is_tensor(flat) or flat.dim() not in (1, 2) or flat.shape[0] != self.total_pixels:
+            raise ValueError("crnerf_amd.geometry: Views.split expects a [%d] or [%d,C] tensor" % (self.total_pixels, self.total_pixels))
+        return [flat[o:o + w * h].reshape((h, w) + tuple(flat.shape[1:])) for o, (w, h) in zip(self.offsets, self.sizes)]
+
+    def pack(self, photos):
+        """One flat uint8 [total_pixels,3] device buffer of the photos: a list of N uint8 [H,W,3] arrays or tensors, on the host or the
+        device.  ValueError: a count, dtype or shape that does not match its view."""
+        what = "crnerf_amd.geometry: Views.pack"
+        photos = list(photos)
+        if len(photos) != self.n:
+            raise ValueError("%s: %d photos for %d views" % (what, len(photos), self.n))
+        rows = []
+        for k, (img, (w, h)) in enumerate(zip(photos, self.sizes)):
+            t = torch.as_tensor(img)
+            if t.dtype != torch.uint8 or tuple(t.shape) != (h, w, 3):
+                raise ValueError("%s: photo %d must be uint8 [%d,%d,3] ([H,W,3] of its view), got %s %s" % (what, k, h, w, t.dtype, tuple(t.shape)))
+            rows.append(t)
+        dev = self.cams.device
+        if not rows:
+            return torch.empty(0, 3, dtype=torch.uint8, device=dev)
+        if all(t.device.type == "cpu" for t in rows):      # host photos: one buffer on the host, one upload
+            return torch.cat([t.reshape(-1, 3) for t in rows]).to(dev)
+        return torch.cat([t.reshape(-1, 3).to(dev) for t in rows])
+
+
+def _host_f64(a):
+    """A tensor, an array or a (nested) sequence of either as one float64 tensor on the host; float64 input keeps its bits."""
+    if torch.is_tensor(a):
+        return a.detach().to("cpu", torch.float64)
+    if isinstance(a, (list, tuple)) and len(a) and all(torch.is_tensor(t) for t in a):
+        return torch.stack([t.detach().to("cpu", torch.float64) for t in a])
+    return torch.from_numpy(np.array(a, dtype=np.float64))
+
+
+def _check_views(views, what):
+    if not isinstance(views, Views):
+        raise ValueError("crnerf_amd.geometry: %s: views must be a geometry.Views" % what)
+    return views
+
+
+def _zbuffer(mesh, views, z_near):
+    """The flat depth buffer of the mesh in the views."""
+    v = _check_views(views, "depth_maps")
+    return ops.mesh_zbuffer(mesh.vertices, mesh.faces, v.cams, v.dims, v.offset_table, v.total_pixels, z_near)
+
+
+@torch.no_grad()
+def photo_colors(vertices, photos, views, normals=None, depths=None, depth_tol=0.02, z_near=1e-3):
+    """(colors [n,3] float32 in [0,1], n_views [n] int32) of the points vertices [n,3] by reprojection of posed photos (csrc/crnerf_mesh_photo.h
+    states every rule): every point is projected into every view of `views` (a Views); a view counts when the point is at least z_near in front
+    of it, inside the photo, faces the camera (normals [n,3] given and not zero) and is not occluded (depths given); the counting views'
+    bilinear samples are averaged.  Zeros, and n_views 0, where no view counts.  photos: a list of uint8 [H,W,3] arrays, as for views.pack, or
+    the packed buffer.  depths: the flat buffer or the list of Mesh.depth_maps, or None for no occlusion test -- depths along the optical
+    axis, NOT the renderer's along-ray depths.  depth_tol: a point may lie behind the z-buffer by the factor 1 + depth_tol; a smaller
+    tolerance rejects grazing views, a larger one lets background leak at silhouettes."""
+    v = _check_views(views, "photo_colors")
+    packed = photos if torch.is_tensor(photos) else v.pack(photos)
+    if depths is not None and not torch.is_tensor(depths):
+        depths = list(depths)
+        if len(depths) != v.n or any(not torch.is_tensor(d) or tuple(d.shape) != (h, w) for d, (w, h) in zip(depths, v.sizes)):
+            raise ValueError("crnerf_amd.geometry: photo_colors: depths must be the flat buffer or the list of [H,W] maps of Mesh.depth_maps")
+        depths = torch.cat([d.reshape(-1) for d in depths]) if depths else torch.empty(0, dtype=torch.float32, device=v.cams.device)
+    return ops.mesh_photo_colors(vertices, normals, packed, depths, v.cams, v.dims, v.offset_table, v.total_pixels, z_near, depth_tol)
 
 
 class MeshParts:

@@ -784,6 +784,74 @@ def mesh_vertex_normals(vertices, faces, k2):
     return out
 
 
+def _photo_views(cams, dims, offsets, total_pixels, z_near, what, on_device):
+    """The three view tables of csrc/crnerf_mesh_photo.h held to their shapes and dtypes, total_pixels and z_near to what the library accepts.
+    Returns (cams, dims, offsets pointers or None, N, total_pixels, z_near)."""
+    cp = _parts_input(cams, "cams", what, torch.float64, cols=16, on_device=on_device)
+    N = cams.shape[0]
+    dp = _parts_input(dims, "dims", what, torch.int32, cols=2, rows=N, on_device=on_device)
+    op = _parts_input(offsets, "offsets", what, torch.int64, rows=N, on_device=on_device)
+    if isinstance(total_pixels, bool) or int(total_pixels) != total_pixels or not 0 <= int(total_pixels) <= 2 ** 40:
+        raise ValueError("crnerf_amd: %s: total_pixels must be an int in [0, 2^40], got %r" % (what, total_pixels))
+    z_near = float(z_near)
+    if not (math.isfinite(z_near) and z_near > 0.0):
+        raise ValueError("crnerf_amd: %s: z_near must be finite and > 0, got %r" % (what, z_near))
+    return cp, dp, op, N, int(total_pixels), z_near
+
+
+def mesh_zbuffer(vertices, faces, cams, dims, offsets, total_pixels, z_near):
+    """The z-buffer of an indexed mesh in N posed pinhole views, on the device (csrc/crnerf_mesh_photo.h states every rule: corners projected in
+    float64, screen coordinates on a 1/16-pixel lattice, coverage by exact integer edge functions with an inclusive test, perspective-correct
+    depth along the optical axis through an atomic minimum; no near-plane clipping, no culling; a view whose table entry does not fit the
+    buffer is skipped; content deterministic and independent of the order of the faces).  vertices [V,3] float32, faces [F,3] int32,
+    cams [N,16] float64 (fx, fy, cx, cy, R row-major, t), dims [N,2] int32 (W, H), offsets [N] int64: contiguous, on the device, as they are;
+    total_pixels: an int; z_near: a float > 0.  Returns the flat float32 depth [total_pixels], +inf where nothing is drawn.  No read-back."""
+    what = "mesh_zbuffer"
+    vp_ = fp = tables = None
+    for on_device in (False, True):      # every shape and dtype before any device
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        fp = _parts_input(faces, "faces", what, torch.int32, cols=3, on_device=on_device)
+        tables = _photo_views(cams, dims, offsets, total_pixels, z_near, what, on_device)
+    cp, dp, op, N, total, z_near = tables
+    depth = torch.empty(total, dtype=torch.float32, device=vertices.device)
+    if total:
+        _lib.check(_lib.load().crnerf_mesh_zbuffer_f32(vp_, fp, vertices.shape[0], faces.shape[0], cp, dp, op, N, total, z_near,
+                                                       ctypes.c_void_p(depth.data_ptr()), _lib.stream_ptr()), "crnerf_mesh_zbuffer_f32")
+    return depth
+
+
+def mesh_photo_colors(vertices, normals, photos, depth, cams, dims, offsets, total_pixels, z_near, depth_tol):
+    """Per-vertex colours by reprojection of N posed photos, on the device (csrc/crnerf_mesh_photo.h states every rule: a view counts for a
+    vertex when the vertex is in front of it, faces it -- normals given and not zero --, projects inside the photo and is not behind the
+    z-buffer by more than the factor 1 + depth_tol; the photo is sampled bilinearly in float64 and the samples are averaged from exact integer
+    sums; content deterministic).  vertices [V,3] float32, normals [V,3] float32 or None, photos [total_pixels,3] uint8 (the views' pixels, flat),
+    depth [total_pixels] float32 (mesh_zbuffer's) or None for no occlusion test, cams / dims / offsets as for mesh_zbuffer: contiguous, on the
+    device, as they are.  Returns (colors [V,3] float32 in [0,1], views [V] int32: the number of views that counted; zeros where none did).
+    No read-back."""
+    what = "mesh_photo_colors"
+    vp_ = np_ = pp = zp = tables = None
+    for on_device in (False, True):
+        vp_ = _parts_input(vertices, "vertices", what, torch.float32, cols=3, on_device=on_device)
+        V = vertices.shape[0]
+        np_ = None if normals is None else _parts_input(normals, "normals", what, torch.float32, cols=3, rows=V, on_device=on_device)
+        tables = _photo_views(cams, dims, offsets, total_pixels, z_near, what, on_device)
+        total = tables[4]
+        pp = _parts_input(photos, "photos", what, torch.uint8, cols=3, rows=total, on_device=on_device)
+        zp = None if depth is None else _parts_input(depth, "depth", what, torch.float32, rows=total, on_device=on_device)
+        if not on_device:
+            depth_tol = float(depth_tol)
+            if not (math.isfinite(depth_tol) and depth_tol >= 0.0):
+                raise ValueError("crnerf_amd: %s: depth_tol must be finite and >= 0, got %r" % (what, depth_tol))
+    cp, dp, op, N, total, z_near = tables
+    colors = torch.empty(V, 3, dtype=torch.float32, device=vertices.device)
+    views = torch.empty(V, dtype=torch.int32, device=vertices.device)
+    if V:
+        _lib.check(_lib.load().crnerf_mesh_photo_colors_u8(vp_, np_, V, pp, zp, cp, dp, op, N, total, z_near, depth_tol,
+                                                           ctypes.c_void_p(colors.data_ptr()), ctypes.c_void_p(views.data_ptr()),
+                                                           _lib.stream_ptr()), "crnerf_mesh_photo_colors_u8")
+    return colors, views
+
+
 def composite(raw, z, noise=None, noise_std=0.0):
     lib = _lib.load()
     raw, z = _f32c(raw, "raw"), _f32c(z, "z")
